@@ -6,11 +6,11 @@ One "step" = one pass of the hot path over one batch of l-channels per GPU, inpu
   channel) + the (l_ini, n0_ini) eigenvector and its WRITE_WF table on the rank that owns l_ini + the RCCL all-gather of the
   spectra.  The library's default route for k <= 9 is the BAND route (csrc/crawford.hip: the pencil stays banded at half-width 8,
   one-column chase on tiles of 8); the DENSE route (banded Cholesky -> standard form -> sy2sb -> two-step bulge chasing: north_star's letter) is measured
-  in the same run as `dense_two_stage` (a few extra untimed-for-`value` steps) and is what `--route 1` makes `value`.
+  with --full as `dense_two_stage` (a few extra untimed-for-`value` steps) and is what `--route 1` makes `value`.
 Workload (BASELINE configs[3], "Hydrogen l=0..127, N_bsp=4096"): KIND_GRID=0 ra=0 rb=800 k=9
 nfun=4096 Zatom=1.  The l-loop being sharded is reference matrices.f90:242-248.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1 without RANK in the environment: this process starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -19,14 +19,22 @@ line and exits with its code.  Under a launcher (RANK set) every rank runs `run(
 
 `value`: at N = 1 the 128 channels of BASELINE configs[3] on the one GPU.  At N > 1 the default is `--scaling strong`:
 BASELINE configs[3] exactly as written -- 128 channels in total, 128/N per GPU (round-3 verdict: the honest headline of an
-N-GPU line); the line also carries `weak_scaling` (every GPU solves `--channels` consecutive channels, rank r takes
-l = r*channels .. (r+1)*channels-1; cost per channel does not depend on l), measured in the same run (K more steps after the
-timed region of `value`, same barrier / max-over-ranks bracket).  `--scaling weak` swaps the two.  The shards come from bspatom_amd/parallel.py (channel_range, gather_spectra -- the
-code the gloo world-size-2 tests cover); no data-path collective except the final gather.
+N-GPU line); with --full the line also carries `weak_scaling` (every GPU solves `--channels` consecutive channels, rank r
+takes l = r*channels .. (r+1)*channels-1; cost per channel does not depend on l), measured in the same run (K more steps
+after the timed region of `value`, same barrier / max-over-ranks bracket).  `--scaling weak` swaps the two.  The shards come
+from bspatom_amd/parallel.py (channel_range, gather_spectra -- the code the gloo world-size-2 tests cover); no data-path
+collective except the final gather.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (whole path against the fp64 peak; per
-kernel: launch durations measured in THIS run with HIP events around every launch, in one extra untimed step) and
-`cpu_baseline` (the compiled reference oracle/_ref/ref_dump.x when present, else the CPU oracle port).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step),
+the configuration and the stage times of the timed steps.  A plain run does nothing else: set-up, W warm-up steps, the K
+timed steps, the outputs (--dump-outputs), the line.  --full adds what takes runs of its own: the other sharding (N > 1),
+`roofline` (whole path against the fp64 peak; per kernel: launch durations measured in THIS run with HIP events around
+every launch, in one extra untimed step), the Rydberg check of the spectra, `dense_two_stage`, `full_V` and `cpu_baseline`
+(the compiled reference oracle/_ref/ref_dump.x when present, else the CPU oracle port).
+
+--dump-outputs DIR writes what the last timed step computed, the arrays a caller of the path receives, as DIR/<name>.npy
+(float64): `spectra` (channels x nfun, the gathered eigenvalues), `eigvec` (the (l_ini, n0_ini) eigenvector) and its WRITE_WF
+table `wf_r`, `wf_u`.  The inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -217,7 +225,7 @@ def run(args):
             l0_, nl_ = parallel.channel_range(rank, world, total - 1)
         return total, cnts, l0_, nl_
 
-    modes = [args.scaling] + ([m for m in ("weak", "strong") if m != args.scaling] if world > 1 else [])
+    modes = [args.scaling] + ([m for m in ("weak", "strong") if m != args.scaling] if world > 1 and args.full else [])
     l_ini = 0
     total_max = max(shard(m)[0] for m in modes)
     if selftest:
@@ -257,7 +265,8 @@ def run(args):
                                    torch.arange(n, dtype=torch.float64).repeat(nl))
             if rank == owner and not selftest:     # owner of l_ini: the one eigenvector KIND_PI=0 consumes + WRITE_WF
                 c = prob.eigvec(l_ini, 1)
-                prob.write_wf(c)
+                state["eigvec"] = c
+                state["wf_r"], state["wf_u"] = prob.write_wf(c)
             # all-gather of the spectra: the only collective of the path (RCCL; at N = 1 under a launcher too).  E_dev is
             # rewritten by the next solve on the library's own stream, so the gather must have completed before the step ends.
             state["E_all"] = parallel.gather_spectra(E_dev[: nl * n], n, counts)
@@ -272,22 +281,30 @@ def run(args):
             step(True)
         sync()
         dt = time.perf_counter() - t0
+        outputs = None
+        if args.dump_outputs and mode == args.scaling:
+            # host copies now: at one rank E_all is a view of E_dev, which any later solve rewrites
+            outputs = {k: np.array(v) for k, v in state.items() if k != "E_all"}
+            if rank == 0:
+                outputs["spectra"] = np.array(state["E_all"].cpu())
         if use_dist:
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         return {"mode": mode, "total": total, "counts": counts, "l0": l0, "nl": nl, "owner": owner, "dt": dt,
-                "stage_ms": stage_ms / max(steps, 1), "E_all": state["E_all"],
+                "stage_ms": stage_ms / max(steps, 1), "E_all": state["E_all"], "outputs": outputs,
                 "value": total * steps / dt, "ms_per_step": 1e3 * dt / steps}
 
     recs = [measure(m, args.steps, args.warmup) for m in modes]
     main = recs[0]
     total, counts, nl = main["total"], main["counts"], main["nl"]
+    if main["outputs"] is not None:
+        dump_outputs(args.dump_outputs, main["outputs"])
 
-    # one more, UNTIMED step of the main sharding with HIP events around every launch of the big kernels (option "ktime")
+    # --full: one more, UNTIMED step of the main sharding with HIP events around every launch of the big kernels (option "ktime")
     ktimes = None
     kstage = None
-    if not selftest and nl > 0 and not args.no_kernel_timing:
+    if args.full and not selftest and nl > 0 and not args.no_kernel_timing:
         capi.set_option("ktime", 1)
         prob.solve_dev(main["l0"], nl, E_dev.data_ptr())
         ktimes = capi.kernel_times()
@@ -295,11 +312,11 @@ def run(args):
         kstage = prob.last_timing()
     sync()
 
-    # two extra legs, untimed for `value` (N = 1 only): the dense route (north_star's letter) when `value` came from the band route,
-    # and one call of bsp_dsygv_('V') -- all eigenvectors, the contract of the reference's call site (matrices.f90:248)
+    # --full: two extra legs, untimed for `value` (N = 1 only): the dense route (north_star's letter) when `value` came from the
+    # band route, and one call of bsp_dsygv_('V') -- all eigenvectors, the contract of the reference's call site (matrices.f90:248)
     route = prob.route() if not selftest else 0
     dense_leg = fullv_leg = None
-    if not selftest and world == 1 and nl > 0:
+    if args.full and not selftest and world == 1 and nl > 0:
         if route == 2 and not args.no_dense_leg:
             dense_leg = dense_route_leg(args, prob, capi, torch, main["l0"], nl, E_dev, n)
         if not args.no_full_v:
@@ -337,7 +354,9 @@ def run(args):
                         "channels_per_gpu": rec["counts"], "channels_total": rec["total"],
                         "stage_ms_per_step_rank0": dict(zip(["assemble", "chol_std", "sy2sb", "sb2st", "bisect", "total_device"],
                                                             [float(x) for x in rec["stage_ms"]]))}
-        if not selftest:
+        if not selftest and not args.full:
+            out.update(stage_report(route, main["stage_ms"]))
+        elif not selftest:
             out.update(report(args, world, n, prob.npad, main, ktimes, kstage, route))
             if dense_leg:
                 out["dense_two_stage"] = dense_leg
@@ -567,7 +586,6 @@ def report(args, world, n, npad, main, ktimes, kstage, route):
                                             "note": "F(n) = 4/3 n^3 + 4 n^2 k per channel: no implementation of the dense two-stage route can "
                                                     "exceed this rate on %d GPU(s); `dense_two_stage` is that route measured in this run" % world},
                 "traffic": pmc_total, "traffic_note": traffic_note, "kernels": kern, "kernel_timing_step_stage_ms": kstage}
-        names = STAGES_BAND
     else:
         kern, other = dense_kernel_entries(ktimes, npad, nl, pmc_bytes, pmc_file, pmc_stale, mfma, mfma_file, mfma_stale)
         ach = flop_dense(n, args.k) * main["value"] / 1e12
@@ -577,10 +595,34 @@ def report(args, world, n, npad, main, ktimes, kstage, route):
                          "matrix/vector peak of %d GPU(s)" % world,
                 "traffic": pmc_total, "traffic_note": traffic_note, "kernels": kern, "other_kernels_this_run": other,
                 "kernel_timing_step_stage_ms": kstage}
-        names = STAGES_DENSE
-    return {"roofline": roof, "route": {1: "dense", 2: "band"}[route],
-            "stage_ms_per_step_rank0": dict(zip(names + ["total_device"], [float(x) for x in stage_ms])),
-            "rydberg_max_rel_err_n<=8": ryd, "csrc_sha16": kernel_sources_sha()}
+    out = {"roofline": roof}
+    out.update(stage_report(route, stage_ms))
+    out.update({"rydberg_max_rel_err_n<=8": ryd, "csrc_sha16": kernel_sources_sha()})
+    return out
+
+
+def stage_report(route, stage_ms):
+    """the route the timed steps took and their stage times (library timing, per step)"""
+    names = STAGES_BAND if route == 2 else STAGES_DENSE
+    return {"route": {1: "dense", 2: "band"}[route],
+            "stage_ms_per_step_rank0": dict(zip(names + ["total_device"], [float(x) for x in stage_ms]))}
+
+
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float64.  Spectra above DUMP_MAX_BYTES keep a fixed, seeded sample of
+    their channels (rows), whose indices go to spectra_channels.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    E = arrays.get("spectra")
+    if E is not None and E.nbytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (E.shape[1] * 8)
+        rows = np.sort(np.random.default_rng(0).choice(E.shape[0], size=keep, replace=False))
+        arrays = dict(arrays, spectra=E[rows], spectra_channels=rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def main():
@@ -606,9 +648,16 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="skip the extra untimed step that brackets every launch with HIP events (profiler runs: the trace should hold "
                          "the timed steps only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what `value` does not need: the other sharding (N > 1), one step with per-launch kernel "
+                         "timing (roofline), the dense route, one bsp_dsygv_('V') call and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU rehearsal of the N-rank launch path (gloo, stand-in spectra, no GPU, no solve): tests only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.scaling is None:
         args.scaling = "strong" if args.gpus > 1 else "weak"
     if args.gpus > 1 and "RANK" not in os.environ:

@@ -61,12 +61,13 @@ LINK="$OPENBLAS -Wl,-rpath,$SCIPY_LIBS -lm"
 "$FC" $FFLAGS -c "$HERE/ref_handoff_driver.f90" -o ref_handoff_driver.o
 "$FC" -o "$OUT/ref_handoff.x" ref_handoff_driver.o Bsp_Atom_subs.o $COMMON $LINK
 # link-level drop-in: the reference's own objects against libbspatom_lapack.so (dsygv_ -> GPU).  The forwarder object
-# is compiled WITHOUT its dsygv_ (-DNO_DSYGV) so that the only definition of that symbol is the GPU library's.
+# is compiled WITHOUT its dsygv_ (-DNO_DSYGV) so that the only definition of that symbol is the GPU library's.  The library
+# is found relative to the binary ($ORIGIN), so the tree may be copied or moved after the build.
 PROD=$(cd "$HERE/../../bspatom_amd" && pwd)
 if [ -f "$PROD/libbspatom_lapack.so" ]; then
   gcc -O2 -DNO_DSYGV -c "$HERE/lapack_forward.c" -o lapack_forward_nodsygv.o
   "$FC" -o "$OUT/Bsp_Atom_gpu.x" Bsp_Atom.o ${COMMON/lapack_forward.o/lapack_forward_nodsygv.o} \
-        -L"$PROD" -lbspatom_lapack -lbspatom -Wl,-rpath,"$PROD" $LINK
+        -L"$PROD" -lbspatom_lapack -lbspatom -Wl,-rpath,'$ORIGIN/../../bspatom_amd' $LINK
   echo "build_ref: built $OUT/Bsp_Atom_gpu.x (dsygv_ from $PROD/libbspatom_lapack.so)"
 fi
 rm -f *.mod

@@ -19,7 +19,7 @@ def test_bench_under_torchrun_one_rank(scaling, route):
     port = 29600 + os.getpid() % 300 + (0 if scaling == "weak" else 1) + 2 * route
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-           "--nfun", "1024", "--rb", "200", "--channels", "8", "--scaling", scaling, "--no-cpu-baseline", "--route", str(route)]
+           "--nfun", "1024", "--rb", "200", "--channels", "8", "--scaling", scaling, "--no-cpu-baseline", "--route", str(route), "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
@@ -51,6 +51,31 @@ def test_bench_under_torchrun_one_rank(scaling, route):
         assert d["dense_two_stage"]["value"] > 0 and 0 < d["dense_two_stage"]["roofline"]["frac"] < 1
         assert d["full_V"]["unit"] == "channels/s" and d["full_V"]["check_64_vectors"]["max_S_orthonormality_defect"] < 1e-11
         assert d["roofline"]["dense_algorithm_ceiling"]["eigensolves_per_s_at_100_percent_of_fp64_peak"] > 0
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline keys and none of the extra legs, and --dump-outputs writes
+    what the last timed step computed: the spectra of every channel, the (l_ini, n0_ini) eigenvector and its WRITE_WF table."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--nfun", "1024",
+           "--rb", "200", "--channels", "8", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.split("\n") if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["unit"] == "eigensolves/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 2
+    assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "dense_two_stage", "full_V", "cpu_baseline"):
+        assert k not in d, k
+    E = np.load(out / "spectra.npy")
+    c = np.load(out / "eigvec.npy")
+    r, u = np.load(out / "wf_r.npy"), np.load(out / "wf_u.npy")
+    assert E.shape == (8, 1024) and c.shape == (1024,) and r.shape == u.shape == (10001,)
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in (E, c, r, u))
+    assert np.all(np.diff(E, axis=1) >= 0)
+    assert max(abs(E[0, i] + 0.5 / (i + 1) ** 2) * 2 * (i + 1) ** 2 for i in range(4)) < 1e-9     # Rydberg, l = 0, n <= 4
 
 
 def test_sharded_host_under_torchrun(tmp_path):

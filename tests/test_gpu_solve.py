@@ -1076,8 +1076,13 @@ def test_reference_binary_on_gpu_dsygv(tmp_path, name):
     if not os.path.exists(exe):
         pytest.skip("oracle/_ref/Bsp_Atom_gpu.x not built (needs /root/reference in the build container)")
     g = load_golden(name)
+    # the GPU library is the one this tree built: named to the loader, since the binary's own search path cannot reach it
+    # when oracle/_ref/ was built elsewhere or is reached through a link
+    libdir = os.path.join(ROOT, "bspatom_amd")
+    assert os.path.exists(os.path.join(libdir, "libbspatom_lapack.so")), "build() did not make bspatom_amd/libbspatom_lapack.so"
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join([libdir] + [p for p in [os.environ.get("LD_LIBRARY_PATH")] if p]))
     with open(golden_input(name)) as fin:
-        p = subprocess.run([exe], stdin=fin, cwd=tmp_path, capture_output=True, text=True, timeout=600)
+        p = subprocess.run([exe], stdin=fin, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert "Program Finished!" in p.stdout
     nch, nfun = g["E"].shape

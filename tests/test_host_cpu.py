@@ -241,14 +241,14 @@ def test_bench_starts_its_own_ranks_gloo(scaling):
     """`python bench.py --gpus 2` WITHOUT a launcher (the command the driver's N = 1 line generalises to): the parent must
     start `torch.distributed.run --nproc-per-node 2` as a child, stay off the GPU itself, and relay exactly one JSON line.
     Rehearsed on the CPU with --selftest-launcher (gloo, stand-in spectra, no solve): sharding, the all-gather, the barrier
-    bracket, the max over ranks and the one-line output are the code the GPU run uses.  At N > 1 the line carries BOTH
-    figures: the weak one (channels per GPU fixed) and configs[3] as stated (channels in total fixed); `value` is the one
+    bracket, the max over ranks and the one-line output are the code the GPU run uses.  With --full at N > 1 the line carries
+    BOTH figures: the weak one (channels per GPU fixed) and configs[3] as stated (channels in total fixed); `value` is the one
     --scaling names."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--nfun", "48",
-                        "--channels", "6", "--scaling", scaling, "--selftest-launcher"], cwd=ROOT, env=env, capture_output=True,
-                       text=True, timeout=300)
+                        "--channels", "6", "--scaling", scaling, "--selftest-launcher", "--full"], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.split("\n") if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), p.stdout           # stdout is the one line, nothing else
@@ -267,6 +267,28 @@ def test_bench_starts_its_own_ranks_gloo(scaling):
         other = d["weak_scaling"]
         assert other["scaling"] == "weak" and other["channels_per_gpu"] == [6, 6] and other["channels_total"] == 12
     assert other["value"] > 0 and other["steps"] == 2
+
+
+def test_plain_bench_run_measures_one_sharding_and_dumps_its_outputs(tmp_path):
+    """Without --full the N-rank run times the sharding --scaling names and nothing else (one collective per step and
+    warm-up step); --dump-outputs writes the gathered spectra of the last timed step (here the stand-ins) as float64."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--nfun", "48",
+                        "--channels", "6", "--scaling", "weak", "--selftest-launcher", "--dump-outputs", str(out)], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.split("\n") if l.strip()]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 12 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["config"]["collective_calls"] == 3 + 1 and "weak_scaling" not in d and "configs3_as_stated" not in d
+    assert sorted(os.listdir(out)) == ["spectra.npy"]
+    E = np.load(out / "spectra.npy")
+    assert E.dtype == np.float64 and E.shape == (12, 48)
+    assert np.array_equal(E, np.arange(12.0)[:, None] * 1e6 + np.arange(48.0)[None, :])
 
 
 def test_bench_refuses_a_world_size_it_was_not_asked_for():

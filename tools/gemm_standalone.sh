@@ -1,7 +1,8 @@
 # standalone durations of the sy2sb kernels (one pipeline, no look-ahead, so nothing overlaps): sums over one step
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
 export BSP_SY2SB_GROUPS=1 BSP_SY2SB_LOOKAHEAD=0
-rm -rf /tmp/px; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/px -o t -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline > /tmp/px.log 2>&1
+rm -rf /tmp/px; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/px -o t -- python3 $BENCH --steps 1 --warmup 0 --no-cpu-baseline --full > /tmp/px.log 2>&1
 f=$(find /tmp/px -name '*kernel_stats.csv' | head -1)
 python3 -c "
 import csv

@@ -15,5 +15,5 @@ python3 tools/mfma_util.py $O/mfma $O/mfma_util.json > $O/mfma_util.txt || true
 cp $(find $O/stats -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 python3 tools/valu_util.py $O/valu > $O/valu_util.txt 2>&1 || true
 find $O -name '*kernel_trace.csv' -delete; find $O -name '*agent_info.csv' -delete; find $O -name '*counter_collection.csv' -delete
-python3 bench.py --route $RT > $O/bench_line.json 2> $O/bench.err
+python3 bench.py --route $RT --full > $O/bench_line.json 2> $O/bench.err
 head -8 $O/kernel_stats.csv | cut -c1-170; cat $O/pmc_summary.txt; cat $O/mfma_util.txt; cat $O/valu_util.txt; tail -c 600 $O/bench_line.json

@@ -3,7 +3,7 @@ set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3a; rm -rf $O; mkdir -p $O
 cd $R
 timeout -k 10 900 python tools/make_ratchet.py > $O/ratchet.log 2>&1 && cp gpurun_out/accuracy_ratchet.json $O/
-timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench128.json 2> $O/bench128.err
+timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --full > $O/bench128.json 2> $O/bench128.err
 for c in 64 32 16; do
   timeout -k 10 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --channels $c > $O/bench$c.json 2> $O/bench$c.err
 done

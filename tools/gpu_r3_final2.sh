@@ -23,4 +23,4 @@ timeout -k 10 600 python tools/truth_report.py c3_1024_l31 c5_1024_k11 lin1024 c
 (make -C tools/microbench > /dev/null 2>&1; cd tools/microbench && echo "# barrier_lds" && ./barrier_lds && echo "# lds_rate" && ./lds_rate) > $O/microbench2.txt 2>&1
 bash tools/gpu_sb16_diag.sh 128 > $O/sb16_stamps.txt 2>&1
 bash tools/gpu_v8_v9.sh > $O/v8_v9.txt 2>&1; tail -12 $O/v8_v9.txt | cut -c1-200
-python3 bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json
+python3 bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json

@@ -7,7 +7,7 @@ echo "pytest exit $rc"; tail -12 $O/pytest.log | cut -c1-300
 [ $rc -ge 124 ] && exit $rc
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; }
 tail -3 $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r4d/bench_default.json'))
