@@ -33,7 +33,7 @@ class Sizes(C.Structure):
 
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
-           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_write_wf", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_write_wf", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -63,6 +63,8 @@ def lib():
         L.bspatom_solve_dev.argtypes = [vp, i32, i32, vp, vp]
         L.bspatom_eigvec.argtypes = [vp, i32, i32, vp]
         L.bspatom_eigvecs.argtypes = [vp, i32, i32, i32, vp]
+        L.bspatom_eigvecs_batch.argtypes = [vp, i32, i32, i32, i32, vp]
+        L.bspatom_eigvecs_batch_dev.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bspatom_dipole_elements.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
         L.bspatom_dipole_bands.argtypes = [vp, vp]
         L.bspatom_write_wf.argtypes = [vp, vp, i32, vp, vp]
@@ -179,6 +181,18 @@ class Problem:
         Z = np.zeros((count, self.nfun))
         _chk(lib().bspatom_eigvecs(self._h, l, n0, count, _p(Z)), "bspatom_eigvecs")
         return Z
+
+    def eigvecs_batch(self, l0, nl, n0, count):
+        """Eigenvectors n0 .. n0+count-1 (1-based) of channels l0 .. l0+nl-1 in one call: array (nl, count, nfun),
+        [c] bit-identical to eigvecs(l0 + c, n0, count)."""
+        Z = np.zeros((max(nl, 0), max(count, 0), self.nfun))
+        _chk(lib().bspatom_eigvecs_batch(self._h, l0, nl, n0, count, _p(Z)), "bspatom_eigvecs_batch")
+        return Z
+
+    def eigvecs_batch_dev(self, l0, nl, n0, count, dev_ptr):
+        """eigvecs_batch into device memory of this problem's device (nl * count * nfun doubles at dev_ptr, e.g. a torch
+        tensor's data_ptr()), written in place; returns when the vectors are there."""
+        _chk(lib().bspatom_eigvecs_batch_dev(self._h, l0, nl, n0, count, C.c_void_p(dev_ptr)), "bspatom_eigvecs_batch_dev")
 
     def dipole_elements(self, l_ini, n0_ini, l_fin, n0_fin, count, a):
         """D[i] = c(l_fin, n0_fin+i)^T (a[0] R_r + a[1] R_1/r + a[2] R_d/dr) c(l_ini, n0_ini), 1-based state numbers:

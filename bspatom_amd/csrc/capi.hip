@@ -773,6 +773,59 @@ extern "C" int bspatom_eigvecs(bspatom_problem *p, int l, int n0, int count, dou
     return invit_failed(p);
 }
 
+// bspatom_eigvecs for the channel range l0 .. l0+nl-1 in one persistent launch per group of channels (eigvec.hip::invit_batch_kernel):
+// the same vectors bit for bit.  Z: host memory (dev false: staged through a device buffer of at most EIGVECS_STAGE_BYTES, one
+// channel at least) or the caller's device memory (dev true: written in place).  The scratch is one slot per resident wave,
+// whatever nl * count is.
+static constexpr size_t EIGVECS_STAGE_BYTES = (size_t)256 << 20;
+static int eigvecs_batch_impl(bspatom_problem *p, int l0, int nl, int n0, int count, double *Z, bool dev)
+{
+    if (!p || !Z) return BSP_ERR_ARG;
+    const HostSetup &h = p->hs;
+    const int n = h.nfun;
+    if (nl < 1 || count < 1 || n0 < 1 || n0 + count - 1 > n || l0 < p->last_l0 || (long)l0 + nl > (long)p->last_l0 + p->last_nl)
+        return BSP_ERR_ARG;
+    BSP_HIP(hipSetDevice(p->device));
+    const int ch0 = l0 - p->last_l0;
+    const size_t per_ch = (size_t)count * n;         // doubles of one channel's block
+    size_t gmax = ((size_t)1 << 30) / count;          // channels per launch: items = group * count stays an int
+    const size_t gstage = EIGVECS_STAGE_BYTES / (per_ch * sizeof(double));
+    if (!dev && gstage < gmax) gmax = gstage;
+    if (gmax < 1) gmax = 1;
+    const int group = (size_t)nl < gmax ? nl : (int)gmax;
+    int slots = 0, rc;
+    if ((rc = invit_batch_slots(h.k, group * count, &slots))) return rc;
+    DevBuf work, stage;
+    if ((rc = work.alloc((size_t)slots * invit_batch_slot_doubles(n, h.k)))) return rc;
+    if (!dev && (rc = stage.alloc((size_t)group * per_ch))) return rc;
+    hipError_t e = hipMemsetAsync(p->d_info, 0, sizeof(int), p->st);
+    for (int c = 0; e == hipSuccess && c < nl; c += group) {
+        const int g = (nl - c < group) ? nl - c : group, items = g * count;
+        double *out = dev ? Z + (size_t)c * per_ch : stage.p;
+        rc = launch_inverse_iteration_batch(n, h.k, count, items, slots < items ? slots : items, p->d_SB,
+                                            p->d_HB + (size_t)(ch0 + c) * h.k * n, p->d_E + (size_t)(ch0 + c) * n + (n0 - 1),
+                                            work.p, out, p->d_info, p->st);
+        if (rc) break;
+        if (!dev) e = hipMemcpyAsync(Z + (size_t)c * per_ch, stage.p, (size_t)g * per_ch * sizeof(double), hipMemcpyDeviceToHost, p->st);
+    }
+    // every path waits for the stream before the scratch is freed (DevBuf) and before it returns
+    const hipError_t es = hipStreamSynchronize(p->st);
+    if (rc) return rc;
+    BSP_HIP(e);
+    BSP_HIP(es);
+    return invit_failed(p);
+}
+
+extern "C" int bspatom_eigvecs_batch(bspatom_problem *p, int l0, int nl, int n0, int count, double *Z)
+{
+    return eigvecs_batch_impl(p, l0, nl, n0, count, Z, false);
+}
+
+extern "C" int bspatom_eigvecs_batch_dev(bspatom_problem *p, int l0, int nl, int n0, int count, double *Z_dev)
+{
+    return eigvecs_batch_impl(p, l0, nl, n0, count, Z_dev, true);
+}
+
 extern "C" int bspatom_dipole_elements(bspatom_problem *p, int l_ini, int n0_ini, int l_fin, int n0_fin, int count,
                                        const double a[3], double *D)
 {

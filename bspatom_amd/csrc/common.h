@@ -235,6 +235,12 @@ int launch_inverse_iteration(int n, int k, int nvec, const double *d_SB, const d
                              const int *d_chan, const double *d_E, double *d_work, double *d_vec,
                              int *d_info, hipStream_t st);
 size_t invit_work_doubles(int n, int k);
+// the same vectors for a channel range, persistent grid (invit_batch_kernel): item it = c * count + j is eigenvalue E[c*n + j] of
+// channel c (HB + c*k*n), vector at d_vec + it*n; d_work: slots * invit_batch_slot_doubles, slots from invit_batch_slots
+size_t invit_batch_slot_doubles(int n, int k);
+int invit_batch_slots(int k, int items, int *slots);
+int launch_inverse_iteration_batch(int n, int k, int count, int items, int slots, const double *d_SB, const double *d_HB,
+                                   const double *d_E, double *d_work, double *d_vec, int *d_info, hipStream_t st);
 int launch_band_apply(int n, int k, const double *d_RB, const double a[3], const double *d_x, double *d_v, hipStream_t st);
 int launch_dots(int n, int m, const double *d_Z, const double *d_v, double *d_D, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,

@@ -61,9 +61,21 @@ __device__ __forceinline__ double ev_row0_max(double x)          // max over lan
 // round trip into every column of the factorisation.
 __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// BT >= b = k - 1: rows of the register window (instances 8 and 15).  One wavefront (lane = its lane); y: n doubles of LDS; work:
-// n (3 b + 3) doubles; *info <- iv + 1 if the iterate vanished.
-template <int BT>
+// Where y lives (invit_batch_kernel: in global memory, a slot of the work area, instead of LDS) changes what a pass boundary
+// must wait for.  RULE (y in global memory): a wave's own global stores of y must be COMPLETE (s_waitcnt vmcnt(0)) before the
+// pass that reads them -- lane 0 stores y[j] in the solves and lane j % 64 loads it in the next pass; lds_sync() waits for
+// LDS traffic only (lgkmcnt) and orders nothing in global memory.  The single-wave workgroup needs no s_barrier for it.
+template <bool YG>
+__device__ __forceinline__ void y_sync()
+{
+    if constexpr (YG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else lds_sync();
+}
+
+// BT >= b = k - 1: rows of the register window (instances 8 and 15).  One wavefront (lane = its lane); y: n doubles of LDS (YG false)
+// or of global memory (YG true: every pass boundary waits for the wave's global stores, y_sync); work: n (3 b + 3) doubles;
+// *info <- iv + 1 if the iterate vanished.  The arithmetic does not depend on YG.
+template <int BT, bool YG = false>
 __device__ __forceinline__ void invit_body(int n, int k, const double *__restrict__ SB, const double *__restrict__ HB, const double E,
                                            double *work, double *vec, int *info, int iv, double *y, const int lane)
 {
@@ -146,6 +158,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
     // ---- inverse iteration: 3 solves ----
     for (int j = lane; j < n; j += 64) y[j] = 1.0;
     __syncthreads();                                   // also: U, L, piv are in memory (vmcnt(0))
+    if constexpr (YG) y_sync<YG>();                    // (y_sync: y = 1 is in memory before the forward pass reads it)
     for (int iter = 0; iter < 3; ++iter) {
         // forward: y <- L^-1 P y.  The b + 1 entries y[j .. j + b] that step j can touch live in a REGISTER window, lane i holding
         // y[j + i]: the pivot value goes round by readlane, the window moves on by a one-lane DPP shift, the entry that enters
@@ -159,15 +172,26 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                 lvn[u] = (u < n && lane >= 1 && lane <= b) ? Lm[(size_t)u * b + lane - 1] : 0.0;
                 pvn[u] = (u < n) ? piv[u] : 0.0;
             }
+            // YG: the entering entries come from global memory, a block ahead, ONE per lane (lane u: step u's), and go round by
+            // readlane -- PF uniform loads kept in flight per block would hold 2 PF more VGPRs and cost the kernel a wave per SIMD.
+            // The entries read are above every index this pass has written when they are requested.
+            double yln = 0.0;
+            if constexpr (YG) yln = (lane < PF && lane + b + 1 < n) ? y[lane + b + 1] : 0.0;
             for (int j0 = 0; j0 < n; j0 += PF) {
                 double lv[PF], pvv[PF], yin[PF];         // multipliers, pivot rows, entering entries of PF steps: independent of the recurrence
+                double yl = 0.0;
+                if constexpr (YG) {
+                    yl = yln;
+                    yln = (lane < PF && j0 + PF + lane + b + 1 < n) ? y[j0 + PF + lane + b + 1] : 0.0;
+                }
 #pragma unroll
                 for (int u = 0; u < PF; ++u) {
                     const int j = j0 + u, jn = j + PF;
                     lv[u] = lvn[u]; pvv[u] = pvn[u];
                     lvn[u] = (jn < n && lane >= 1 && lane <= b) ? Lm[(size_t)jn * b + lane - 1] : 0.0;
                     pvn[u] = (jn < n) ? piv[jn] : 0.0;
-                    yin[u] = (j + b + 1 < n) ? y[j + b + 1] : 0.0;
+                    if constexpr (YG) yin[u] = ev_readlane(yl, u);
+                    else yin[u] = (j + b + 1 < n) ? y[j + b + 1] : 0.0;
                 }
 #pragma unroll
                 for (int u = 0; u < PF; ++u) {
@@ -187,7 +211,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                     }
                 }
             }
-            lds_sync();
+            y_sync<YG>();
         }
         // backward: x_j = (y_j - sum_{cc=1..2b} U[j][cc] x_{j+cc}) / U[j][0], the 2 b entries x[j + 1 .. j + 2 b] in a register window
         // likewise (lane cc holds x[j + cc]; zero beyond the matrix)
@@ -200,8 +224,16 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                 uvn[u] = (j >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)j * (2 * b + 1) + lane] : 0.0;
                 udn[u] = (j >= 0) ? U[(size_t)j * (2 * b + 1)] : 1.0;
             }
+            // YG: y[j] likewise, a block ahead and one per lane (lane u: step u's); below every index this pass has written
+            double ybn = 0.0;
+            if constexpr (YG) ybn = (lane < PF && n - 1 - lane >= 0) ? y[n - 1 - lane] : 0.0;
             for (int j0 = n - 1; j0 >= 0; j0 -= PF) {
                 double uv[PF], ru[PF], yv[PF];           // row j of U: lane cc holds U[j][cc]; 1 / U[j][0] and y[j] for every lane
+                double yb = 0.0;
+                if constexpr (YG) {
+                    yb = ybn;
+                    ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : 0.0;
+                }
 #pragma unroll
                 for (int u = 0; u < PF; ++u) {
                     const int j = j0 - u, jn = j - PF;
@@ -209,7 +241,8 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                     ru[u] = (j >= 0) ? 1.0 / udn[u] : 0.0;
                     uvn[u] = (jn >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)jn * (2 * b + 1) + lane] : 0.0;
                     udn[u] = (jn >= 0) ? U[(size_t)jn * (2 * b + 1)] : 1.0;
-                    yv[u] = (j >= 0) ? y[j] : 0.0;
+                    if constexpr (YG) yv[u] = ev_readlane(yb, u);
+                    else yv[u] = (j >= 0) ? y[j] : 0.0;
                 }
 #pragma unroll
                 for (int u = 0; u < PF; ++u) {
@@ -225,7 +258,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                     }
                 }
             }
-            lds_sync();
+            y_sync<YG>();
         }
         // normalise by max-abs, then rhs = S x for the next iteration
         double mx = 0.0;
@@ -245,6 +278,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) { dp = fmax(dp, __shfl_xor(dp, off)); dm = fmax(dm, __shfl_xor(dm, off)); }
         __syncthreads();
+        if constexpr (YG) y_sync<YG>();                // the scaled y and tmp are in memory: the S x below and the next pass read them
         if (iter == 1 && fmin(dp, dm) <= 1e-12) break;
         if (iter < 2) {
             for (int j = lane; j < n; j += 64) {
@@ -258,7 +292,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                 }
                 y[j] = s;
             }
-            lds_sync();
+            y_sync<YG>();
         }
     }
     // ---- S-normalise: c^T S c = 1, sign: first significant coefficient positive ----
@@ -302,6 +336,37 @@ __global__ __launch_bounds__(64) void invit_kernel(int n, int k, const double *_
                    vecall + (size_t)iv * n, info, iv, y, threadIdx.x);
 }
 
+// Throughput form (bspatom_eigvecs_batch): a PERSISTENT grid of single-wave workgroups, one per resident work slot (the
+// occupancy query x CUs, invit_batch_slots), takes the items (channel c, vector j) = it / count, it % count by a
+// static stride over nl * count.  Every item is the same bounded work (invit_body: the LU and at most three solves) and no wave
+// waits for another -- no spin, no grid barrier: a wrong residency estimate costs speed, never progress.  The slot's scratch
+// is U, L, piv, tmp as in invit_kernel and y in global memory after them (no n-sized dynamic LDS, so the registers alone set
+// the occupancy); the vectors are invit_kernel's bit for bit (the same invit_body, only where y lives differs).
+// HB: the first channel's band (channel c at HB + c k n); E: its eigenvalue n0 (channel c's at E + c n, vector j at + j);
+// vec: nl * count vectors of n, item it at vec + it n.
+template <int BT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void invit_batch_kernel(
+    int n, int k, const double *__restrict__ SB, const double *__restrict__ HB, const double *__restrict__ E, int count, int items,
+    double *workall, double *vec, int *info)
+{
+    const int b = k - 1;
+    const size_t ws = (size_t)n * (3 * b + 3);
+    double *work = workall + (size_t)blockIdx.x * (ws + n), *y = work + ws;
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        const int c = it / count, j = it - c * count;
+        // Registers: the loop over items let the compiler keep what it hoisted out of invit_body live across the items (246 VGPRs,
+        // one wave per SIMD).  The empty asm makes the operands new values in every item, so they are recomputed inside it as in
+        // invit_kernel: 176 VGPRs, and 168 (three waves per SIMD, no spill) under amdgpu_waves_per_eu(3).  (The asm emits no instruction.)
+        int nn = n, kk = k, ln = threadIdx.x;
+        const double *sb = SB, *hb = HB, *ee = E;
+        double *wk = work, *yy = y, *vv = vec;
+        asm volatile("" : "+s"(nn), "+s"(kk), "+s"(sb), "+s"(hb), "+s"(ee), "+s"(wk), "+s"(yy), "+s"(vv), "+v"(ln));
+        // (y_sync across items: every load of y and tmp of an item is consumed by its norm and sign before its stores of vec,
+        // which nothing reads again -- the next item's stores cannot overtake them)
+        invit_body<BT, true>(nn, kk, sb, hb + (size_t)c * kk * nn, ee[(size_t)c * nn + j], wk, vv + (size_t)it * nn, info, it, yy, ln);
+    }
+}
+
 // The consumed eigenvector EARLY (capi.hip::solve_impl, band route): eigenvalue m of the pencil of one channel by multisection on its
 // inertia (bandsect.h: 256 threads), then the inverse iteration by the first wavefront of the SAME workgroup while the others leave.
 // One launch, because the workgroup asks for a CU's whole LDS (own_lds bytes of dynamic LDS it never touches): it runs beside the
@@ -338,6 +403,34 @@ int launch_inverse_iteration(int n, int k, int nvec, const double *d_SB, const d
     }
     if (k - 1 <= 8) hipLaunchKernelGGL(invit_kernel<8>, dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info);
     else hipLaunchKernelGGL(invit_kernel<EB_MAX>, dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+// scratch of one work slot of invit_batch_kernel: invit_work_doubles plus y
+size_t invit_batch_slot_doubles(int n, int k) { return invit_work_doubles(n, k) + (size_t)n; }
+
+// work slots invit_batch_kernel keeps resident on the current device (the occupancy query x CUs), at most `items`
+int invit_batch_slots(int k, int items, int *slots)
+{
+    if (k - 1 > EB_MAX || k < 2 || items < 1) return BSP_ERR_ARG;
+    int dev = 0, cus = 0, per_cu = 0;
+    BSP_HIP(hipGetDevice(&dev));
+    BSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (k - 1 <= 8) BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, invit_batch_kernel<8>, 64, 0));
+    else BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, invit_batch_kernel<EB_MAX>, 64, 0));
+    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+    *slots = (int)(r < items ? r : items);
+    return BSP_OK;
+}
+
+// items = nl * count inverse iterations on `slots` workgroups (d_work: slots * invit_batch_slot_doubles); see invit_batch_kernel
+int launch_inverse_iteration_batch(int n, int k, int count, int items, int slots, const double *d_SB, const double *d_HB,
+                                   const double *d_E, double *d_work, double *d_vec, int *d_info, hipStream_t st)
+{
+    if (k - 1 > EB_MAX || k < 2 || count < 1 || items < 1 || slots < 1) return BSP_ERR_ARG;
+    if (k - 1 <= 8) hipLaunchKernelGGL(invit_batch_kernel<8>, dim3(slots), dim3(64), 0, st, n, k, d_SB, d_HB, d_E, count, items, d_work, d_vec, d_info);
+    else hipLaunchKernelGGL(invit_batch_kernel<EB_MAX>, dim3(slots), dim3(64), 0, st, n, k, d_SB, d_HB, d_E, count, items, d_work, d_vec, d_info);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }

@@ -64,6 +64,12 @@
           INTEGER(C_INT), VALUE :: l, n0, cnt
           REAL(C_DOUBLE), INTENT(OUT) :: Z(*)
         END FUNCTION
+        INTEGER(C_INT) FUNCTION bspatom_eigvecs_batch(prob, l0, nl, n0, cnt, Z) BIND(C, NAME='bspatom_eigvecs_batch')
+          IMPORT :: C_INT, C_PTR, C_DOUBLE
+          TYPE(C_PTR), VALUE :: prob
+          INTEGER(C_INT), VALUE :: l0, nl, n0, cnt
+          REAL(C_DOUBLE), INTENT(OUT) :: Z(*)
+        END FUNCTION
         INTEGER(C_INT) FUNCTION bspatom_dipole_elements(prob, l_ini, n0_ini, l_fin, n0_fin, cnt, a, D)                    &
      &                  BIND(C, NAME='bspatom_dipole_elements')
           IMPORT :: C_INT, C_PTR, C_DOUBLE
@@ -152,7 +158,8 @@
       INTEGER :: n0_fin, n1_fin, nlim, nbds, nbold, ntemp, nE0, n1_max, ni, ntemp0
       INTEGER, ALLOCATABLE :: n01(:,:)
       REAL(DP) :: Elim, Ei
-      REAL(DP), ALLOCATABLE :: Zl(:,:)
+      REAL(DP), ALLOCATABLE :: Zb(:,:,:)
+      INTEGER :: lg, ng, gsz
       REAL(DP), ALLOCATABLE :: En(:), ci(:), r(:), u(:)
       INTEGER(C_INT32_T), ALLOCATABLE :: info(:)
 !     KIND_PI = 1, 2: TRANS_AMP / CROSS_SECTIONS (names as in PhotoIon.f90)
@@ -635,18 +642,23 @@
           WRITE(6,*) 'bsp_atom_host: n1_max exceeds the vectors the reference keeps (ctemp)'
           STOP 1
         END IF
-        ALLOCATE( Zl(nfun,n1_max) )
+!       the vectors of gsz channels per call of bspatom_eigvecs_batch (one launch for the group), at most 256 MiB of them
+        gsz = INT(MAX(1_8, MIN(INT(lmax+1,8), 33554432_8 / (INT(nfun,8)*INT(n1_max,8)))))
+        ALLOCATE( Zb(nfun,n1_max,gsz) )
         OPEN( UNIT=80, FILE='Eigenvec_All.dat', ACTION='WRITE' )
         WRITE(80,*) nfun, n1_max, lmax
-        DO l = 0, lmax
-          rc = bspatom_eigvecs(prob, INT(l,C_INT), 1_C_INT, INT(n1_max,C_INT), Zl)
+        DO lg = 0, lmax, gsz
+          ng = MIN(gsz, lmax + 1 - lg)
+          rc = bspatom_eigvecs_batch(prob, INT(lg,C_INT), INT(ng,C_INT), 1_C_INT, INT(n1_max,C_INT), Zb)
           IF( rc /= 0 ) THEN
-            WRITE(6,*) 'bsp_atom_host: bspatom_eigvecs failed, code ', rc
+            WRITE(6,*) 'bsp_atom_host: bspatom_eigvecs_batch failed, code ', rc
             STOP 1
           END IF
-          WRITE(80,*) l
-          DO ni = 1, n1_max
-            WRITE(80,300) ni, (Zl(i,ni), i=1,nfun)
+          DO l = lg, lg + ng - 1
+            WRITE(80,*) l
+            DO ni = 1, n1_max
+              WRITE(80,300) ni, (Zb(i,ni,l-lg+1), i=1,nfun)
+            END DO
           END DO
         END DO
         CLOSE(80)

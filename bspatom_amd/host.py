@@ -165,6 +165,9 @@ def run(text, outdir=".", device=0, npts=10000):
     return E, c, "\n".join(out)
 
 
+EIGVECS_GROUP_BYTES = 256 << 20       # write_eigenvec_all: host memory for the vectors of one group of channels
+
+
 def write_eigenvec_all(path, prob, lmax, n1_max):
     """`Eigenvec_All.dat` as SOLVE_SYSTEM writes it for KIND_PI >= 3 (matrices.f90:366-378): a list-directed
     header `nfun n1_max lmax`, then per channel a list-directed `l` and n1_max records FORMAT(I5,5000G20.10)
@@ -172,11 +175,22 @@ def write_eigenvec_all(path, prob, lmax, n1_max):
     channels 0..lmax must have been solved.  List-directed integers are written the way flang does (one blank,
     no padding), which is what the golden files hold; gfortran/ifort pad them, READ(*,*) accepts either."""
     nfun = prob.nfun
+    # a problem with eigvecs_batch gives the vectors of a group of channels per call (one launch instead of one per channel;
+    # the same bits), at most EIGVECS_GROUP_BYTES of them at a time
+    batch = getattr(prob, "eigvecs_batch", None)
+    group = max(1, EIGVECS_GROUP_BYTES // (8 * max(1, n1_max * nfun)))
+    Zg, g0 = None, 0
     with open(path, "w") as f:
         f.write(" %d %d %d\n" % (nfun, n1_max, lmax))                  # WRITE(80,*) nfun, n1_max, lmax
         for l in range(lmax + 1):
             f.write(" %d\n" % l)
-            Z = prob.eigvecs(l, 1, n1_max)
+            if batch is None:
+                Z = prob.eigvecs(l, 1, n1_max)
+            else:
+                if Zg is None or l >= g0 + len(Zg):
+                    g0 = l
+                    Zg = batch(l, min(group, lmax + 1 - l), 1, n1_max)
+                Z = Zg[l - g0]
             for ni in range(n1_max):
                 f.write("%5d" % (ni + 1) + "".join(fortran_g(v, 20, 10) for v in Z[ni]) + "\n")
 

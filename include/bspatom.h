@@ -107,6 +107,17 @@ int bspatom_eigvec(bspatom_problem *p, int l, int n0, double *c);
  * Z[j*nfun + i] = component i of eigenvector n0+j.  Requires a previous bspatom_solve covering l. */
 int bspatom_eigvecs(bspatom_problem *p, int l, int n0, int count, double *Z);
 
+/* Eigenvectors n0 .. n0+count-1 (1-based) of channels l0 .. l0+nl-1 of the last solved batch, in one call:
+ * Z[((size_t)c * count + j) * nfun + i] = component i of eigenvector n0+j of channel l0+c.
+ * Column for column BIT-IDENTICAL to bspatom_eigvecs(p, l0+c, n0, count, ...): the same inverse iteration on a persistent grid
+ * of one wave per resident work slot (device scratch bounded by the slots, not by nl*count).  The host variant stages the
+ * output through a device buffer of at most 256 MiB (one channel's block at least).  BSPATOM_ERR_ARG unless every channel
+ * lies in the last solve, nl >= 1, count >= 1, n0 >= 1 and n0+count-1 <= nfun (and after bspatom_assemble);
+ * BSPATOM_ERR_UNSUPPORTED if an iterate vanished. */
+int bspatom_eigvecs_batch(bspatom_problem *p, int l0, int nl, int n0, int count, double *Z);
+/* Same, Z_dev in device memory of the problem's device (e.g. a torch tensor's data_ptr), nl*count*nfun doubles, written in place. */
+int bspatom_eigvecs_batch_dev(bspatom_problem *p, int l0, int nl, int n0, int count, double *Z_dev);
+
 /* Dipole matrix elements between eigenvectors of the last solved batch: the DGEMV + DDOT of TRANS_AMP for the
  * plane-wave branches KIND_PI = 1, 2 (reference PhotoIon.f90:95-107):
  *   D[i] = c(l_fin, n0_fin + i)^T (a[0] R_r + a[1] R_{1/r} + a[2] R_{d/dr}) c(l_ini, n0_ini),  i = 0 .. count-1,
