@@ -33,7 +33,7 @@ class Sizes(C.Structure):
 
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
-           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_write_wf", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev", "bspatom_write_wf", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -66,6 +66,8 @@ def lib():
         L.bspatom_eigvecs_batch.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bspatom_eigvecs_batch_dev.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bspatom_dipole_elements.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
+        L.bspatom_dipole_matrix.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+        L.bspatom_dipole_matrix_dev.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.bspatom_dipole_bands.argtypes = [vp, vp]
         L.bspatom_write_wf.argtypes = [vp, vp, i32, vp, vp]
         L.bspatom_last_timing.argtypes = [vp, vp]
@@ -202,6 +204,33 @@ class Problem:
         D = np.zeros(count)
         _chk(lib().bspatom_dipole_elements(self._h, l_ini, n0_ini, l_fin, n0_fin, count, _p(a), _p(D)), "bspatom_dipole_elements")
         return D
+
+    @staticmethod
+    def _dipole_pairs(pairs, a):
+        pr = np.asarray(list(pairs), dtype=np.int32).reshape(-1, 2)
+        li, lf = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape == (3,):
+            a = np.broadcast_to(a, (len(pr), 3))
+        assert a.shape == (len(pr), 3), a.shape
+        return li, lf, np.ascontiguousarray(a)
+
+    def dipole_matrix(self, pairs, n0_ini, count_ini, n0_fin, count_fin, a):
+        """D[p, i, f] = c(l_fin, n0_fin+f)^T (a[p,0] R_r + a[p,1] R_1/r + a[p,2] R_d/dr) c(l_ini, n0_ini+i) for every
+        (l_ini, l_fin) = pairs[p] in one call: array (npairs, count_ini, count_fin); row [p, i] is dipole_elements(l_ini,
+        n0_ini + i, l_fin, n0_fin, count_fin, a[p]) up to the summation order.  a: (npairs, 3), or one triple for every pair."""
+        li, lf, a = self._dipole_pairs(pairs, a)
+        D = np.zeros((len(li), max(count_ini, 0), max(count_fin, 0)))
+        _chk(lib().bspatom_dipole_matrix(self._h, len(li), _p(li), _p(lf), n0_ini, count_ini, n0_fin, count_fin, _p(a), _p(D)),
+             "bspatom_dipole_matrix")
+        return D
+
+    def dipole_matrix_dev(self, pairs, n0_ini, count_ini, n0_fin, count_fin, a, dev_ptr):
+        """dipole_matrix into device memory of this problem's device (npairs * count_ini * count_fin doubles at dev_ptr, e.g. a
+        torch tensor's data_ptr()), written in place; returns when the block is there."""
+        li, lf, a = self._dipole_pairs(pairs, a)
+        _chk(lib().bspatom_dipole_matrix_dev(self._h, len(li), _p(li), _p(lf), n0_ini, count_ini, n0_fin, count_fin, _p(a),
+                                             C.c_void_p(dev_ptr)), "bspatom_dipole_matrix_dev")
 
     def write_wf(self, c, npts=10000):
         c = np.ascontiguousarray(c, dtype=np.float64)

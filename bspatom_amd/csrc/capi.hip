@@ -1,6 +1,7 @@
 // capi.hip -- the C ABI of libbspatom (include/bspatom.h): problem handle, the batched solve
 // pipeline and the stage-level entry points.  One HIP stream per problem; every stage of a solve
 // is enqueued on it back-to-back (no host synchronisation between stages) and timed with events.
+#include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <new>
@@ -82,7 +83,7 @@ const OptName OPT_TABLE[] = {
     {"ktime", "BSP_KTIME", &Options::ktime}, {"tsqr_regcap", "BSP_TSQR_REGCAP", &Options::tsqr_regcap},
     {"tsqr_max_m", "BSP_TSQR_MAX_M", &Options::tsqr_max_m}, {"sb16_rows", "BSP_SB16_ROWS", &Options::sb16_rows},
     {"route", "BSP_ROUTE", &Options::route}, {"cw_onediv", "BSP_CW_ONEDIV", &Options::cw_onediv}, {"cw_items4", "BSP_CW_ITEMS4", &Options::cw_items4}, {"cw_nw", "BSP_CW_NW", &Options::cw_nw}, {"cw_ldspad", "BSP_CW_LDSPAD", &Options::cw_ldspad}, {"cw_ipw", "BSP_CW_IPW", &Options::cw_ipw}, {"cw_band8", "BSP_CW_BAND8", &Options::cw_band8}, {"cw_split", "BSP_CW_SPLIT", &Options::cw_split}, {"cw_diag", "BSP_CW_DIAG", &Options::cw_diag}, {"s_overlap", "BSP_S_OVERLAP", &Options::s_overlap}, {"cw_streams", "BSP_CW_STREAMS", &Options::cw_streams}, {"cw_chunk_min", "BSP_CW_CHUNK_MIN", &Options::cw_chunk_min}, {"sb8_wgs", "BSP_SB8_WGS", &Options::sb8_wgs},
-    {"fused_probe", "BSP_FUSED_PROBE", &Options::fused_probe},
+    {"fused_probe", "BSP_FUSED_PROBE", &Options::fused_probe}, {"dipole_stage_mb", "BSP_DIPOLE_STAGE_MB", &Options::dipole_stage_mb},
 };
 }  // namespace
 
@@ -878,6 +879,186 @@ extern "C" int bspatom_dipole_elements(bspatom_problem *p, int l_ini, int n0_ini
     BSP_HIP(e);
     if ((rc = invit_failed(p))) return rc;
     return check_status(p);
+}
+
+// bspatom_dipole_elements for whole windows of initial and final states of many channel pairs in one call (dipole.hip):
+// D[p][i][f] = c(l_fin[p], n0_fin + f)^T (a[3p] R_r + a[3p+1] R_1/r + a[3p+2] R_d/dr) c(l_ini[p], n0_ini + i).
+// The pairs are taken in groups, in the order given; the device scratch of a group -- its distinct (channel, window) eigenvector
+// blocks, W = A x of its distinct (operator, initial block) items, the split-K partials and, for host output, D itself --
+// stays within DIPOLE_STAGE_BYTES (option dipole_stage_mb), one pair at least.  The eigenvectors are bspatom_eigvecs' bit for
+// bit (one launch_inverse_iteration_batch per run of consecutive channels and window); nothing of a pair's arithmetic depends on
+// the other pairs or on the grouping.  The scratch of the inverse iterations is one slot per resident wave beside that.
+static constexpr size_t DIPOLE_STAGE_BYTES = (size_t)2 << 30;
+
+namespace {
+struct DevLongs {
+    long long *p = nullptr;
+    ~DevLongs() { hipFree(p); }
+    int put(const std::vector<long long> &h)
+    {
+        BSP_HIP(hipMalloc(reinterpret_cast<void **>(&p), (h.size() ? h.size() : 1) * sizeof(long long)));
+        BSP_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice));
+        return BSP_OK;
+    }
+};
+struct DipItem {                                   // W item: operator and initial channel
+    int ch; uint64_t a[3];
+    bool operator<(const DipItem &o) const { return ch != o.ch ? ch < o.ch : memcmp(a, o.a, sizeof a) < 0; }
+};
+struct DipGroup {
+    int p0 = 0, np = 0;
+    std::vector<int> chA, chB;                     // sorted distinct channels whose initial / final window the group needs
+    std::vector<DipItem> items;                    // sorted distinct W items
+    static bool has(const std::vector<int> &v, int c) { return std::binary_search(v.begin(), v.end(), c); }
+    static void add(std::vector<int> &v, int c) { if (!has(v, c)) v.insert(std::lower_bound(v.begin(), v.end(), c), c); }
+    static int pos(const std::vector<int> &v, int c) { return (int)(std::lower_bound(v.begin(), v.end(), c) - v.begin()); }
+    bool has_item(const DipItem &t) const { return std::binary_search(items.begin(), items.end(), t); }
+    int item_pos(const DipItem &t) const { return (int)(std::lower_bound(items.begin(), items.end(), t) - items.begin()); }
+};
+}  // namespace
+
+static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini,
+                              int n0_fin, int count_fin, const double *a, double *D, bool dev)
+{
+    if (!p || !l_ini || !l_fin || !a || !D) return BSP_ERR_ARG;
+    const HostSetup &h = p->hs;
+    const int n = h.nfun;
+    const int lo = p->last_l0, hi = p->last_l0 + p->last_nl;
+    if (npairs < 1 || count_ini < 1 || count_fin < 1 || n0_ini < 1 || n0_fin < 1 || (long)n0_ini + count_ini - 1 > n ||
+        (long)n0_fin + count_fin - 1 > n) return BSP_ERR_ARG;
+    for (int q = 0; q < npairs; ++q)
+        if (l_ini[q] < lo || l_ini[q] >= hi || l_fin[q] < lo || l_fin[q] >= hi) return BSP_ERR_ARG;
+    BSP_HIP(hipSetDevice(p->device));
+    int rc;
+    if (!p->ptab_ready) {
+        if ((rc = launch_point_table(h.nkp, h.k, h.ka, h.nfun, p->d_rt, p->d_aind, p->d_xg, p->d_wg, p->d_vpot,
+                                     p->d_ptab, p->d_left, p->d_status, p->st))) return rc;
+        p->ptab_ready = true;
+    }
+    // ---- the groups ----
+    const bool same = n0_ini == n0_fin && count_ini == count_fin;        // one window: a channel's block serves both roles
+    const size_t mn = (size_t)count_ini * count_fin, vi = (size_t)count_ini * n, vf = (size_t)count_fin * n;
+    int chunk = 0, ns = 1;
+    dipole_kslices(n, count_ini, count_fin, &chunk, &ns);
+    const size_t per_pair = (ns > 1 ? (size_t)ns * mn : 0) + (dev ? 0 : mn);
+    const size_t limit = (opts().dipole_stage_mb > 0 ? (size_t)opts().dipole_stage_mb << 20 : DIPOLE_STAGE_BYTES) / sizeof(double);
+    auto item_of = [&](int q) { DipItem t; t.ch = l_ini[q] - lo; memcpy(t.a, a + 3 * (size_t)q, sizeof t.a); return t; };
+    auto doubles_of = [&](const DipGroup &g) {
+        return g.chA.size() * vi + g.chB.size() * vf + g.items.size() * vi + (size_t)g.np * per_pair;
+    };
+    std::vector<DipGroup> groups;
+    DipGroup cur;
+    for (int q = 0; q < npairs; ++q) {
+        const int ci = l_ini[q] - lo, cf = l_fin[q] - lo;
+        const DipItem t = item_of(q);
+        if (cur.np > 0) {
+            // what the group would need with this pair in it
+            size_t need = doubles_of(cur) + per_pair;
+            if (!DipGroup::has(cur.chA, ci)) need += vi;
+            if (same) { if (cf != ci && !DipGroup::has(cur.chA, cf)) need += vi; }
+            else if (!DipGroup::has(cur.chB, cf)) need += vf;
+            if (!cur.has_item(t)) need += vi;
+            if (need > limit) { groups.push_back(cur); cur = DipGroup(); cur.p0 = q; }
+        }
+        DipGroup::add(cur.chA, ci);
+        DipGroup::add(same ? cur.chA : cur.chB, cf);
+        if (!cur.has_item(t)) cur.items.insert(cur.items.begin() + cur.item_pos(t), t);
+        cur.np += 1;
+    }
+    groups.push_back(cur);
+    // ---- tables (offsets in doubles from the scratch base) and sizes ----
+    size_t stage_doubles = 0, nitems_all = 0;
+    long max_run_items = 1;
+    const long gmaxA = ((long)1 << 30) / count_ini, gmaxB = ((long)1 << 30) / count_fin;      // items of a launch stay an int
+    for (const DipGroup &g : groups) {
+        if (doubles_of(g) > stage_doubles) stage_doubles = doubles_of(g);
+        nitems_all += g.items.size();
+        for (int w = 0; w < 2; ++w) {
+            const std::vector<int> &ch = w ? g.chB : g.chA;
+            const long cnt = w ? count_fin : count_ini, gmax = w ? gmaxB : gmaxA;
+            for (size_t i = 0; i < ch.size();) {
+                size_t j = i + 1;
+                while (j < ch.size() && ch[j] == ch[j - 1] + 1 && (long)(j - i) < gmax) ++j;
+                if ((long)(j - i) * cnt > max_run_items) max_run_items = (long)(j - i) * cnt;
+                i = j;
+            }
+        }
+    }
+    std::vector<long long> tab(nitems_all + 2 * (size_t)npairs);      // [xoff of every item | (W, Z) offsets of every pair]
+    std::vector<double> acoef(3 * nitems_all);
+    {
+        size_t q0 = 0;
+        for (const DipGroup &g : groups) {
+            const size_t offB = g.chA.size() * vi, offW = offB + g.chB.size() * vf;
+            for (size_t t = 0; t < g.items.size(); ++t) {
+                tab[q0 + t] = (long long)((size_t)DipGroup::pos(g.chA, g.items[t].ch) * vi);
+                memcpy(&acoef[3 * (q0 + t)], g.items[t].a, sizeof g.items[t].a);
+            }
+            for (int q = g.p0; q < g.p0 + g.np; ++q) {
+                const int cf = l_fin[q] - lo;
+                tab[nitems_all + 2 * (size_t)q] = (long long)(offW + (size_t)g.item_pos(item_of(q)) * vi);
+                tab[nitems_all + 2 * (size_t)q + 1] = same ? (long long)((size_t)DipGroup::pos(g.chA, cf) * vi)
+                                                           : (long long)(offB + (size_t)DipGroup::pos(g.chB, cf) * vf);
+            }
+            q0 += g.items.size();
+        }
+    }
+    int slots = 0;
+    if ((rc = invit_batch_slots(h.k, (int)max_run_items, &slots))) return rc;
+    DevBuf RB, work, stage, dA;
+    DevLongs dtab;
+    if ((rc = RB.alloc((size_t)3 * (2 * h.k - 1) * n)) || (rc = work.alloc((size_t)slots * invit_batch_slot_doubles(n, h.k))) ||
+        (rc = stage.alloc(stage_doubles)) || (rc = dA.put(acoef.data(), acoef.size())) || (rc = dtab.put(tab))) return rc;
+    hipError_t e = hipMemsetAsync(p->d_info, 0, sizeof(int), p->st);
+    if (e == hipSuccess) rc = launch_dipole_bands(n, h.k, h.ka, h.nkp, p->d_ptab, p->d_left, RB.p, p->st);
+    // ---- group by group on the problem's stream ----
+    size_t q0 = 0;
+    for (size_t gi = 0; e == hipSuccess && !rc && gi < groups.size(); ++gi) {
+        const DipGroup &g = groups[gi];
+        const size_t offB = g.chA.size() * vi, offW = offB + g.chB.size() * vf, offP = offW + g.items.size() * vi;
+        const size_t offD = offP + (ns > 1 ? (size_t)g.np * ns * mn : 0);
+        for (int w = 0; w < 2 && !rc; ++w) {
+            const std::vector<int> &ch = w ? g.chB : g.chA;
+            const int cnt = w ? count_fin : count_ini, n0 = w ? n0_fin : n0_ini;
+            const long gmax = w ? gmaxB : gmaxA;
+            const size_t vw = w ? vf : vi;
+            for (size_t i = 0; i < ch.size() && !rc;) {               // maximal runs of consecutive channels
+                size_t j = i + 1;
+                while (j < ch.size() && ch[j] == ch[j - 1] + 1 && (long)(j - i) < gmax) ++j;
+                const int items = (int)(j - i) * cnt;
+                rc = launch_inverse_iteration_batch(n, h.k, cnt, items, slots < items ? slots : items, p->d_SB,
+                                                    p->d_HB + (size_t)ch[i] * h.k * n, p->d_E + (size_t)ch[i] * n + (n0 - 1), work.p,
+                                                    stage.p + (w ? offB : 0) + i * vw, p->d_info, p->st);
+                i = j;
+            }
+        }
+        if (!rc) rc = launch_band_apply_block(n, h.k, count_ini, (int)g.items.size(), RB.p, dA.p + 3 * q0, dtab.p + q0, stage.p,
+                                              stage.p + offW, p->st);
+        double *out = dev ? D + (size_t)g.p0 * mn : stage.p + offD;
+        if (!rc) rc = launch_dipole_block(n, count_ini, count_fin, g.np, dtab.p + nitems_all + 2 * (size_t)g.p0, stage.p,
+                                          ns > 1 ? stage.p + offP : nullptr, out, p->st);
+        if (!rc && !dev) e = hipMemcpyAsync(D + (size_t)g.p0 * mn, out, (size_t)g.np * mn * sizeof(double), hipMemcpyDeviceToHost, p->st);
+        q0 += g.items.size();
+    }
+    // every path waits for the stream before the scratch is freed (DevBuf) and before it returns
+    const hipError_t es = hipStreamSynchronize(p->st);
+    if (rc) return rc;
+    BSP_HIP(e);
+    BSP_HIP(es);
+    if ((rc = invit_failed(p))) return rc;
+    return check_status(p);
+}
+
+extern "C" int bspatom_dipole_matrix(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini,
+                                     int count_ini, int n0_fin, int count_fin, const double *a, double *D)
+{
+    return dipole_matrix_impl(p, npairs, l_ini, l_fin, n0_ini, count_ini, n0_fin, count_fin, a, D, false);
+}
+
+extern "C" int bspatom_dipole_matrix_dev(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini,
+                                         int count_ini, int n0_fin, int count_fin, const double *a, double *D_dev)
+{
+    return dipole_matrix_impl(p, npairs, l_ini, l_fin, n0_ini, count_ini, n0_fin, count_fin, a, D_dev, true);
 }
 
 extern "C" int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u)

@@ -88,6 +88,8 @@ struct Options {
     int cw_ipw = 0;              // BSP_CW_IPW: items per wave of crawford_item4_kernel (0 = 4; 1, 2: experiment 9; bit-identical results)
     int cw_ldspad = 0;           // BSP_CW_LDSPAD: KB of unused dynamic LDS per workgroup of crawford_item4_kernel (timing experiment: occupancy)
     int cw_onediv = 0;           // BSP_CW_ONEDIV: reflectors of the band route's RQ loop in the one-division form (A/B switch)
+    int dipole_stage_mb = 0;     // BSP_DIPOLE_STAGE_MB: > 0 = device scratch of one group of pairs of bspatom_dipole_matrix in MB (0 = 2 GiB); small
+                                 // values force several groups (the results do not depend on the grouping: the test's hook)
     int ktime = 0;               // 1: HIP events around every launch of the kernels in KSlot (bspatom_kernel_times; bench.py's
                                  // per-kernel roofline entries are measured with it in one extra, untimed step)
 };
@@ -243,6 +245,17 @@ int launch_inverse_iteration_batch(int n, int k, int count, int items, int slots
                                    const double *d_E, double *d_work, double *d_vec, int *d_info, hipStream_t st);
 int launch_band_apply(int n, int k, const double *d_RB, const double a[3], const double *d_x, double *d_v, hipStream_t st);
 int launch_dots(int n, int m, const double *d_Z, const double *d_v, double *d_D, hipStream_t st);
+// dipole.hip: dipole matrix blocks of many channel pairs (bspatom_dipole_matrix)
+// W[q][j][:] = (a[3q] R_r + a[3q+1] R_1/r + a[3q+2] R_d/dr) x_j for the `count` vectors at d_base + d_xoff[q] of each of nitems
+// items, every column bit-identical to launch_band_apply's
+int launch_band_apply_block(int n, int k, int count, int nitems, const double *d_RB, const double *d_acoef, const long long *d_xoff,
+                            const double *d_base, double *d_W, hipStream_t st);
+// K slices of one pair's product, a rule in (n, count_ini, count_fin) alone
+void dipole_kslices(int n, int count_ini, int count_fin, int *chunk, int *nslices);
+// d_out[p][i][f] = W_p[i][:] . Z_p[f][:] for npairs pairs on one grid; W_p at d_base + d_pw[2p] ([count_ini][n]), Z_p at
+// d_base + d_pw[2p+1] ([count_fin][n]); d_part: npairs * nslices * count_ini * count_fin doubles when nslices > 1 (summed in slice order)
+int launch_dipole_block(int n, int count_ini, int count_fin, int npairs, const long long *d_pw, const double *d_base, double *d_part,
+                        double *d_out, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 

@@ -425,6 +425,7 @@ def dipole_matelem(prob, channels, n1_max, kind_pi=1, mph=0):
     import numpy as np
     nlm = len(channels)
     z = np.zeros((nlm * n1_max, nlm * n1_max, 1), dtype=np.complex128)
+    blocks = []                                    # (a_, b_, initial channel, final channel, c0, coefficients)
     for a_, (li, mi) in enumerate(channels):
         for b_, (lj, mj) in enumerate(channels):
             if abs(li - lj) != 1 or b_ < a_:
@@ -440,9 +441,18 @@ def dipole_matelem(prob, channels, n1_max, kind_pi=1, mph=0):
                 c0 = math.sqrt(float(l0 + 1)) * t3a
                 c1, c2 = (float(l0 + 1), -1.0) if lf == l0 + 1 else (float(l0), 1.0)
                 coef = [0.0, c1, c2]
-            for nj in range(1, n1_max + 1):
-                D = prob.dipole_elements(l0, nj, lf, 1, n1_max, coef)
-                z[a_ * n1_max: (a_ + 1) * n1_max, b_ * n1_max + nj - 1, 0] = c0 * D
+            blocks.append((a_, b_, l0, lf, c0, coef))
+    if hasattr(prob, "dipole_matrix") and blocks:
+        # every block of the file in one call (bspatom_dipole_matrix): D[p][nj - 1][n - 1], ket = initial, bra = final
+        D = prob.dipole_matrix([(l0, lf) for _, _, l0, lf, _, _ in blocks], 1, n1_max, 1, n1_max,
+                               np.array([coef for *_, coef in blocks], dtype=np.float64))
+        for p, (a_, b_, _, _, c0, _) in enumerate(blocks):
+            z[a_ * n1_max: (a_ + 1) * n1_max, b_ * n1_max: (b_ + 1) * n1_max, 0] = c0 * D[p].T
+        return z
+    for a_, b_, l0, lf, c0, coef in blocks:
+        for nj in range(1, n1_max + 1):
+            D = prob.dipole_elements(l0, nj, lf, 1, n1_max, coef)
+            z[a_ * n1_max: (a_ + 1) * n1_max, b_ * n1_max + nj - 1, 0] = c0 * D
     return z
 
 

@@ -128,6 +128,27 @@ int bspatom_eigvecs_batch_dev(bspatom_problem *p, int l0, int nl, int n0, int co
 int bspatom_dipole_elements(bspatom_problem *p, int l_ini, int n0_ini, int l_fin, int n0_fin, int count,
                             const double a[3], double *D);
 
+/* The same elements for whole windows of initial AND final states of many channel pairs in one call -- the reference's unit
+ * of work, "all states of two channels" (matrices.f90:331 keeps ctemp(:,1:ntemp,l); PhotoIon.f90:95-107 runs over it):
+ *   D[((size_t)p*count_ini + i)*count_fin + f] =
+ *     c(l_fin[p], n0_fin+f)^T (a[3p] R_r + a[3p+1] R_{1/r} + a[3p+2] R_{d/dr}) c(l_ini[p], n0_ini+i)
+ * for p < npairs, i < count_ini, f < count_fin; 1-based state numbers, channels of the last solve.  Matrices, eigenvectors
+ * (bspatom_eigvecs' bit for bit), signs and normalisation are those of bspatom_dipole_elements: row i of pair p is what
+ * bspatom_dipole_elements(p, l_ini[p], n0_ini+i, l_fin[p], n0_fin, count_fin, a+3p, .) returns up to the summation order of
+ * the final dot product, which here runs on the matrix cores over K slices fixed by (nfun, count_ini, count_fin) alone and
+ * summed in slice order.  Pairs may repeat channels in either role and l_ini[p] == l_fin[p] is allowed.  The pairs are
+ * processed in groups, in the order given; a group's device scratch (its distinct eigenvector blocks, A x of its distinct
+ * initial blocks, the K-slice partials, and D for the host variant) stays within 2 GiB -- bspatom_eigvecs_batch stages through
+ * 256 MiB -- or one pair's need if that is more; bspatom_set_option("dipole_stage_mb", m) sets another bound.  Results are
+ * run-to-run bit-identical, and a pair's block depends neither on the other pairs of the call nor on the grouping.
+ * BSPATOM_ERR_ARG: a null pointer, npairs < 1, a count < 1, a window outside 1..nfun, a channel outside the last solve (every
+ * channel after bspatom_assemble); BSPATOM_ERR_UNSUPPORTED if an inverse iteration broke down. */
+int bspatom_dipole_matrix(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini,
+                          int n0_fin, int count_fin, const double *a, double *D);
+/* Same, D_dev in device memory of the problem's device (npairs*count_ini*count_fin doubles), written in place. */
+int bspatom_dipole_matrix_dev(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini,
+                              int count_ini, int n0_fin, int count_fin, const double *a, double *D_dev);
+
 /* WRITE_WF (Bsp_Atom.f90:118-146): u(r_i) = sum_j c_j B_j(r_i), r_i = ra + i*(rb-ra)/npts,
  * i = 0..npts.  Returns BSPATOM_ERR_BSPLVB where the reference STOPs. r[npts+1], u[npts+1]. */
 int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u);
