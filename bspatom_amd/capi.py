@@ -33,7 +33,7 @@ class Sizes(C.Structure):
 
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
-           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev", "bspatom_write_wf", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -70,6 +70,11 @@ def lib():
         L.bspatom_dipole_matrix_dev.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.bspatom_dipole_bands.argtypes = [vp, vp]
         L.bspatom_write_wf.argtypes = [vp, vp, i32, vp, vp]
+        L.bspatom_quadrature.argtypes = [vp, C.POINTER(i32), vp, vp]
+        L.bspatom_tabulate.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+        L.bspatom_tabulate_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+        L.bspatom_wavefunctions.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.bspatom_wavefunctions_dev.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -237,6 +242,59 @@ class Problem:
         r = np.zeros(npts + 1); u = np.zeros(npts + 1)
         _chk(lib().bspatom_write_wf(self._h, _p(c), npts, _p(r), _p(u)), "bspatom_write_wf")
         return r, u
+
+    def quadrature(self):
+        """(r, w): points and weights of the assembly's Gauss-Legendre quadrature on the knot intervals of positive width,
+        ascending, ka per interval -- the grid `r=None` selects in tabulate / wavefunctions."""
+        nr = C.c_int(0)
+        _chk(lib().bspatom_quadrature(self._h, C.byref(nr), None, None), "bspatom_quadrature")
+        r = np.zeros(nr.value); w = np.zeros(nr.value)
+        _chk(lib().bspatom_quadrature(self._h, C.byref(nr), _p(r), _p(w)), "bspatom_quadrature")
+        return r, w
+
+    def _points(self, r):
+        """(npts, host array or None) of a points argument: None = the quadrature grid"""
+        if r is None:
+            nr = C.c_int(0)
+            _chk(lib().bspatom_quadrature(self._h, C.byref(nr), None, None), "bspatom_quadrature")
+            return nr.value, None
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+        return r.size, r
+
+    def tabulate(self, Z, r=None, deriv=True):
+        """u(r) = sum_j Z[v, j] B_j(r) and, with deriv, u'(r) for the rows of Z (nvec, nfun) at the points r (host array, any
+        order, inside [ra, rb]; None: the quadrature grid): (U, dU), each (nvec, npts), or U alone."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64).reshape(-1, self.nfun)
+        npts, r = self._points(r)
+        U = np.zeros((Z.shape[0], npts)); dU = np.zeros_like(U) if deriv else None
+        _chk(lib().bspatom_tabulate(self._h, Z.shape[0], _p(Z), npts, _p(r), _p(U), _p(dU)), "bspatom_tabulate")
+        return (U, dU) if deriv else U
+
+    def tabulate_dev(self, nvec, Z_ptr, U_ptr, dU_ptr=None, r=None):
+        """tabulate with the vectors (nvec * nfun doubles at Z_ptr) and the tables (nvec * npts doubles at U_ptr and, unless
+        None, at dU_ptr) in device memory of this problem's device, e.g. torch tensors' data_ptr(); written in place.  r is
+        a host array or None (the quadrature grid).  Returns npts when the tables are there."""
+        npts, r = self._points(r)
+        _chk(lib().bspatom_tabulate_dev(self._h, nvec, C.c_void_p(Z_ptr), npts, _p(r), C.c_void_p(U_ptr),
+                                        C.c_void_p(dU_ptr) if dU_ptr else None), "bspatom_tabulate_dev")
+        return npts
+
+    def wavefunctions(self, l0, nl, n0, count, r=None, deriv=True):
+        """u(r) and, with deriv, u'(r) of eigenvectors n0 .. n0+count-1 (1-based) of channels l0 .. l0+nl-1 of the last solve at
+        the points r (None: the quadrature grid): (U, dU), each (nl, count, npts), or U alone; equal to tabulate applied to
+        eigvecs_batch(l0, nl, n0, count), bit for bit."""
+        npts, r = self._points(r)
+        U = np.zeros((max(nl, 0), max(count, 0), npts)); dU = np.zeros_like(U) if deriv else None
+        _chk(lib().bspatom_wavefunctions(self._h, l0, nl, n0, count, npts, _p(r), _p(U), _p(dU)), "bspatom_wavefunctions")
+        return (U, dU) if deriv else U
+
+    def wavefunctions_dev(self, l0, nl, n0, count, U_ptr, dU_ptr=None, r=None):
+        """wavefunctions into device memory of this problem's device (nl * count * npts doubles at U_ptr and, unless None, at
+        dU_ptr), written in place.  Returns npts when the tables are there."""
+        npts, r = self._points(r)
+        _chk(lib().bspatom_wavefunctions_dev(self._h, l0, nl, n0, count, npts, _p(r), C.c_void_p(U_ptr),
+                                             C.c_void_p(dU_ptr) if dU_ptr else None), "bspatom_wavefunctions_dev")
+        return npts
 
     def early_vector_state(self):
         """0: the last solve computed no early vector; 1: computed and kept; -1: computed, failed its check, dropped (include/bspatom.h)."""

@@ -84,6 +84,7 @@ const OptName OPT_TABLE[] = {
     {"tsqr_max_m", "BSP_TSQR_MAX_M", &Options::tsqr_max_m}, {"sb16_rows", "BSP_SB16_ROWS", &Options::sb16_rows},
     {"route", "BSP_ROUTE", &Options::route}, {"cw_onediv", "BSP_CW_ONEDIV", &Options::cw_onediv}, {"cw_items4", "BSP_CW_ITEMS4", &Options::cw_items4}, {"cw_nw", "BSP_CW_NW", &Options::cw_nw}, {"cw_ldspad", "BSP_CW_LDSPAD", &Options::cw_ldspad}, {"cw_ipw", "BSP_CW_IPW", &Options::cw_ipw}, {"cw_band8", "BSP_CW_BAND8", &Options::cw_band8}, {"cw_split", "BSP_CW_SPLIT", &Options::cw_split}, {"cw_diag", "BSP_CW_DIAG", &Options::cw_diag}, {"s_overlap", "BSP_S_OVERLAP", &Options::s_overlap}, {"cw_streams", "BSP_CW_STREAMS", &Options::cw_streams}, {"cw_chunk_min", "BSP_CW_CHUNK_MIN", &Options::cw_chunk_min}, {"sb8_wgs", "BSP_SB8_WGS", &Options::sb8_wgs},
     {"fused_probe", "BSP_FUSED_PROBE", &Options::fused_probe}, {"dipole_stage_mb", "BSP_DIPOLE_STAGE_MB", &Options::dipole_stage_mb},
+    {"wf_stage_mb", "BSP_WF_STAGE_MB", &Options::wf_stage_mb},
 };
 }  // namespace
 
@@ -1086,6 +1087,183 @@ extern "C" int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, d
     BSP_HIP(hipMemcpy(r, p->d_wfr, (size_t)(npts + 1) * sizeof(double), hipMemcpyDeviceToHost));
     BSP_HIP(hipMemcpy(u, p->d_wfu, (size_t)(npts + 1) * sizeof(double), hipMemcpyDeviceToHost));
     return BSP_OK;
+}
+
+// ---- u(r), u'(r) of blocks of vectors (wavefn.hip; WFALL, TorusFuns.f90:193-261) -------------------------------------------
+
+extern "C" int bspatom_quadrature(bspatom_problem *p, int *nr, double *r, double *w)
+{
+    if (!p || !nr) return BSP_ERR_ARG;
+    const HostSetup &h = p->hs;
+    *nr = wf_quadrature(h.nkp, h.ka, h.rt.data(), h.xg.data(), h.wg.data(), nullptr, r, w);
+    return BSP_OK;
+}
+
+static constexpr size_t WF_STAGE_BYTES = (size_t)256 << 20;
+static size_t wf_stage_bytes()
+{
+    const int mb = opts().wf_stage_mb;
+    return mb > 0 ? (size_t)mb << 20 : WF_STAGE_BYTES;
+}
+
+struct WfBasis {
+    DevBuf tab;        // [2k][npts]
+    DevInts left;      // [npts]
+};
+
+// The basis table of a call on the problem's stream: r == nullptr: the quadrature grid (npts must be its size; the rows of the
+// assembly's point table, which is run first if it has not been), else the caller's points, checked on the host before any launch.
+// Returns with the stream drained (the uploads it made are freed here) and the kernels' status word checked.
+static int wf_basis(bspatom_problem *p, int npts, const double *r, WfBasis *b)
+{
+    const HostSetup &h = p->hs;
+    if (npts < 1) return BSP_ERR_ARG;
+    std::vector<int> rows;
+    if (!r) {
+        if (npts != wf_quadrature(h.nkp, h.ka, h.rt.data(), h.xg.data(), h.wg.data(), nullptr, nullptr, nullptr)) return BSP_ERR_ARG;
+        rows.resize(npts);
+        wf_quadrature(h.nkp, h.ka, h.rt.data(), h.xg.data(), h.wg.data(), rows.data(), nullptr, nullptr);
+    } else if (!wf_points_valid(h.nkp, h.rt.data(), npts, r)) return BSP_ERR_ARG;
+    BSP_HIP(hipSetDevice(p->device));
+    int rc;
+    if ((rc = b->tab.alloc((size_t)npts * 2 * h.k)) || (rc = b->left.alloc(npts))) return rc;
+    DevInts d_rows;
+    DevBuf d_r;
+    if (!r) {
+        if (!p->ptab_ready) {
+            if ((rc = launch_point_table(h.nkp, h.k, h.ka, h.nfun, p->d_rt, p->d_aind, p->d_xg, p->d_wg, p->d_vpot,
+                                         p->d_ptab, p->d_left, p->d_status, p->st))) return rc;
+            p->ptab_ready = true;
+        }
+        if ((rc = d_rows.alloc(npts))) return rc;
+        BSP_HIP(hipMemcpy(d_rows.p, rows.data(), (size_t)npts * sizeof(int), hipMemcpyHostToDevice));
+        rc = launch_basis_gather(h.k, npts, d_rows.p, p->d_ptab, p->d_left, b->tab.p, b->left.p, p->st);
+    } else {
+        if ((rc = d_r.put(r, npts))) return rc;
+        rc = launch_basis_table(h.nkp, h.k, h.nfun, npts, p->d_rt, p->d_aind, d_r.p, b->tab.p, b->left.p, p->d_status, p->st);
+    }
+    const hipError_t es = hipStreamSynchronize(p->st);
+    if (rc) return rc;
+    BSP_HIP(es);
+    if ((rc = check_status(p))) { if (r) hipMemset(p->d_status, 0, sizeof(int)); return rc; }
+    return BSP_OK;
+}
+
+// vectors per pass of a host variant: U and dU of them together stay within the staging bound, one vector's rows at least
+static size_t wf_stage_vectors(int npts, bool deriv, size_t nvec)
+{
+    size_t g = wf_stage_bytes() / ((size_t)npts * (deriv ? 2 : 1) * sizeof(double));
+    if (g < 1) g = 1;
+    return g < nvec ? g : nvec;
+}
+
+// nv vectors at d_Z through the stage buffer ([m][npts] values, then [m][npts] derivatives) to the host rows U, dU
+static int wf_stage_out(bspatom_problem *p, const WfBasis &b, int npts, size_t nv, size_t g, const double *d_Z, double *stage,
+                        double *U, double *dU)
+{
+    const HostSetup &h = p->hs;
+    for (size_t v = 0; v < nv; v += g) {
+        const size_t m = nv - v < g ? nv - v : g;
+        int rc;
+        if ((rc = launch_tabulate(h.k, h.nfun, npts, (int)m, b.tab.p, b.left.p, d_Z + v * h.nfun, stage, dU ? stage + m * npts : nullptr,
+                                  p->st))) return rc;
+        BSP_HIP(hipMemcpyAsync(U + v * npts, stage, m * npts * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        if (dU) BSP_HIP(hipMemcpyAsync(dU + v * npts, stage + m * npts, m * npts * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    return BSP_OK;
+}
+
+static int tabulate_impl(bspatom_problem *p, int nvec, const double *Z, int npts, const double *r, double *U, double *dU, bool dev)
+{
+    if (!p || !Z || !U || nvec < 1 || npts < 1) return BSP_ERR_ARG;
+    const HostSetup &h = p->hs;
+    WfBasis b;
+    int rc;
+    if ((rc = wf_basis(p, npts, r, &b))) return rc;
+    DevBuf stage, zc;
+    if (dev) rc = launch_tabulate(h.k, h.nfun, npts, nvec, b.tab.p, b.left.p, Z, U, dU, p->st);
+    else {
+        const size_t g = wf_stage_vectors(npts, dU != nullptr, nvec), n = h.nfun;
+        if ((rc = stage.alloc(g * npts * (dU ? 2 : 1))) || (rc = zc.alloc(g * n))) return rc;
+        for (size_t v = 0; rc == BSP_OK && v < (size_t)nvec; v += g) {
+            const size_t m = (size_t)nvec - v < g ? (size_t)nvec - v : g;
+            if (hipMemcpyAsync(zc.p, Z + v * n, m * n * sizeof(double), hipMemcpyHostToDevice, p->st) != hipSuccess) { rc = BSP_ERR_HIP; break; }
+            rc = wf_stage_out(p, b, npts, m, g, zc.p, stage.p, U + v * npts, dU ? dU + v * npts : nullptr);
+        }
+    }
+    // every path waits for the stream before the scratch is freed (DevBuf) and before it returns
+    const hipError_t es = hipStreamSynchronize(p->st);
+    if (rc) return rc;
+    BSP_HIP(es);
+    return BSP_OK;
+}
+
+extern "C" int bspatom_tabulate(bspatom_problem *p, int nvec, const double *Z, int npts, const double *r, double *U, double *dU)
+{
+    return tabulate_impl(p, nvec, Z, npts, r, U, dU, false);
+}
+
+extern "C" int bspatom_tabulate_dev(bspatom_problem *p, int nvec, const double *Z_dev, int npts, const double *r, double *U_dev,
+                                    double *dU_dev)
+{
+    return tabulate_impl(p, nvec, Z_dev, npts, r, U_dev, dU_dev, true);
+}
+
+// The eigenvectors come from launch_inverse_iteration_batch in groups of channels (bspatom_eigvecs_batch's launch: the same bits),
+// one group's block within the staging bound (one channel at least); a group is tabulated from device memory, in place (dev) or
+// through the stage buffer.
+static int wavefunctions_impl(bspatom_problem *p, int l0, int nl, int n0, int count, int npts, const double *r, double *U, double *dU,
+                              bool dev)
+{
+    if (!p || !U) return BSP_ERR_ARG;
+    const HostSetup &h = p->hs;
+    const int n = h.nfun;
+    if (nl < 1 || count < 1 || n0 < 1 || n0 + count - 1 > n || l0 < p->last_l0 || (long)l0 + nl > (long)p->last_l0 + p->last_nl || npts < 1)
+        return BSP_ERR_ARG;
+    WfBasis b;
+    int rc;
+    if ((rc = wf_basis(p, npts, r, &b))) return rc;
+    const int ch0 = l0 - p->last_l0;
+    const size_t per_ch = (size_t)count * n;         // doubles of one channel's eigenvector block
+    size_t gmax = ((size_t)1 << 30) / count;          // channels per launch: items = group * count stays an int
+    const size_t gstage = wf_stage_bytes() / (per_ch * sizeof(double));
+    if (gstage < gmax) gmax = gstage;
+    if (gmax < 1) gmax = 1;
+    const int group = (size_t)nl < gmax ? nl : (int)gmax;
+    int slots = 0;
+    if ((rc = invit_batch_slots(h.k, group * count, &slots))) return rc;
+    DevBuf work, zblk, stage;
+    if ((rc = work.alloc((size_t)slots * invit_batch_slot_doubles(n, h.k))) || (rc = zblk.alloc((size_t)group * per_ch))) return rc;
+    const size_t gv = wf_stage_vectors(npts, dU != nullptr, (size_t)group * count);
+    if (!dev && (rc = stage.alloc(gv * npts * (dU ? 2 : 1)))) return rc;
+    hipError_t e = hipMemsetAsync(p->d_info, 0, sizeof(int), p->st);
+    for (int c = 0; e == hipSuccess && rc == BSP_OK && c < nl; c += group) {
+        const int g = (nl - c < group) ? nl - c : group, items = g * count;
+        rc = launch_inverse_iteration_batch(n, h.k, count, items, slots < items ? slots : items, p->d_SB,
+                                            p->d_HB + (size_t)(ch0 + c) * h.k * n, p->d_E + (size_t)(ch0 + c) * n + (n0 - 1),
+                                            work.p, zblk.p, p->d_info, p->st);
+        if (rc) break;
+        const size_t o = (size_t)c * count * npts;
+        if (dev) rc = launch_tabulate(h.k, n, npts, items, b.tab.p, b.left.p, zblk.p, U + o, dU ? dU + o : nullptr, p->st);
+        else rc = wf_stage_out(p, b, npts, (size_t)items, gv, zblk.p, stage.p, U + o, dU ? dU + o : nullptr);
+    }
+    const hipError_t es = hipStreamSynchronize(p->st);
+    if (rc) return rc;
+    BSP_HIP(e);
+    BSP_HIP(es);
+    return invit_failed(p);
+}
+
+extern "C" int bspatom_wavefunctions(bspatom_problem *p, int l0, int nl, int n0, int count, int npts, const double *r, double *U,
+                                     double *dU)
+{
+    return wavefunctions_impl(p, l0, nl, n0, count, npts, r, U, dU, false);
+}
+
+extern "C" int bspatom_wavefunctions_dev(bspatom_problem *p, int l0, int nl, int n0, int count, int npts, const double *r,
+                                         double *U_dev, double *dU_dev)
+{
+    return wavefunctions_impl(p, l0, nl, n0, count, npts, r, U_dev, dU_dev, true);
 }
 
 // ---- stage-level entry points ----------------------------------------------------------------

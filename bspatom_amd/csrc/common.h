@@ -90,6 +90,8 @@ struct Options {
     int cw_onediv = 0;           // BSP_CW_ONEDIV: reflectors of the band route's RQ loop in the one-division form (A/B switch)
     int dipole_stage_mb = 0;     // BSP_DIPOLE_STAGE_MB: > 0 = device scratch of one group of pairs of bspatom_dipole_matrix in MB (0 = 2 GiB); small
                                  // values force several groups (the results do not depend on the grouping: the test's hook)
+    int wf_stage_mb = 0;         // BSP_WF_STAGE_MB: > 0 = device staging of bspatom_tabulate / bspatom_wavefunctions (U and dU of one group of vectors,
+                                 // one group's eigenvector block) in MB (0 = 256 MiB); small values force several groups (the test's hook)
     int ktime = 0;               // 1: HIP events around every launch of the kernels in KSlot (bspatom_kernel_times; bench.py's
                                  // per-kernel roofline entries are measured with it in one extra, untimed step)
 };
@@ -258,6 +260,18 @@ int launch_dipole_block(int n, int count_ini, int count_fin, int npairs, const l
                         double *d_out, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
+// wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)
+// host: points / weights of the assembly's quadrature on the intervals of positive width and their rows of the point table
+int wf_quadrature(int nkp, int ka, const double *rt, const double *xg, const double *wg, int *rows, double *r, double *w);
+bool wf_points_valid(int nkp, const double *rt, int npts, const double *r);
+// basis table of a call, point index fastest: d_tab[j * npts + ip] (j < k: B, k <= j < 2k: B'), d_tleft[ip] = left
+int launch_basis_table(int nkp, int k, int nfun, int npts, const double *d_rt, const double *d_aind, const double *d_r, double *d_tab,
+                       int *d_tleft, int *d_status, hipStream_t st);
+int launch_basis_gather(int k, int npts, const int *d_rows, const double *d_ptab, const int *d_pleft, double *d_tab, int *d_tleft,
+                        hipStream_t st);
+// d_U[v * npts + ip] = sum_j d_Z[v * nfun + j] B_j(r_ip), d_dU likewise with B' (null: values only)
+int launch_tabulate(int k, int nfun, int npts, int nvec, const double *d_tab, const int *d_tleft, const double *d_Z, double *d_U,
+                    double *d_dU, hipStream_t st);
 
 // capi.hip: enqueue Cholesky -> standard form -> sy2sb -> sb2st -> bisection on `st` for nl channels
 // whose upper bands are already in d_SB / d_HB.  ev (optional): 5 events recorded at the stage

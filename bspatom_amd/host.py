@@ -456,6 +456,51 @@ def dipole_matelem(prob, channels, n1_max, kind_pi=1, mph=0):
     return z
 
 
+# ---- wavefunctions on r: files per state, radial integrals on the assembly's quadrature ------------------------------------
+def write_wf_states(outdir, prob, l, n0, count, npts=10000):
+    """One `wf_l<l>_n<n>.dat` per state n = n0 .. n0+count-1 of channel l in WRITE_WF's format (Bsp_Atom.f90:118-146:
+    npts + 1 records '(2G20.10)' `r_i, u(r_i)`, r_i = ra + i*(rb-ra)/npts), all states from ONE prob.wavefunctions call.
+    Returns the paths."""
+    import numpy as np
+    ra, rb = float(prob.inp.ra), float(prob.inp.rb)
+    r = ra + np.arange(npts + 1, dtype=np.float64) * ((rb - ra) / float(npts))
+    U = prob.wavefunctions(l, 1, n0, count, r=r, deriv=False)[0]
+    rtxt = [fortran_g(float(ri), 20, 10) for ri in r]
+    paths = []
+    for j in range(count):
+        paths.append(os.path.join(outdir, "wf_l%d_n%d.dat" % (l, n0 + j)))
+        with open(paths[-1], "w") as f:
+            for rt_, ui in zip(rtxt, U[j]):
+                f.write(rt_ + fortran_g(float(ui), 20, 10) + "\n")
+    return paths
+
+
+def radial_matrix(prob, pairs, g, n0_ini, count_ini, n0_fin, count_fin, deriv=False):
+    """D[p, i, f] = <f| g(r) |i> = sum_q w_q g(r_q) u_f(r_q) u_i(r_q), or <f| g(r) d/dr |i> = sum_q w_q g(r_q) u_f(r_q) u_i'(r_q)
+    with deriv, for every (l_ini, l_fin) = pairs[p], i < count_ini, f < count_fin (1-based windows from n0_ini, n0_fin): the
+    layout of Problem.dipole_matrix.  The sum is the assembly's own Gauss-Legendre quadrature (prob.quadrature()), so g = r,
+    g = 1/r and g = 1 with deriv give what dipole_matrix gives with a = (1,0,0), (0,1,0), (0,0,1), up to rounding.  g: a
+    callable of the array of points, or an array on the quadrature grid.  NumPy on the host tables of prob.wavefunctions (one
+    call per distinct channel and role): for moderate sizes; heavy users contract the tables of wavefunctions_dev on the GPU."""
+    import numpy as np
+    r, w = prob.quadrature()
+    gw = np.asarray(g(r) if callable(g) else g, dtype=np.float64) * w
+    if gw.shape != r.shape:
+        raise ValueError("g must give one value per quadrature point (%d), got shape %s" % (r.size, gw.shape))
+    pairs = [(int(li), int(lf)) for li, lf in pairs]
+    ini, fin = {}, {}
+    for li, lf in pairs:
+        if li not in ini:
+            t = prob.wavefunctions(li, 1, n0_ini, count_ini, deriv=deriv)
+            ini[li] = (t[1] if deriv else t)[0]
+        if lf not in fin:
+            fin[lf] = prob.wavefunctions(lf, 1, n0_fin, count_fin, deriv=False)[0]
+    D = np.zeros((len(pairs), count_ini, count_fin))
+    for p, (li, lf) in enumerate(pairs):
+        D[p] = (ini[li] * gw) @ fin[lf].T
+    return D
+
+
 # ---- KIND_PI = 0 on several GPUs: one process per GPU, channels sharded, spectra gathered (SURVEY 8e) ---------------
 def write_structure_outputs(nfun, lmax, E, l_ini, wf, outdir):
     """Enl.dat, wf_n0.dat and the stdout text of a KIND_PI = 0 run from the spectra E[l][i] and the tabulated initial

@@ -153,6 +153,44 @@ int bspatom_dipole_matrix_dev(bspatom_problem *p, int npairs, const int32_t *l_i
  * i = 0..npts.  Returns BSPATOM_ERR_BSPLVB where the reference STOPs. r[npts+1], u[npts+1]. */
 int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u);
 
+/* ---- wavefunctions and their derivatives as functions of r (csrc/wavefn.hip) --------------------------------------------- */
+/* The points and weights of the assembly's Gauss-Legendre quadrature (matrices.f90:91-97: r = f1 + xg*f2, dr = f2*wg with
+ * f1 = (rt(i+1) + rt(i))/2, f2 = (rt(i+1) - rt(i))/2) for the knot intervals of positive width (rt(i+1) > rt(i)), ascending, ka per
+ * interval: the grid rtot of TORMAT / WFALL (TorusFuns.f90:87-104, nr = nointv*ka).  *nr = their number; r, w may be NULL (size
+ * query).  ON PURPOSE these are the assembly's f1 + xg*f2, not a second gauleg(rt(i), rt(i+1)) as TORMAT calls it (:99): on the
+ * assembly's own points sum_p w_p u_i(r_p) u_j(r_p) is c_i^T S c_j term for term, and likewise for the rij of MATRIX_SVT, so every
+ * radial integral <f| g(r) |i>, <f| g(r) d/dr |i> formed from the tables below is the quadrature the matrices were built with.
+ * Host arithmetic, no GPU work. */
+int bspatom_quadrature(bspatom_problem *p, int *nr, double *r, double *w);
+
+/* WFALL (TorusFuns.f90:193-261) for any block of coefficient vectors:
+ *   U[v*npts + ip] = sum_j Z[v*nfun + j] B_j(r_ip),   dU[v*npts + ip] = sum_j Z[v*nfun + j] B_j'(r_ip)   (dU may be NULL: values only)
+ * for v < nvec, ip < npts.  r is a HOST pointer in every variant; r == NULL selects the quadrature grid above (npts must then equal
+ * nr; the assembly's point table is run first if it has not been and its B_j, B_j' are used).  The caller's points may be unsorted and
+ * may repeat; each must be finite and lie in [rt(1), rt(nkp)] (BSPATOM_ERR_ARG otherwise, checked on the host before any launch).
+ * The interval of a point is interv's (interv.f90:86-117), including the walk down at r == rt(nkp); BSPATOM_ERR_BSPLVB where the
+ * reference STOPs (bsplvb.f90:30-34).  B_j, B_j' are BSPALL's (Modules.f90:71-110): two bsplvb recurrences, dbsp = (k-1) (Aind1
+ * bspp(j) - Aind2 bspp(j+1)), zero coefficients outside 1..nfun; the sums run over the k local functions ascending from 0.0, one IEEE
+ * multiply and one IEEE add per term, IEEE division, no FMA -- WFALL's order.  So a value is reproducible bit for bit from a CPU
+ * restatement, run-to-run identical, and independent of grouping, tiling and the other vectors of the call.
+ * The host variant stages U and dU together through a device buffer of at most 256 MiB (bspatom_set_option("wf_stage_mb", m) sets
+ * another bound; one vector's rows at least); the _dev variant (Z_dev, U_dev, dU_dev in device memory of the problem's device) writes
+ * in place, its scratch is the basis table: npts*2k doubles and npts ints.  BSPATOM_ERR_ARG: a null p, Z or U, nvec < 1, npts < 1,
+ * r == NULL with npts != nr, a bad point. */
+int bspatom_tabulate(bspatom_problem *p, int nvec, const double *Z, int npts, const double *r, double *U, double *dU);
+int bspatom_tabulate_dev(bspatom_problem *p, int nvec, const double *Z_dev, int npts, const double *r, double *U_dev, double *dU_dev);
+
+/* The same for the eigenvectors n0 .. n0+count-1 (1-based) of channels l0 .. l0+nl-1 of the last solve -- fur(ir, n, l), dfur(ir, n, l)
+ * of WFALL (TorusFuns.f90:218, 245-246), the factors of FRMATINT's u_i u_j'/r^2 and u_i u_j/r^3 (TorusFunsInts.f90:286-382):
+ *   U[((size_t)c*count + j)*npts + ip] = u(r_ip) of eigenvector n0+j of channel l0+c, dU likewise (may be NULL).
+ * The eigenvectors are bspatom_eigvecs' bit for bit (signs, S-normalisation), computed in groups of channels whose block stays within
+ * the bound above (one channel at least): the result equals bspatom_tabulate* applied to bspatom_eigvecs_batch's output, bit for bit.
+ * Points as above.  BSPATOM_ERR_ARG as bspatom_eigvecs_batch (every channel after bspatom_assemble) and for the points;
+ * BSPATOM_ERR_UNSUPPORTED if an inverse iteration broke down. */
+int bspatom_wavefunctions(bspatom_problem *p, int l0, int nl, int n0, int count, int npts, const double *r, double *U, double *dU);
+int bspatom_wavefunctions_dev(bspatom_problem *p, int l0, int nl, int n0, int count, int npts, const double *r, double *U_dev,
+                              double *dU_dev);
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
