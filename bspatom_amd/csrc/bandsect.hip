@@ -18,7 +18,7 @@
 // eigenvalue; the search needs no monotonicity (lo = the point before the FIRST point whose count exceeds m), its result is an
 // eigenvalue of the pencil to ~1e-13 of the spectrum's width in practice, and the caller does not rest on that: once the spectra are
 // there it checks the value against eigenvalue m of the tridiagonal matrix and its neighbours, and otherwise forgets the early
-// vector (capi.hip::solve_impl; bspatom_eigvec then computes it from the spectra as for any other vector).
+// vector (capi.hip::solve_impl; capi_states.hip::bspatom_eigvec then computes it from the spectra as for any other vector).
 #include "bandsect.h"
 
 namespace bsp {

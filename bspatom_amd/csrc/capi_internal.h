@@ -1,0 +1,112 @@
+// capi_internal.h -- what the translation units of the C ABI share (capi.hip: handle, options, solve; capi_states.hip: the
+// consumers of the last solve; capi_stage.hip: the stage-level entry points).  Private to csrc.
+#pragma once
+#include <cstring>
+#include <vector>
+#include "common.h"
+#include "host_setup.h"
+#include "../../include/bspatom.h"
+
+struct bspatom_problem {
+    bsp::HostSetup hs;
+    int device, npad;
+    hipStream_t st = nullptr;
+    // device: set-up tables
+    double *d_rt = nullptr, *d_aind = nullptr, *d_xg = nullptr, *d_wg = nullptr, *d_vpot = nullptr, *d_bl = nullptr;
+    double *d_ptab = nullptr; int *d_left = nullptr; int *d_status = nullptr;
+    bool ptab_ready = false;
+    // device: per-solve buffers (sized for cap_nl channels)
+    int cap_nl = 0;
+    double *d_SB = nullptr, *d_HB = nullptr, *d_UB = nullptr, *d_rdiag = nullptr;
+    double *d_Y = nullptr, *d_C = nullptr, *d_AB = nullptr, *d_d = nullptr, *d_e = nullptr, *d_E = nullptr;
+    void *d_work = nullptr, *d_sbctl = nullptr;
+    void *d_cwork = nullptr;         // band route (crawford.hip)
+    int cap_dense = 0, cap_band = 0; // channels the dense buffers (Y, C, work) / the band route's work area are sized for
+    int *d_info = nullptr;
+    // eigenvector / wave-function scratch
+    double *d_vwork = nullptr, *d_vec = nullptr, *d_wfr = nullptr, *d_wfu = nullptr, *d_Esel = nullptr;
+    int *d_chan = nullptr;
+    int wf_cap = 0;
+    // the eigenvector the reference consumes, Hij(:, n0_ini) of channel l_ini (matrices.f90:267), computed on a side
+    // stream while the batched bisection runs; bspatom_eigvec returns it when asked for exactly that state
+    hipStream_t st2 = nullptr;
+    hipEvent_t evx = nullptr;
+    hipStream_t stS = nullptr;                // band route: the S-only part of the reduction beside the assembly of the H_l
+    hipEvent_t evS = nullptr, evC[bsp::CW_CHUNKS] = {};
+    bool pre_early = false, pre_early_ok = false;   // the prefetched vector's eigenvalue came from the pencil (bandsect.hip); it passed the check
+    double *d_pvec = nullptr, *d_pE = nullptr;
+    int *d_pinfo = nullptr;
+    int pre_l = -1, pre_n0 = -1, pre_ch = 0;
+    // last solve
+    int last_l0 = 0, last_nl = 0;
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double ms[6] = {0, 0, 0, 0, 0, 0};
+};
+
+namespace bsp {
+inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// BSP_HIP as an expression: BSP_OK, or BSP_ERR_HIP with the error printed
+#define HIP_RC(x) ([&]() -> int { BSP_HIP(x); return BSP_OK; }())
+
+// n elements of device memory (one at least), freed when the owner leaves its scope: what was enqueued on them must be complete
+// by then (drain / finish below)
+template <class T>
+class DevArray {
+public:
+    T *p = nullptr;
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    ~DevArray() { hipFree(p); }
+    int alloc(size_t n) { BSP_HIP(hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T))); return BSP_OK; }
+    int put(const T *h, size_t n) { const int rc = alloc(n); return rc ? rc : HIP_RC(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice)); }
+    int get(T *h, size_t n) const { return HIP_RC(hipMemcpy(h, p, n * sizeof(T), hipMemcpyDeviceToHost)); }
+};
+
+// the point table of the problem's grid (assemble.hip), run on the problem's stream the first time something needs it
+inline int ensure_point_table(bspatom_problem *p)
+{
+    if (p->ptab_ready) return BSP_OK;
+    const HostSetup &h = p->hs;
+    const int rc = launch_point_table(h.nkp, h.k, h.ka, h.nfun, p->d_rt, p->d_aind, p->d_xg, p->d_wg, p->d_vpot, p->d_ptab, p->d_left,
+                                      p->d_status, p->st);
+    if (!rc) p->ptab_ready = true;
+    return rc;
+}
+
+// the kernels' status word (common.h): BSP_OK or the error one of them left
+inline int check_status(bspatom_problem *p)
+{
+    int st = 0;
+    BSP_HIP(hipMemcpy(&st, p->d_status, sizeof(int), hipMemcpyDeviceToHost));
+    return st;
+}
+
+// d_info after inverse iterations: 1 + index of a vector whose iterate had norm zero (eigvec.hip), else 0
+inline int invit_failed(bspatom_problem *p)
+{
+    int v = 0;
+    BSP_HIP(hipMemcpy(&v, p->d_info, sizeof(int), hipMemcpyDeviceToHost));
+    return v ? BSP_ERR_UNSUPPORTED : BSP_OK;
+}
+
+// states n0 .. n0+count-1 (from 1) of channels l0 .. l0+nl-1: BSP_OK if the last solve holds them all, else BSP_ERR_ARG
+inline int last_solve_window(const bspatom_problem *p, int l0, int nl, int n0, int count)
+{
+    return nl >= 1 && count >= 1 && n0 >= 1 && (long)n0 + count - 1 <= p->hs.nfun && l0 >= p->last_l0 &&
+           (long)l0 + nl <= (long)p->last_l0 + p->last_nl ? BSP_OK : BSP_ERR_ARG;
+}
+
+// The tail of an entry point that enqueued work on p->st, called while its DevArrays are alive: EVERY path waits for the stream
+// before the scratch is freed and before the call returns.  rc, the first error of the call so far, comes before the wait's own.
+inline int drain(bspatom_problem *p, int rc)
+{
+    const hipError_t es = hipStreamSynchronize(p->st);
+    return rc ? rc : HIP_RC(es);
+}
+
+// drain, then whether an inverse iteration of the call broke down
+inline int finish(bspatom_problem *p, int rc) { return (rc = drain(p, rc)) ? rc : invit_failed(p); }
+
+int ensure_vec_scratch(bspatom_problem *p);     // capi.hip: d_vwork, d_vec, d_chan, d_Esel for one vector
+}  // namespace bsp
