@@ -33,7 +33,8 @@ class Sizes(C.Structure):
 
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
-           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -69,6 +70,10 @@ def lib():
         L.bspatom_dipole_matrix.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.bspatom_dipole_matrix_dev.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.bspatom_dipole_bands.argtypes = [vp, vp]
+        L.bspatom_operator_bands.argtypes = [vp, i32, vp, vp, vp]
+        L.bspatom_operator_bands_dev.argtypes = [vp, i32, vp, vp, vp]
+        L.bspatom_operator_matrix.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+        L.bspatom_operator_matrix_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.bspatom_write_wf.argtypes = [vp, vp, i32, vp, vp]
         L.bspatom_quadrature.argtypes = [vp, C.POINTER(i32), vp, vp]
         L.bspatom_tabulate.argtypes = [vp, i32, vp, i32, vp, vp, vp]
@@ -236,6 +241,68 @@ class Problem:
         li, lf, a = self._dipole_pairs(pairs, a)
         _chk(lib().bspatom_dipole_matrix_dev(self._h, len(li), _p(li), _p(lf), n0_ini, count_ini, n0_fin, count_fin, _p(a),
                                              C.c_void_p(dev_ptr)), "bspatom_dipole_matrix_dev")
+
+    def _nr(self):
+        nr = C.c_int(0)
+        _chk(lib().bspatom_quadrature(self._h, C.byref(nr), None, None), "bspatom_quadrature")
+        return nr.value
+
+    @staticmethod
+    def _deriv(deriv, nop):
+        deriv = np.ascontiguousarray(deriv, dtype=np.int32).reshape(-1)
+        assert deriv.shape == (nop,), deriv.shape
+        return deriv
+
+    def _operators(self, g, deriv):
+        """(nop, g as (nop, nr) float64, deriv as (nop,) int32) of host operator arguments"""
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        g = g.reshape(-1, g.shape[-1]) if g.ndim else g.reshape(1, 1)
+        assert g.shape[1] == self._nr(), (g.shape, self._nr())
+        return g.shape[0], g, self._deriv(deriv, g.shape[0])
+
+    @staticmethod
+    def _operator_pairs(pairs, a, nop):
+        pr = np.asarray(list(pairs), dtype=np.int32).reshape(-1, 2)
+        li, lf = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape == (nop,):
+            a = np.broadcast_to(a, (len(pr), nop))
+        assert a.shape == (len(pr), nop), a.shape
+        return li, lf, np.ascontiguousarray(a)
+
+    def operator_bands(self, g, deriv):
+        """Full bands (nop, 2k-1, nfun) of G_o(i, j) = sum_q B_i(r_q) g[o, q] X_j(r_q) w_q on the quadrature grid (quadrature()),
+        X = B_j (deriv[o] = 0) or B_j' (1): [o, d + k - 1, i] = G_o(i, i + d).  With g = (r, 1/r, 1), deriv = (0, 0, 1) these are
+        dipole_bands() bit for bit.  g: (nop, nr) or (nr,)."""
+        nop, g, deriv = self._operators(g, deriv)
+        GB = np.zeros((nop, 2 * self.k - 1, self.nfun))
+        _chk(lib().bspatom_operator_bands(self._h, nop, _p(g), _p(deriv), _p(GB)), "bspatom_operator_bands")
+        return GB
+
+    def operator_bands_dev(self, nop, g_ptr, deriv, GB_ptr):
+        """operator_bands with g (nop * nr doubles at g_ptr) and the bands (nop * (2k-1) * nfun doubles at GB_ptr) in device memory
+        of this problem's device, e.g. torch tensors' data_ptr(); written in place.  deriv is a host array."""
+        _chk(lib().bspatom_operator_bands_dev(self._h, nop, C.c_void_p(g_ptr), _p(self._deriv(deriv, nop)), C.c_void_p(GB_ptr)),
+             "bspatom_operator_bands_dev")
+
+    def operator_matrix(self, pairs, g, deriv, n0_ini, count_ini, n0_fin, count_fin, a):
+        """D[p, i, f] = c(l_fin, n0_fin+f)^T (sum_o a[p, o] G_o) c(l_ini, n0_ini+i) for every (l_ini, l_fin) = pairs[p] in one call,
+        G_o the operator_bands of (g, deriv): array (npairs, count_ini, count_fin), the layout and the conventions of
+        dipole_matrix.  a: (npairs, nop), or (nop,) for every pair."""
+        nop, g, deriv = self._operators(g, deriv)
+        li, lf, a = self._operator_pairs(pairs, a, nop)
+        D = np.zeros((len(li), max(count_ini, 0), max(count_fin, 0)))
+        _chk(lib().bspatom_operator_matrix(self._h, nop, _p(g), _p(deriv), len(li), _p(li), _p(lf), n0_ini, count_ini, n0_fin,
+                                           count_fin, _p(a), _p(D)), "bspatom_operator_matrix")
+        return D
+
+    def operator_matrix_dev(self, pairs, nop, g_ptr, deriv, n0_ini, count_ini, n0_fin, count_fin, a, dev_ptr):
+        """operator_matrix with g (nop * nr doubles at g_ptr) and D (npairs * count_ini * count_fin doubles at dev_ptr) in device
+        memory of this problem's device, written in place; deriv and a are host arrays.  Returns when the block is there."""
+        li, lf, a = self._operator_pairs(pairs, a, nop)
+        _chk(lib().bspatom_operator_matrix_dev(self._h, nop, C.c_void_p(g_ptr), _p(self._deriv(deriv, nop)), len(li), _p(li), _p(lf),
+                                               n0_ini, count_ini, n0_fin, count_fin, _p(a), C.c_void_p(dev_ptr)),
+             "bspatom_operator_matrix_dev")
 
     def write_wf(self, c, npts=10000):
         c = np.ascontiguousarray(c, dtype=np.float64)

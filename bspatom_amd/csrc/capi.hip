@@ -103,7 +103,8 @@ const char *const KSLOT_NAMES[KS_COUNT] = {"gemm2_kernel<128,128,MODE 1> (rank-1
                                           "panel_qr2_kernel / panel_qr_kernel", "sy2sb chain: G, K (split-K gemm_kernel + splitk_reduce), form_T, tsmm64 (W, Z)",
                                           "sb2sb_mfma_kernel (band 64 -> 16)", "sbr_rows_kernel<8> / <16> / sb16st_kernel (one-column chase to tridiagonal)", "bisect3_kernel",
                                           "band_cholesky_kernel + std_form_kernel",
-                                          "crawford_item_kernel and its set-up kernels (band route: pencil -> band 15)"};
+                                          "crawford_item_kernel and its set-up kernels (band route: pencil -> band 15)",
+                                          "operator_band_kernel (bands of caller-given g(r), g(r) d/dr)"};
 }  // namespace
 void ktime_begin(int slot, hipStream_t st)
 {

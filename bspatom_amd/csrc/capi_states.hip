@@ -216,11 +216,13 @@ extern "C" int bspatom_dipole_elements(bspatom_problem *p, int l_ini, int n0_ini
 // stays within DIPOLE_STAGE_BYTES (option dipole_stage_mb), one pair at least.  The eigenvectors are bspatom_eigvecs' bit for
 // bit (one EigBlocks launch per run of consecutive channels and window); nothing of a pair's arithmetic depends on
 // the other pairs or on the grouping.  The scratch of the inverse iterations is one slot per resident wave beside that.
+// pair_matrix_impl is that plan for any number nco of coefficients per pair (bspatom_operator_matrix: A_p = sum_o a[p*nco + o]
+// G_o); the operator bands and the apply launch are the caller's, the bands counted outside the bound.
 static constexpr size_t DIPOLE_STAGE_BYTES = (size_t)2 << 30;
 namespace {
-struct DipItem {                                   // W item: operator and initial channel
-    int ch; uint64_t a[3];
-    bool operator<(const DipItem &o) const { return ch != o.ch ? ch < o.ch : memcmp(a, o.a, sizeof a) < 0; }
+struct DipItem {                                   // W item: operator (nco coefficients of the caller's array) and initial channel
+    int ch, nco; const double *a;
+    bool operator<(const DipItem &o) const { return ch != o.ch ? ch < o.ch : memcmp(a, o.a, (size_t)nco * sizeof(double)) < 0; }
 };
 struct DipRun { int ch, len, w; size_t pos; };     // channels ch .. ch+len-1, block pos .. of the list of window w (0: chA, 1: chB)
 struct DipGroup {
@@ -247,10 +249,13 @@ struct DipGroup {
 };
 }  // namespace
 
-static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini,
-                              int n0_fin, int count_fin, const double *a, double *D, bool dev)
+// bands(): allocates and enqueues the operator bands of the call on the problem's stream (after the point table);
+// apply(nitems, d_acoef, d_xoff, d_base, d_W): the launch of W = A x for nitems items, d_acoef[nitems][nco].
+template <class Bands, class Apply>
+static int pair_matrix_impl(bspatom_problem *p, int nco, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini,
+                            int count_ini, int n0_fin, int count_fin, const double *a, double *D, bool dev, Bands bands, Apply apply)
 {
-    if (!p || !l_ini || !l_fin || !a || !D || npairs < 1) return BSP_ERR_ARG;
+    if (!p || !l_ini || !l_fin || !a || !D || npairs < 1 || nco < 1) return BSP_ERR_ARG;
     for (int q = 0; q < npairs; ++q)
         if (last_solve_window(p, l_ini[q], 1, n0_ini, count_ini) || last_solve_window(p, l_fin[q], 1, n0_fin, count_fin)) return BSP_ERR_ARG;
     const HostSetup &h = p->hs;
@@ -265,7 +270,7 @@ static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_i
     dipole_kslices(n, count_ini, count_fin, &chunk, &ns);
     const size_t per_pair = (ns > 1 ? (size_t)ns * mn : 0) + (dev ? 0 : mn);
     const size_t limit = (opts().dipole_stage_mb > 0 ? (size_t)opts().dipole_stage_mb << 20 : DIPOLE_STAGE_BYTES) / sizeof(double);
-    auto item_of = [&](int q) { DipItem t; t.ch = l_ini[q] - lo; memcpy(t.a, a + 3 * (size_t)q, sizeof t.a); return t; };
+    auto item_of = [&](int q) { return DipItem{l_ini[q] - lo, nco, a + (size_t)nco * q}; };
     auto doubles_of = [&](const DipGroup &g) {
         return g.chA.size() * vi + g.chB.size() * vf + g.items.size() * vi + (size_t)g.np * per_pair;
     };
@@ -301,13 +306,13 @@ static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_i
         for (const DipRun &r : g.runs) max_run_items = std::max(max_run_items, r.len * cntw[r.w]);
     }
     std::vector<long long> tab(nitems_all + 2 * (size_t)npairs);      // [xoff of every item | (W, Z) offsets of every pair]
-    std::vector<double> acoef(3 * nitems_all);
+    std::vector<double> acoef((size_t)nco * nitems_all);
     size_t q0 = 0;                                                    // items of the groups before
     for (const DipGroup &g : groups) {
         const size_t offB = g.chA.size() * vi, offW = offB + g.chB.size() * vf;
         for (size_t t = 0; t < g.items.size(); ++t) {
             tab[q0 + t] = (long long)((size_t)DipGroup::pos(g.chA, g.items[t].ch) * vi);
-            memcpy(&acoef[3 * (q0 + t)], g.items[t].a, sizeof g.items[t].a);
+            memcpy(&acoef[(size_t)nco * (q0 + t)], g.items[t].a, (size_t)nco * sizeof(double));
         }
         for (int q = g.p0; q < g.p0 + g.np; ++q) {
             const int cf = l_fin[q] - lo;
@@ -317,14 +322,14 @@ static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_i
         }
         q0 += g.items.size();
     }
-    DevArray<double> RB, stage, dA;
+    DevArray<double> stage, dA;
     DevArray<long long> dtab;
     EigBlocks eb;
-    if ((rc = RB.alloc(dipole_band_doubles(h))) || (rc = eb.prepare(p, max_run_items)) || (rc = stage.alloc(stage_doubles)) ||
+    if ((rc = eb.prepare(p, max_run_items)) || (rc = stage.alloc(stage_doubles)) ||
         (rc = dA.put(acoef.data(), acoef.size())) || (rc = dtab.put(tab.data(), tab.size()))) return rc;
     // ---- group by group on the problem's stream ----
     rc = HIP_RC(hipMemsetAsync(p->d_info, 0, sizeof(int), p->st));
-    if (!rc) rc = launch_dipole_bands(n, h.k, h.ka, h.nkp, p->d_ptab, p->d_left, RB.p, p->st);
+    if (!rc) rc = bands();
     q0 = 0;
     for (size_t gi = 0; !rc && gi < groups.size(); ++gi) {
         const DipGroup &g = groups[gi];
@@ -332,8 +337,7 @@ static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_i
         const size_t offD = offP + (ns > 1 ? (size_t)g.np * ns * mn : 0);
         for (const DipRun &r : g.runs)
             if (!rc) rc = eb.launch(p, r.ch, r.len, n0w[r.w], cntw[r.w], stage.p + (r.w ? offB + r.pos * vf : r.pos * vi));
-        if (!rc) rc = launch_band_apply_block(n, h.k, count_ini, (int)g.items.size(), RB.p, dA.p + 3 * q0, dtab.p + q0, stage.p,
-                                              stage.p + offW, p->st);
+        if (!rc) rc = apply((int)g.items.size(), dA.p + (size_t)nco * q0, dtab.p + q0, stage.p, stage.p + offW);
         double *out = dev ? D + (size_t)g.p0 * mn : stage.p + offD;
         if (!rc) rc = launch_dipole_block(n, count_ini, count_fin, g.np, dtab.p + nitems_all + 2 * (size_t)g.p0, stage.p,
                                           ns > 1 ? stage.p + offP : nullptr, out, p->st);
@@ -342,6 +346,21 @@ static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_i
     }
     if ((rc = finish(p, rc))) return rc;
     return check_status(p);
+}
+
+static int dipole_matrix_impl(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini,
+                              int n0_fin, int count_fin, const double *a, double *D, bool dev)
+{
+    DevArray<double> RB;
+    return pair_matrix_impl(p, 3, npairs, l_ini, l_fin, n0_ini, count_ini, n0_fin, count_fin, a, D, dev,
+        [&]() {
+            const HostSetup &h = p->hs;
+            const int rc = RB.alloc(dipole_band_doubles(h));
+            return rc ? rc : launch_dipole_bands(h.nfun, h.k, h.ka, h.nkp, p->d_ptab, p->d_left, RB.p, p->st);
+        },
+        [&](int nitems, const double *d_acoef, const long long *d_xoff, const double *d_base, double *d_W) {
+            return launch_band_apply_block(p->hs.nfun, p->hs.k, count_ini, nitems, RB.p, d_acoef, d_xoff, d_base, d_W, p->st);
+        });
 }
 
 extern "C" int bspatom_dipole_matrix(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini,
@@ -353,6 +372,102 @@ extern "C" int bspatom_dipole_matrix_dev(bspatom_problem *p, int npairs, const i
                                          int count_ini, int n0_fin, int count_fin, const double *a, double *D_dev)
 {
     return dipole_matrix_impl(p, npairs, l_ini, l_fin, n0_ini, count_ini, n0_fin, count_fin, a, D_dev, true);
+}
+
+// ---- caller-given radial operators g(r), g(r) d/dr (opmat.hip) -------------------------------------------------------------
+namespace {
+// The operator bands of a call: g (nop*nr doubles indexed like bspatom_quadrature's points; host memory is uploaded once, device
+// memory is read in place), deriv and the interval table of operator_band_kernel (from wf_quadrature's rows) on the device.
+struct OpBands {
+    int nop = 0, nr = 0;
+    DevArray<double> g_up, GB;
+    DevArray<int> deriv, qfirst;
+    const double *d_g = nullptr;
+    double *band = nullptr;                        // [nop][2k-1][nfun]: GB, or the caller's device memory
+    static bool args_ok(const bspatom_problem *p, int nop, const double *g, const int32_t *deriv)
+    {
+        if (!p || !g || !deriv || nop < 1) return false;
+        for (int o = 0; o < nop; ++o)
+            if (deriv[o] != 0 && deriv[o] != 1) return false;
+        return true;
+    }
+    int prepare(bspatom_problem *p, int nop_, const double *g, bool g_dev, const int32_t *deriv_, double *GB_dev)
+    {
+        const HostSetup &h = p->hs;
+        nop = nop_;
+        nr = wf_quadrature(h.nkp, h.ka, h.rt.data(), h.xg.data(), h.wg.data(), nullptr, nullptr, nullptr);
+        if (nr < 1) return BSP_ERR_ARG;
+        std::vector<int> rows(nr), qf(h.nkp - 1, -1), dv(deriv_, deriv_ + nop);
+        wf_quadrature(h.nkp, h.ka, h.rt.data(), h.xg.data(), h.wg.data(), rows.data(), nullptr, nullptr);
+        for (int q = 0; q < nr; q += h.ka) qf[rows[q] / h.ka] = q;
+        int rc;
+        if ((rc = qfirst.put(qf.data(), qf.size())) || (rc = deriv.put(dv.data(), dv.size()))) return rc;
+        if (!GB_dev && (rc = GB.alloc(doubles(h)))) return rc;
+        band = GB_dev ? GB_dev : GB.p;
+        if (g_dev) d_g = g;
+        else { if ((rc = g_up.put(g, (size_t)nop * nr))) return rc; d_g = g_up.p; }
+        return BSP_OK;
+    }
+    size_t doubles(const HostSetup &h) const { return (size_t)nop * (2 * h.k - 1) * h.nfun; }
+    int launch(bspatom_problem *p) const
+    {
+        const HostSetup &h = p->hs;
+        return launch_operator_bands(h.nfun, h.k, h.ka, h.nkp, nop, nr, p->d_ptab, p->d_left, qfirst.p, d_g, deriv.p, band, p->st);
+    }
+};
+}  // namespace
+
+static int operator_bands_impl(bspatom_problem *p, int nop, const double *g, const int32_t *deriv, double *GB, bool dev)
+{
+    if (!OpBands::args_ok(p, nop, g, deriv) || !GB) return BSP_ERR_ARG;
+    BSP_HIP(hipSetDevice(p->device));
+    int rc;
+    if ((rc = ensure_point_table(p))) return rc;
+    OpBands ob;
+    if ((rc = ob.prepare(p, nop, g, dev, deriv, dev ? GB : nullptr))) return rc;
+    rc = ob.launch(p);
+    if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(GB, ob.band, ob.doubles(p->hs) * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    if ((rc = drain(p, rc))) return rc;
+    return check_status(p);
+}
+
+extern "C" int bspatom_operator_bands(bspatom_problem *p, int nop, const double *g, const int32_t *deriv, double *GB)
+{
+    return operator_bands_impl(p, nop, g, deriv, GB, false);
+}
+extern "C" int bspatom_operator_bands_dev(bspatom_problem *p, int nop, const double *g_dev, const int32_t *deriv, double *GB_dev)
+{
+    return operator_bands_impl(p, nop, g_dev, deriv, GB_dev, true);
+}
+
+// bspatom_dipole_matrix's plan (pair_matrix_impl) with the bands of the caller's operators and nop coefficients per pair
+static int operator_matrix_impl(bspatom_problem *p, int nop, const double *g, const int32_t *deriv, int npairs, const int32_t *l_ini,
+                                const int32_t *l_fin, int n0_ini, int count_ini, int n0_fin, int count_fin, const double *a, double *D,
+                                bool dev)
+{
+    if (!OpBands::args_ok(p, nop, g, deriv)) return BSP_ERR_ARG;
+    OpBands ob;
+    return pair_matrix_impl(p, nop, npairs, l_ini, l_fin, n0_ini, count_ini, n0_fin, count_fin, a, D, dev,
+        [&]() {
+            const int rc = ob.prepare(p, nop, g, dev, deriv, nullptr);
+            return rc ? rc : ob.launch(p);
+        },
+        [&](int nitems, const double *d_acoef, const long long *d_xoff, const double *d_base, double *d_W) {
+            return launch_band_combine_apply(p->hs.nfun, p->hs.k, nop, count_ini, nitems, ob.band, d_acoef, d_xoff, d_base, d_W, p->st);
+        });
+}
+
+extern "C" int bspatom_operator_matrix(bspatom_problem *p, int nop, const double *g, const int32_t *deriv, int npairs,
+                                       const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini, int n0_fin,
+                                       int count_fin, const double *a, double *D)
+{
+    return operator_matrix_impl(p, nop, g, deriv, npairs, l_ini, l_fin, n0_ini, count_ini, n0_fin, count_fin, a, D, false);
+}
+extern "C" int bspatom_operator_matrix_dev(bspatom_problem *p, int nop, const double *g_dev, const int32_t *deriv, int npairs,
+                                           const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini, int n0_fin,
+                                           int count_fin, const double *a, double *D_dev)
+{
+    return operator_matrix_impl(p, nop, g_dev, deriv, npairs, l_ini, l_fin, n0_ini, count_ini, n0_fin, count_fin, a, D_dev, true);
 }
 
 extern "C" int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u)

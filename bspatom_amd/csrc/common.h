@@ -106,7 +106,7 @@ void process_device_latch(int device);
 // Two events per launch, recorded on the launch's own stream; bspatom_kernel_times() sums the elapsed times per slot after
 // the device has drained.  Launches of different streams overlap, so the sums of a slot are sums of launch DURATIONS (what
 // rocprofv3 --kernel-trace --stats reports), not wall time.
-enum KSlot { KS_SYR2K = 0, KS_SYMM, KS_PANEL_QR, KS_CHAIN, KS_SB2SB, KS_SB16ST, KS_BISECT, KS_STDFORM, KS_CRAWFORD, KS_COUNT };
+enum KSlot { KS_SYR2K = 0, KS_SYMM, KS_PANEL_QR, KS_CHAIN, KS_SB2SB, KS_SB16ST, KS_BISECT, KS_STDFORM, KS_CRAWFORD, KS_OPBAND, KS_COUNT };
 void ktime_begin(int slot, hipStream_t st);
 void ktime_end(int slot, hipStream_t st);
 struct KScope {
@@ -258,6 +258,15 @@ void dipole_kslices(int n, int count_ini, int count_fin, int *chunk, int *nslice
 // d_base + d_pw[2p+1] ([count_fin][n]); d_part: npairs * nslices * count_ini * count_fin doubles when nslices > 1 (summed in slice order)
 int launch_dipole_block(int n, int count_ini, int count_fin, int npairs, const long long *d_pw, const double *d_base, double *d_part,
                         double *d_out, hipStream_t st);
+// opmat.hip: bands and pair blocks of caller-given radial operators (bspatom_operator_bands / bspatom_operator_matrix)
+// d_GB[(o*(2k-1) + (d+k-1))*nfun + i] = sum_q B_i(r_q) g_o(q) X_j(r_q) w_q, j = i + d, X = B (d_deriv[o] == 0) or B' (1); d_g[nop][nr] on the
+// quadrature grid of wf_quadrature, d_qfirst[nkp-1]: quadrature index of every knot interval's first point, -1 for zero width
+int launch_operator_bands(int nfun, int k, int ka, int nkp, int nop, int nr, const double *d_ptab, const int *d_left,
+                          const int *d_qfirst, const double *d_g, const int *d_deriv, double *d_GB, hipStream_t st);
+// launch_band_apply_block with nop coefficients per item: W[q][j][:] = (sum_o a[q*nop + o] G_o) x_j, entries of the sum formed for o
+// ascending, rows over diagonals ascending, no FMA
+int launch_band_combine_apply(int n, int k, int nop, int count, int nitems, const double *d_GB, const double *d_acoef,
+                              const long long *d_xoff, const double *d_base, double *d_W, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

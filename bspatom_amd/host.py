@@ -481,7 +481,8 @@ def radial_matrix(prob, pairs, g, n0_ini, count_ini, n0_fin, count_fin, deriv=Fa
     layout of Problem.dipole_matrix.  The sum is the assembly's own Gauss-Legendre quadrature (prob.quadrature()), so g = r,
     g = 1/r and g = 1 with deriv give what dipole_matrix gives with a = (1,0,0), (0,1,0), (0,0,1), up to rounding.  g: a
     callable of the array of points, or an array on the quadrature grid.  NumPy on the host tables of prob.wavefunctions (one
-    call per distinct channel and role): for moderate sizes; heavy users contract the tables of wavefunctions_dev on the GPU."""
+    call per distinct channel and role): for moderate sizes; heavy users call operator_matrix below, which contracts over the
+    basis on the GPU (Problem.operator_matrix)."""
     import numpy as np
     r, w = prob.quadrature()
     gw = np.asarray(g(r) if callable(g) else g, dtype=np.float64) * w
@@ -499,6 +500,37 @@ def radial_matrix(prob, pairs, g, n0_ini, count_ini, n0_fin, count_fin, deriv=Fa
     for p, (li, lf) in enumerate(pairs):
         D[p] = (ini[li] * gw) @ fin[lf].T
     return D
+
+
+def operator_matrix(prob, pairs, ops, n0_ini, count_ini, n0_fin, count_fin, a=None):
+    """D[p, i, f] = <f| sum_o a[p, o] O_o |i> for every (l_ini, l_fin) = pairs[p], i < count_ini, f < count_fin (1-based windows
+    from n0_ini, n0_fin), O_o = g_o(r) or g_o(r) d/dr: ops is a list of (g, deriv), g a callable of the array of points or an array
+    on the quadrature grid (prob.quadrature()), as in radial_matrix.  The same quadrature sums as radial_matrix, contracted over
+    the basis on the GPU in ONE Problem.operator_matrix call (bspatom_operator_matrix: the band of every operator, A x for all
+    initial vectors, the product on the matrix cores).  a: (npairs, nop), or (nop,) for every pair; None requires exactly one
+    operator and means coefficient 1."""
+    import numpy as np
+    ops = list(ops)
+    if not ops:
+        raise ValueError("ops must name at least one operator")
+    r = prob.quadrature()[0]
+    G = np.empty((len(ops), r.size))
+    deriv = np.zeros(len(ops), dtype=np.int32)
+    for o, (g, dv) in enumerate(ops):
+        gv = np.asarray(g(r) if callable(g) else g, dtype=np.float64)
+        if gv.shape != r.shape:
+            raise ValueError("operator %d: g must give one value per quadrature point (%d), got shape %s" % (o, r.size, gv.shape))
+        G[o] = gv
+        deriv[o] = 1 if dv else 0
+    if a is None:
+        if len(ops) != 1:
+            raise ValueError("a=None needs exactly one operator, got %d" % len(ops))
+        a = np.ones(1)
+    a = np.asarray(a, dtype=np.float64)
+    pairs = [(int(li), int(lf)) for li, lf in pairs]
+    if a.shape != (len(ops),) and a.shape != (len(pairs), len(ops)):
+        raise ValueError("a must have shape (%d,) or (%d, %d), got %s" % (len(ops), len(pairs), len(ops), a.shape))
+    return prob.operator_matrix(pairs, G, deriv, n0_ini, count_ini, n0_fin, count_fin, a)
 
 
 # ---- KIND_PI = 0 on several GPUs: one process per GPU, channels sharded, spectra gathered (SURVEY 8e) ---------------

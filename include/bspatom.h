@@ -149,6 +149,43 @@ int bspatom_dipole_matrix(bspatom_problem *p, int npairs, const int32_t *l_ini, 
 int bspatom_dipole_matrix_dev(bspatom_problem *p, int npairs, const int32_t *l_ini, const int32_t *l_fin, int n0_ini,
                               int count_ini, int n0_fin, int count_fin, const double *a, double *D_dev);
 
+/* Matrix elements of caller-given radial operators g(r) and g(r) d/dr (csrc/opmat.hip) -- the general case of the rij above: for
+ * KIND_PI >= 3 MATRIX_SVT assembles zAij (matrices.f90:114-139, 165-171), for every tabulated profile zIth(ibet, igl, il, jl, comp) the
+ * sums fbra * g(r_q) * fket * dr and fbra * g(r_q) * dfket * dr; FRMATINT's u_i u_j'/r^2 and u_i u_j/r^3 (TorusFunsInts.f90:286-382),
+ * multipoles r^lambda, a perturbing potential are the same thing.  g is known by its values on the Gauss-Legendre points alone:
+ * nr = what bspatom_quadrature returns, g holds nop*nr doubles, operator o at g + o*nr, indexed like the quadrature points;
+ * deriv[o] = 0: G_o(i,j) = sum_q B_i(r_q) g_o(q) B_j(r_q) w_q, deriv[o] = 1: B_j' in place of B_j.
+ *   GB[(o*(2k-1) + (d+k-1))*nfun + i] = G_o(i, i+d), 0-based i, d = -(k-1)..k-1 (the layout of bspatom_dipole_bands; zero where i+d
+ *   is outside 0..nfun-1): the FULL band, both triangles computed independently, as the reference does.  GB: nop*(2k-1)*nfun doubles.
+ * The arithmetic is fixed: one accumulator from 0.0, terms added over intervals ascending and points ascending across the intervals
+ * common to both functions (matrices.f90:71-72), each term ((fbra * g) * fket) * dr or ((fbra * g) * dfket) * dr, IEEE multiplies
+ * and adds, no FMA; fbra, fket, dfket, dr are the assembly's point table; intervals of zero width carry no g value and are skipped.
+ * So: with g = (r, 1/r, 1), deriv = (0, 0, 1) and the r of bspatom_quadrature the three bands equal bspatom_dipole_bands bit for bit
+ * (hence the reference's rij); a complex profile is two operators, Re g and Im g, whose bands are the real and imaginary parts of
+ * the reference's complex sum bit for bit (real times complex is componentwise); an operator's band does not depend on the other
+ * operators of the call.  g is not checked for finiteness: a NaN in goes to NaN out.
+ * BSPATOM_ERR_ARG: a null pointer, nop < 1, a deriv value outside {0, 1}.  The _dev variant: g_dev, GB_dev in device memory of the
+ * problem's device; deriv stays a host pointer. */
+int bspatom_operator_bands(bspatom_problem *p, int nop, const double *g, const int32_t *deriv, double *GB);
+int bspatom_operator_bands_dev(bspatom_problem *p, int nop, const double *g_dev, const int32_t *deriv, double *GB_dev);
+
+/* bspatom_dipole_matrix for those operators:
+ *   D[((size_t)p*count_ini + i)*count_fin + f] = c(l_fin[p], n0_fin+f)^T A_p c(l_ini[p], n0_ini+i),   A_p = sum_o a[p*nop + o] G_o.
+ * An entry of A_p is formed as s = a_0*G_0, then s = s + a_o*G_o for o ascending; a row of A_p x over diagonals ascending; both
+ * without FMA; the final product D = W Z^T is bspatom_dipole_matrix's (matrix cores, K slices by (nfun, count_ini, count_fin) alone,
+ * summed in slice order).  Eigenvectors, signs and normalisation, channels of the last solve, 1-based windows, repeated channels in
+ * either role and l_ini[p] == l_fin[p], the grouping under the dipole_stage_mb bound (the operator bands, nop*(2k-1)*nfun doubles,
+ * and the uploaded g are counted outside it), run-to-run bit-identical results and a pair's block independent of the other pairs and
+ * of the grouping: all as bspatom_dipole_matrix states them.  The host variant uploads g and deriv once per call.
+ * BSPATOM_ERR_ARG: a null pointer, nop < 1, a deriv value outside {0, 1}, and what bspatom_dipole_matrix names;
+ * BSPATOM_ERR_UNSUPPORTED if an inverse iteration broke down.  The _dev variant: g_dev and D_dev in device memory of the problem's
+ * device; deriv, l_ini, l_fin and a stay host pointers. */
+int bspatom_operator_matrix(bspatom_problem *p, int nop, const double *g, const int32_t *deriv, int npairs, const int32_t *l_ini,
+                            const int32_t *l_fin, int n0_ini, int count_ini, int n0_fin, int count_fin, const double *a, double *D);
+int bspatom_operator_matrix_dev(bspatom_problem *p, int nop, const double *g_dev, const int32_t *deriv, int npairs,
+                                const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini, int n0_fin, int count_fin,
+                                const double *a, double *D_dev);
+
 /* WRITE_WF (Bsp_Atom.f90:118-146): u(r_i) = sum_j c_j B_j(r_i), r_i = ra + i*(rb-ra)/npts,
  * i = 0..npts.  Returns BSPATOM_ERR_BSPLVB where the reference STOPs. r[npts+1], u[npts+1]. */
 int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u);
@@ -206,7 +243,7 @@ int bspatom_last_timing(const bspatom_problem *p, double ms[6]);
  * times and launch counts per slot since the previous call into ms[] / launches[] (cap >= the slot count, which it returns)
  * and forgets them.  Slots: 0 rank-128 update (syr2k), 1 symm, 2 panel QR, 3 the small products of the panel chain,
  * 4 sb2sb_mfma_kernel, 5 sbr_rows_kernel<8> / <16> (sb16st_kernel with BSP_SB16_ROWS=0), 6 batched bisection, 7 Cholesky + standard form,
- * 8 the band route's reduction (crawford.hip); bspatom_kernel_slot_name(i)
+ * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip); bspatom_kernel_slot_name(i)
  * names them.  Launches on different streams overlap: the sums are sums of launch durations, not wall time. */
 int bspatom_kernel_times(double *ms, int32_t *launches, int cap);
 const char *bspatom_kernel_slot_name(int slot);
