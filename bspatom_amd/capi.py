@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -80,6 +80,8 @@ def lib():
         L.bspatom_tabulate_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
         L.bspatom_wavefunctions.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.bspatom_wavefunctions_dev.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.bspatom_tdse_propagate.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp]
+        L.bspatom_tdse_propagate_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp]
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -170,6 +172,7 @@ class Problem:
     def solve(self, l0, nl):
         E = np.zeros((nl, self.nfun)); info = np.zeros(nl, dtype=np.int32)
         _chk(lib().bspatom_solve(self._h, l0, nl, _p(E), _p(info)), "bspatom_solve")
+        self.last_E, self.last_l0 = E, l0              # host.tdse_system takes the eigenvalues of its channels from here
         return E, info
 
     def solve_dev(self, l0, nl, dev_ptr):
@@ -362,6 +365,49 @@ class Problem:
         _chk(lib().bspatom_wavefunctions_dev(self._h, l0, nl, n0, count, npts, _p(r), C.c_void_p(U_ptr),
                                              C.c_void_p(dU_ptr) if dU_ptr else None), "bspatom_wavefunctions_dev")
         return npts
+
+    @staticmethod
+    def _tdse_pairs(pairs):
+        pr = np.asarray(list(pairs), dtype=np.int32).reshape(-1, 2)
+        return np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+
+    def tdse_propagate(self, E, pairs, D, a0, field, dt, snap_every=0):
+        """nsteps fixed Runge-Kutta steps dt of i da/dt = (E + f(t) D) a in the eigenstate basis (bspatom_tdse_propagate) for nscan
+        wave packets at once.  E: (nch, count); pairs: [(ci, cf)] channel positions; D: (npairs, count, count), D[p, i, f] between
+        state i of channel ci and state f of cf (dipole_matrix's layout); a0: complex (nscan, nch, count) or (nch, count);
+        field: complex (nsteps, 6, nscan), f_q at the stage times (host.field_table).  Returns (a, err), err (nscan,) the largest
+        embedded error estimate of a step, or (a, err, snaps) with snaps (nsteps // snap_every, nscan, nch, count)."""
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        nch, count = E.shape
+        ci, cf = self._tdse_pairs(pairs)
+        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
+        a = np.array(a0, dtype=np.complex128, order="C")
+        one = a.ndim == 2
+        a = np.ascontiguousarray(a.reshape(-1, nch, count))
+        nscan = a.shape[0]
+        field = np.ascontiguousarray(field, dtype=np.complex128)
+        nsteps = field.shape[0] if field.ndim == 3 else 0
+        assert field.shape == (nsteps, 6, nscan), (field.shape, nscan)
+        err = np.zeros(nscan)
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
+        _chk(lib().bspatom_tdse_propagate(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
+                                          _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
+                                          _p(snaps), _p(err)), "bspatom_tdse_propagate")
+        if one:
+            a = a[0]
+        return (a, err) if snaps is None else (a, err, snaps)
+
+    def tdse_propagate_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, snap_every=0, snap_ptr=None):
+        """tdse_propagate with E (nch * count doubles at E_ptr), D, the field table (nsteps * 6 * nscan complex) and the amplitudes
+        (nscan * nch * count complex at a_ptr, advanced in place) in device memory of this problem's device, e.g. torch tensors'
+        data_ptr(); snapshots, if asked for, at snap_ptr.  pairs is a host list.  Returns err (nscan,) when the result is there."""
+        ci, cf = self._tdse_pairs(pairs)
+        err = np.zeros(nscan)
+        _chk(lib().bspatom_tdse_propagate_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
+                                              _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
+                                              float(dt), C.c_void_p(field_ptr), C.c_void_p(a_ptr), snap_every,
+                                              C.c_void_p(snap_ptr) if snap_ptr else None, _p(err)), "bspatom_tdse_propagate_dev")
+        return err
 
     def early_vector_state(self):
         """0: the last solve computed no early vector; 1: computed and kept; -1: computed, failed its check, dropped (include/bspatom.h)."""

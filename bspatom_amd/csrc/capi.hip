@@ -69,6 +69,7 @@ const OptName OPT_TABLE[] = {
     {"fused_probe", "BSP_FUSED_PROBE", &Options::fused_probe},
     {"dipole_stage_mb", "BSP_DIPOLE_STAGE_MB", &Options::dipole_stage_mb},
     {"wf_stage_mb", "BSP_WF_STAGE_MB", &Options::wf_stage_mb},
+    {"tdse_stage_mb", "BSP_TDSE_STAGE_MB", &Options::tdse_stage_mb},
 };
 }  // namespace
 
@@ -104,7 +105,8 @@ const char *const KSLOT_NAMES[KS_COUNT] = {"gemm2_kernel<128,128,MODE 1> (rank-1
                                           "sb2sb_mfma_kernel (band 64 -> 16)", "sbr_rows_kernel<8> / <16> / sb16st_kernel (one-column chase to tridiagonal)", "bisect3_kernel",
                                           "band_cholesky_kernel + std_form_kernel",
                                           "crawford_item_kernel and its set-up kernels (band route: pencil -> band 15)",
-                                          "operator_band_kernel (bands of caller-given g(r), g(r) d/dr)"};
+                                          "operator_band_kernel (bands of caller-given g(r), g(r) d/dr)",
+                                          "tdse_stage_kernel (one Runge-Kutta stage of bspatom_tdse_propagate)"};
 }  // namespace
 void ktime_begin(int slot, hipStream_t st)
 {

@@ -1,0 +1,146 @@
+// capi_tdse.hip -- bspatom_tdse_propagate / _dev (include/bspatom.h): the argument checks, the per-channel entry lists, the
+// working buffers and the step loop of tdse.hip.  The problem handle gives the device and the stream; nothing of a solve is read.
+#include <cmath>
+#include "capi_internal.h"
+
+using namespace bsp;
+
+namespace {
+constexpr size_t TDSE_STAGE_BYTES = (size_t)256 << 20;
+size_t tdse_stage_bytes() { return opts().tdse_stage_mb > 0 ? (size_t)opts().tdse_stage_mb << 20 : TDSE_STAGE_BYTES; }
+
+bool args_ok(const bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf,
+             const double *D, int nscan, int nsteps, double dt, const double *field, const double *a, int snap_every, const double *snap)
+{
+    if (!p || !E || !a || nch < 1 || count < 1 || nscan < 1 || nsteps < 0 || npairs < 0 || snap_every < 0) return false;
+    if (nsteps > 0 && !field) return false;
+    if (npairs > 0 && (!ci || !cf || !D)) return false;
+    if (snap && snap_every == 0) return false;
+    if (!std::isfinite(dt)) return false;
+    for (int q = 0; q < npairs; ++q)
+        if (ci[q] < 0 || ci[q] >= nch || cf[q] < 0 || cf[q] >= nch || ci[q] == cf[q]) return false;
+    return true;
+}
+
+// everything of a call that lives on the device besides the caller's arrays
+struct Plan {
+    TdseDims d;
+    DevArray<int> cptr, ent;
+    DevArray<double> aw, K;
+    DevArray<unsigned long long> err2;
+    size_t rows = 0;
+    int prepare(bspatom_problem *p, int nch, int count, int nscan, int npairs, const int32_t *ci, const int32_t *cf)
+    {
+        d = {nch, count, nscan, tdse_columns(nscan)};
+        rows = (size_t)nch * count;
+        // channel c's entries in ascending p: (p, cf[p], 1) where ci[p] = c, (p, ci[p], 0) where cf[p] = c
+        std::vector<int> cp(nch + 1, 0), en((size_t)6 * npairs + 3, 0);
+        for (int q = 0; q < npairs; ++q) { ++cp[ci[q] + 1]; ++cp[cf[q] + 1]; }
+        for (int c = 0; c < nch; ++c) cp[c + 1] += cp[c];
+        std::vector<int> at(cp.begin(), cp.end() - 1);
+        for (int q = 0; q < npairs; ++q) {
+            int *e = &en[(size_t)3 * at[ci[q]]++];
+            e[0] = q; e[1] = cf[q]; e[2] = 1;
+            e = &en[(size_t)3 * at[cf[q]]++];
+            e[0] = q; e[1] = ci[q]; e[2] = 0;
+        }
+        int rc;
+        if ((rc = cptr.put(cp.data(), cp.size())) || (rc = ent.put(en.data(), en.size())) || (rc = aw.alloc(rows * d.NC)) ||
+            (rc = K.alloc(6 * rows * d.NC)) || (rc = err2.alloc(nscan)))
+            return rc;
+        return HIP_RC(hipMemsetAsync(err2.p, 0, (size_t)nscan * sizeof(unsigned long long), p->st));
+    }
+    TdseBufs bufs(const double *d_E, const double *d_D) const { return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p}; }
+    // steps n0 .. n1-1; d_field: the table from step n0 on; d_snap (or null): where snapshot number s0 (from 0) goes, the later ones behind it
+    int run(bspatom_problem *p, const TdseBufs &w, int n0, int n1, double dt, const double *d_field, int snap_every, double *d_snap, int s0)
+    {
+        for (int n = n0; n < n1; ++n) {
+            double *sn = nullptr;
+            if (d_snap && (n + 1) % snap_every == 0) sn = d_snap + ((size_t)((n + 1) / snap_every - 1 - s0)) * rows * d.nscan * 2;
+            const int rc = launch_tdse_step(d, w, d_field + (size_t)(n - n0) * 12 * d.nscan, dt, sn, p->st);
+            if (rc) return rc;
+        }
+        return BSP_OK;
+    }
+    // after the stream has drained: err[q] = |dt| sqrt(max |sum_s (d_s - b_s) k_s|^2)
+    int errors(double dt, double *err) const
+    {
+        if (!err) return BSP_OK;
+        std::vector<unsigned long long> e2(d.nscan);
+        const int rc = err2.get(e2.data(), e2.size());
+        if (rc) return rc;
+        for (int q = 0; q < d.nscan; ++q) {
+            double m2;
+            memcpy(&m2, &e2[q], sizeof m2);
+            err[q] = std::fabs(dt) * std::sqrt(m2);
+        }
+        return BSP_OK;
+    }
+};
+}  // namespace
+
+extern "C" int bspatom_tdse_propagate_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                                          const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt,
+                                          const double *field_dev, double *a_dev, int snap_every, double *snap_dev, double *err)
+{
+    if (!args_ok(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev)) return BSP_ERR_ARG;
+    if (nsteps == 0) {
+        if (err) for (int q = 0; q < nscan; ++q) err[q] = 0.0;
+        return BSP_OK;
+    }
+    BSP_HIP(hipSetDevice(p->device));
+    Plan pl;
+    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf);
+    if (!rc) rc = launch_tdse_pack(pl.d, a_dev, pl.aw.p, p->st);
+    if (!rc) rc = pl.run(p, pl.bufs(E_dev, D_dev), 0, nsteps, dt, field_dev, snap_every, snap_dev, 0);
+    if (!rc) rc = launch_tdse_unpack(pl.d, pl.aw.p, a_dev, p->st);
+    if ((rc = drain(p, rc))) return rc;
+    return pl.errors(dt, err);
+}
+
+extern "C" int bspatom_tdse_propagate(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
+                                      const int32_t *cf, const double *D, int nscan, int nsteps, double dt, const double *field,
+                                      double *a, int snap_every, double *snap, double *err)
+{
+    if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap)) return BSP_ERR_ARG;
+    if (nsteps == 0) {
+        if (err) for (int q = 0; q < nscan; ++q) err[q] = 0.0;
+        return BSP_OK;
+    }
+    BSP_HIP(hipSetDevice(p->device));
+    const size_t rows = (size_t)nch * count, adbl = rows * nscan * 2, fdbl = (size_t)12 * nscan;     // doubles of a snapshot, of a step's field
+    // steps per group: the field of g steps and the (at most g / snap_every + 1) snapshots among them within the bound, one step at least
+    const bool snapping = snap && snap_every > 0;
+    const size_t bound = tdse_stage_bytes() / sizeof(double);
+    auto snaps_of = [&](size_t g) { return snapping ? g / snap_every + 1 : (size_t)0; };
+    size_t g = bound / fdbl;
+    if (g > (size_t)nsteps) g = nsteps;
+    while (g > 1 && g * fdbl + snaps_of(g) * adbl > bound) {
+        const size_t over = g * fdbl + snaps_of(g) * adbl - bound;
+        const size_t dec = over / (fdbl + adbl) > 1 ? over / (fdbl + adbl) : 1;
+        g = g > dec ? g - dec : 1;
+    }
+    if (g < 1) g = 1;
+    Plan pl;
+    DevArray<double> dE, dD, da, dfield, dsnap;
+    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf);
+    if (!rc) rc = dE.put(E, rows);
+    if (!rc && npairs > 0) rc = dD.put(D, (size_t)npairs * count * count);
+    if (!rc) rc = da.put(a, adbl);
+    if (!rc) rc = dfield.alloc(g * fdbl);
+    if (!rc && snapping) rc = dsnap.alloc(snaps_of(g) * adbl);
+    if (!rc) rc = launch_tdse_pack(pl.d, da.p, pl.aw.p, p->st);
+    const TdseBufs w = pl.bufs(dE.p, dD.p);
+    for (int n0 = 0; !rc && n0 < nsteps; n0 += (int)g) {
+        const int n1 = n0 + (int)g < nsteps ? n0 + (int)g : nsteps;
+        rc = HIP_RC(hipMemcpyAsync(dfield.p, field + (size_t)n0 * fdbl, (size_t)(n1 - n0) * fdbl * sizeof(double), hipMemcpyHostToDevice, p->st));
+        const int s0 = snapping ? n0 / snap_every : 0, s1 = snapping ? n1 / snap_every : 0;
+        if (!rc) rc = pl.run(p, w, n0, n1, dt, dfield.p, snap_every, snapping ? dsnap.p : nullptr, s0);
+        if (!rc && s1 > s0)
+            rc = HIP_RC(hipMemcpyAsync(snap + (size_t)s0 * adbl, dsnap.p, (size_t)(s1 - s0) * adbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc) rc = launch_tdse_unpack(pl.d, pl.aw.p, da.p, p->st);
+    if (!rc) rc = HIP_RC(hipMemcpyAsync(a, da.p, adbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    if ((rc = drain(p, rc))) return rc;
+    return pl.errors(dt, err);
+}

@@ -92,6 +92,8 @@ struct Options {
                                  // values force several groups (the results do not depend on the grouping: the test's hook)
     int wf_stage_mb = 0;         // BSP_WF_STAGE_MB: > 0 = device staging of bspatom_tabulate / bspatom_wavefunctions (U and dU of one group of vectors,
                                  // one group's eigenvector block) in MB (0 = 256 MiB); small values force several groups (the test's hook)
+    int tdse_stage_mb = 0;       // BSP_TDSE_STAGE_MB: > 0 = device staging of bspatom_tdse_propagate's host variant (the field table and the snapshots of one
+                                 // group of steps) in MB (0 = 256 MiB); small values force several groups (the test's hook)
     int ktime = 0;               // 1: HIP events around every launch of the kernels in KSlot (bspatom_kernel_times; bench.py's
                                  // per-kernel roofline entries are measured with it in one extra, untimed step)
 };
@@ -106,7 +108,7 @@ void process_device_latch(int device);
 // Two events per launch, recorded on the launch's own stream; bspatom_kernel_times() sums the elapsed times per slot after
 // the device has drained.  Launches of different streams overlap, so the sums of a slot are sums of launch DURATIONS (what
 // rocprofv3 --kernel-trace --stats reports), not wall time.
-enum KSlot { KS_SYR2K = 0, KS_SYMM, KS_PANEL_QR, KS_CHAIN, KS_SB2SB, KS_SB16ST, KS_BISECT, KS_STDFORM, KS_CRAWFORD, KS_OPBAND, KS_COUNT };
+enum KSlot { KS_SYR2K = 0, KS_SYMM, KS_PANEL_QR, KS_CHAIN, KS_SB2SB, KS_SB16ST, KS_BISECT, KS_STDFORM, KS_CRAWFORD, KS_OPBAND, KS_TDSE, KS_COUNT };
 void ktime_begin(int slot, hipStream_t st);
 void ktime_end(int slot, hipStream_t st);
 struct KScope {
@@ -281,6 +283,22 @@ int launch_basis_gather(int k, int npts, const int *d_rows, const double *d_ptab
 // d_U[v * npts + ip] = sum_j d_Z[v * nfun + j] B_j(r_ip), d_dU likewise with B' (null: values only)
 int launch_tabulate(int k, int nfun, int npts, int nvec, const double *d_tab, const int *d_tleft, const double *d_Z, double *d_U,
                     double *d_dU, hipStream_t st);
+// tdse.hip: the TDSE in the eigenstate basis (bspatom_tdse_propagate).  Working layout of the amplitudes: [nch][count][NC] real,
+// column 2q / 2q + 1 = Re / Im of scan q, NC = tdse_columns(nscan) (2 nscan rounded up to 16, the rest zero)
+struct TdseDims { int nch, count, nscan, NC; };
+struct TdseBufs {
+    const int *cptr, *ent;       // entries cptr[c] .. cptr[c+1]-1 of channel c, ascending p: ent[3e] = p, [3e+1] = the other channel, [3e+2] = 1 if c = ci[p]
+    const double *E, *D;         // [nch][count]; [npairs][count][count]
+    double *a, *K;               // working amplitudes; the six k_s, each nch * count * NC doubles
+    unsigned long long *err2;    // [nscan] bit patterns of max |sum_s (d_s - b_s) k_s|^2, zeroed by the caller
+};
+extern const double TDSE_A[6][5], TDSE_D[6], TDSE_B[6];
+int tdse_columns(int nscan);
+// one step: six stage launches and the step kernel; d_field: the 6 * nscan complex values of this step; d_snap: null, or where the
+// new amplitudes go in the caller's layout [nscan][nch][count] complex
+int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, hipStream_t st);
+int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st);
+int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st);
 
 // capi.hip: enqueue Cholesky -> standard form -> sy2sb -> sb2st -> bisection on `st` for nl channels
 // whose upper bands are already in d_SB / d_HB.  ev (optional): 5 events recorded at the stage

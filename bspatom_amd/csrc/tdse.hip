@@ -1,0 +1,333 @@
+// tdse.hip -- the TDSE in the basis of the field-free eigenstates (bspatom_tdse_propagate):
+//   i da_c/dt = E_c .* a_c + sum_{p: cf[p] = c} f_q(t) D_p^T a_{ci[p]} + sum_{p: ci[p] = c} conj(f_q(t)) D_p a_{cf[p]}
+// for nscan wave packets at once, fixed steps of the embedded six-stage 4(5) Runge-Kutta pair of the reference (MOD_RK_PARAMS,
+// Modules.f90:559-586; the state arrays zf, zdfdt, zVtij at :238-246).  Seven launches per step: one stage kernel per stage, which
+// forms its operand y_s = a + dt sum_j A_sj k_j while it loads it and leaves k_s = -i H(t_n + c_s dt) y_s, then one kernel for the
+// step, the error estimate and the snapshot.
+//
+// Working layout: the amplitudes of channel c are a real matrix [count][NC], column 2q = Re, 2q + 1 = Im of scan q, NC = 2 nscan
+// rounded up to 16 (zero columns); a, k_0 .. k_5 are [nch][count][NC] each.  A coupling block times these columns is a real
+// product on v_mfma_f64_16x16x4_f64; the field, which differs per column, enters in the epilogue.
+#include "common.h"
+#include "mfma_tile.h"
+
+namespace bsp {
+
+// ---- the tableau (MOD_RK_PARAMS, Modules.f90:568-584) ----------------------------------------------------------------------
+// a21 .. a65 (:568-572), c1 .. c6 (:577-578: 0, 2/9, 1/3, 3/4, 1, 5/6 -- the row sums; the field table is laid out on them),
+// the 5th-order weights d1 .. d6 (:580-581) that advance the solution, the 4th-order b1 .. b5 (:574-575, b6 = 0) of the estimate
+const double TDSE_A[6][5] = {{0.0, 0.0, 0.0, 0.0, 0.0},
+                             {2.0 / 9.0, 0.0, 0.0, 0.0, 0.0},
+                             {1.0 / 12.0, 1.0 / 4.0, 0.0, 0.0, 0.0},
+                             {69.0 / 128.0, -243.0 / 128.0, 135.0 / 64.0, 0.0, 0.0},
+                             {-17.0 / 12.0, 27.0 / 4.0, -27.0 / 5.0, 16.0 / 15.0, 0.0},
+                             {65.0 / 432.0, -5.0 / 16.0, 13.0 / 16.0, 4.0 / 27.0, 5.0 / 144.0}};
+const double TDSE_D[6] = {47.0 / 450.0, 0.0, 12.0 / 25.0, 32.0 / 225.0, 1.0 / 30.0, 6.0 / 25.0};
+const double TDSE_B[6] = {1.0 / 9.0, 0.0, 9.0 / 20.0, 16.0 / 45.0, 1.0 / 12.0, 0.0};
+
+constexpr int TBK = 16, TBM = 64, TLDA = TBM + 16;
+
+struct StageCoef { double w[5]; };          // A_s0 .. A_s,s-1
+
+// y_s of one element from a and the k_j of the step, in one fixed order (the staged operand and the epilogue's E .* y agree bit for bit)
+template <int S>
+__device__ __forceinline__ double form_y(const double (&v)[S + 1], const StageCoef &cf, double dt)
+{
+    if constexpr (S == 0) {
+        return v[0];
+    } else {
+        double s = cf.w[0] * v[1];
+#pragma unroll
+        for (int j = 1; j < S; ++j) s = fma(cf.w[j], v[j + 1], s);
+        return fma(dt, s, v[0]);
+    }
+}
+
+template <int S>
+__device__ __forceinline__ void load_y(double (&v)[S + 1], const double *__restrict__ a, const double *__restrict__ K, size_t kstride,
+                                       size_t idx, bool ok)
+{
+    // unconditional loads from a clamped address, the values selected afterwards (dipole.hip)
+    const size_t at = ok ? idx : 0;
+    const double x = a[at];
+    v[0] = ok ? x : 0.0;
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+        const double kx = K[(size_t)j * kstride + at];
+        v[j + 1] = ok ? kx : 0.0;
+    }
+}
+
+// One workgroup = 64 states of one channel x 16 TN columns; wave w owns rows 16 w .. 16 w + 15.  The channel's entries (its pairs
+// in ascending p; ent[3e] = p, [3e+1] = the other channel, [3e+2] = 1 where the channel is ci[p]) are walked in order, every block
+// along K ascending in steps of 16: nothing of the batch (nscan, nch, the list's length) enters the order of the sums of an element.
+//   entry with cf[p] = c:  accT += D_p^T y_ci   -- the A tile is contiguous along M in memory (D_p[i][f], f = output row)
+//   entry with ci[p] = c:  accN += D_p y_cf     -- contiguous along K; staged through the column permutation lds_swz
+// Epilogue per scan: h = E y + f accT + conj(f) accN, k_s = -i h.
+template <int S, int TN>
+__global__ __launch_bounds__(256) void tdse_stage_kernel(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
+                                                        const int *__restrict__ ent, const double *__restrict__ E,
+                                                        const double *__restrict__ D, const double *__restrict__ a,
+                                                        double *__restrict__ K, size_t kstride, const double *__restrict__ fld,
+                                                        StageCoef cf, double dt)
+{
+    constexpr int NB = 16 * TN, TLDB = NB + 16, BEL = TBK * NB / 256;        // B-tile elements per thread: 1 or 2
+    __shared__ double As[TBK * TLDA];
+    __shared__ double Bs[TBK * TLDB];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int b = blockIdx.x;
+    const int jn = b % tn; b /= tn;
+    const int im = b % tm;
+    const int c = b / tm;
+    const int m0 = im * TBM, n0 = jn * NB;
+    const int e0 = cptr[c], e1 = cptr[c + 1];
+    const int ksteps = (count + TBK - 1) / TBK;
+    const size_t blk = (size_t)count * count;
+
+    double4_t accT[1][TN], accN[1][TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        accT[0][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+        accN[0][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    }
+
+    double ra[4], rb[BEL][S + 1];
+    // the loads of iteration it = (entry, k-step): A tile 64 x 16 of D_p (either orientation), B tile 16 x NB of y of the other channel
+    auto load = [&](int it) {
+        const int e = e0 + it / ksteps, k0 = (it % ksteps) * TBK;
+        const int p = ent[3 * e], oc = ent[3 * e + 1], nrm = ent[3 * e + 2];
+        const double *Dp = D + (size_t)p * blk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int idx = tid + r * 256;
+            // nrm: A(m, k) = D_p[m][k], consecutive threads along k; else A(m, k) = D_p[k][m], consecutive threads along m
+            const int mm = nrm ? idx / TBK : idx % TBM, kk = nrm ? idx % TBK : idx / TBM;
+            const int gm = m0 + mm, gk = k0 + kk;
+            const bool ok = gm < count && gk < count;
+            const double v = Dp[ok ? (nrm ? (size_t)gm * count + gk : (size_t)gk * count + gm) : 0];
+            ra[r] = ok ? v : 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < BEL; ++r) {
+            const int idx = tid + r * 256;
+            const int kk = idx / NB, col = n0 + idx % NB, gk = k0 + kk;
+            load_y<S>(rb[r], a, K, kstride, ((size_t)oc * count + gk) * NC + col, gk < count && col < NC);
+        }
+        return nrm;
+    };
+    auto store = [&](int nrm) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int idx = tid + r * 256;
+            const int mm = nrm ? idx / TBK : idx % TBM, kk = nrm ? idx % TBK : idx / TBM;
+            As[kk * TLDA + (mm ^ lds_swz(kk))] = ra[r];
+        }
+#pragma unroll
+        for (int r = 0; r < BEL; ++r) {
+            const int idx = tid + r * 256;
+            const int kk = idx / NB, cc = idx % NB;
+            Bs[kk * TLDB + (cc ^ lds_swz(kk))] = form_y<S>(rb[r], cf, dt);
+        }
+    };
+
+    const int nit = (e1 - e0) * ksteps;
+    int nrm = 0;
+    if (nit > 0) nrm = load(0);
+    for (int it = 0; it < nit; ++it) {
+        store(nrm);
+        __syncthreads();
+        const int cur = nrm;
+        if (it + 1 < nit) nrm = load(it + 1);
+        if (cur) {
+#pragma unroll
+            for (int k4 = 0; k4 < TBK / 4; ++k4) {
+                const int kr = k4 * 4 + (lane >> 4);
+                mfma_step<1, TN>(&As[kr * TLDA + wave * 16], &Bs[kr * TLDB], lane, kr, accN);
+            }
+        } else {
+#pragma unroll
+            for (int k4 = 0; k4 < TBK / 4; ++k4) {
+                const int kr = k4 * 4 + (lane >> 4);
+                mfma_step<1, TN>(&As[kr * TLDA + wave * 16], &Bs[kr * TLDB], lane, kr, accT);
+            }
+        }
+        __syncthreads();
+    }
+
+    // epilogue: this lane holds column col (Re of scan col / 2 if even, Im if odd) of rows (lane >> 4) + 4 r; the other component of the
+    // same scan is in lane ^ 1.  Every lane forms its own component of h; k_s = -i h = (Im h, -Re h) is then the neighbour's value.
+    double *Ks = K + (size_t)S * kstride;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int col = n0 + j * 16 + (lane & 15);
+        const int q = col >> 1, odd = col & 1;
+        const bool cok = col < NC, fok = q < nscan;
+        const double fre = fld[fok ? 2 * q : 0], fim = fld[fok ? 2 * q + 1 : 0];
+        const double fr = fok ? fre : 0.0, fi = fok ? (odd ? fim : -fim) : 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int gm = m0 + wave * 16 + (lane >> 4) + 4 * r;
+            const bool ok = cok && gm < count;
+            const size_t idx = ((size_t)c * count + gm) * NC + col;
+            double v[S + 1];
+            load_y<S>(v, a, K, kstride, idx, ok);
+            const double y = form_y<S>(v, cf, dt);
+            const double en = E[ok ? (size_t)c * count + gm : 0];
+            const double u = accT[0][j][r], w = accN[0][j][r];
+            const double up = __shfl_xor(u, 1), wp = __shfl_xor(w, 1);
+            // even lane: Re h = E y_re + (f_re u_re - f_im u_im) + (f_re w_re + f_im w_im)
+            // odd lane:  Im h = E y_im + (f_re u_im + f_im u_re) + (f_re w_im - f_im w_re)
+            double h = en * y;
+            h = fma(fr, u, h);
+            h = fma(fi, up, h);
+            h = fma(fr, w, h);
+            h = fma(-fi, wp, h);
+            const double hp = __shfl_xor(h, 1);
+            if (ok) Ks[idx] = odd ? -hp : hp;
+        }
+    }
+}
+
+// ---- the step: a += dt sum_s d_s k_s, the error estimate, the snapshot ------------------------------------------------------
+// One thread per (state row, scan): 32 rows x 8 scans per workgroup, the 16 real columns of 8 scans contiguous.  err2[q] (bit
+// pattern of a non-negative double) takes the maximum of |sum_s (d_s - b_s) k_s|^2 with an integer atomic maximum: order-independent.
+// snap (or null): the new amplitudes in the caller's layout [nscan][nch * count] complex.
+struct StepCoef { double d[6], e[6]; };
+
+__global__ __launch_bounds__(256) void tdse_step_kernel(long long rows, int NC, int nscan, double *__restrict__ a,
+                                                       const double *__restrict__ K, size_t kstride, StepCoef sc, double dt,
+                                                       unsigned long long *__restrict__ err2, double *__restrict__ snap)
+{
+    __shared__ double smax[4][8];
+    const int tid = threadIdx.x, ql = tid & 7, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.y * 8 + ql;
+    const long long row = (long long)blockIdx.x * 32 + (tid >> 3);
+    const bool ok = row < rows && 2 * q < NC;
+    double m2 = 0.0;
+    if (ok) {
+        const size_t idx = (size_t)row * NC + 2 * q;
+        double s[2], e[2];
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri) {
+            const double k0 = K[idx + ri];
+            s[ri] = sc.d[0] * k0;
+            e[ri] = sc.e[0] * k0;
+#pragma unroll
+            for (int j = 2; j < 6; ++j) {               // the second stage has weight 0 in both formulas
+                const double kj = K[(size_t)j * kstride + idx + ri];
+                s[ri] = fma(sc.d[j], kj, s[ri]);
+                e[ri] = fma(sc.e[j], kj, e[ri]);
+            }
+            s[ri] = fma(dt, s[ri], a[idx + ri]);
+            a[idx + ri] = s[ri];
+        }
+        m2 = fma(e[0], e[0], e[1] * e[1]);
+        if (snap && q < nscan) {
+            double *o = snap + ((size_t)q * rows + row) * 2;
+            o[0] = s[0];
+            o[1] = s[1];
+        }
+    }
+    // maximum over the 8 lanes of a wave with the same scan, then over the 4 waves.  A NaN never wins a comparison here.
+#pragma unroll
+    for (int sh = 8; sh < 64; sh <<= 1) {
+        const double o = __shfl_xor(m2, sh);
+        m2 = o > m2 ? o : m2;
+    }
+    if (lane < 8) smax[wave][lane] = m2;
+    __syncthreads();
+    if (tid < 8) {
+        double m = smax[0][tid];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) m = smax[w][tid] > m ? smax[w][tid] : m;
+        const int qq = blockIdx.y * 8 + tid;
+        if (qq < nscan && m > 0.0) atomicMax(&err2[qq], (unsigned long long)__double_as_longlong(m));
+    }
+}
+
+// caller's layout a[((q nch + c) count + n) 2 + ri]  <->  working layout; pad columns are written as zeros
+__global__ __launch_bounds__(256) void tdse_pack_kernel(long long rows, int NC, int nscan, const double *__restrict__ src, double *__restrict__ dst)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * NC) return;
+    const long long row = t / NC;
+    const int col = (int)(t - row * NC), q = col >> 1;
+    dst[t] = q < nscan ? src[((size_t)q * rows + row) * 2 + (col & 1)] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void tdse_unpack_kernel(long long rows, int NC, int nscan, const double *__restrict__ src, double *__restrict__ dst)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * 2 * nscan) return;
+    const long long qr = t >> 1;
+    const int ri = (int)(t & 1);
+    const long long q = qr / rows, row = qr - q * rows;
+    dst[t] = src[(size_t)row * NC + 2 * q + ri];
+}
+
+// ---- launchers ---------------------------------------------------------------------------------------------------------------
+int tdse_columns(int nscan) { return (2 * nscan + 15) / 16 * 16; }
+
+template <int S>
+static int launch_stage_s(const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st)
+{
+    StageCoef cf;
+    for (int j = 0; j < 5; ++j) cf.w[j] = TDSE_A[S][j];
+    const int tm = (d.count + TBM - 1) / TBM;
+    const size_t ks = (size_t)d.nch * d.count * d.NC;
+    KScope ks_(KS_TDSE, st);
+    if (d.NC == 16) {
+        const long long grid = (long long)d.nch * tm;
+        if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL((tdse_stage_kernel<S, 1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, 1, w.cptr, w.ent,
+                           w.E, w.D, w.a, w.K, ks, fld, cf, dt);
+    } else {
+        const int tn = (d.NC + 31) / 32;
+        const long long grid = (long long)d.nch * tm * tn;
+        if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL((tdse_stage_kernel<S, 2>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent,
+                           w.E, w.D, w.a, w.K, ks, fld, cf, dt);
+    }
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, hipStream_t st)
+{
+    const size_t fs = (size_t)2 * d.nscan;
+    int rc;
+    if ((rc = launch_stage_s<0>(d, w, d_field, dt, st)) || (rc = launch_stage_s<1>(d, w, d_field + fs, dt, st)) ||
+        (rc = launch_stage_s<2>(d, w, d_field + 2 * fs, dt, st)) || (rc = launch_stage_s<3>(d, w, d_field + 3 * fs, dt, st)) ||
+        (rc = launch_stage_s<4>(d, w, d_field + 4 * fs, dt, st)) || (rc = launch_stage_s<5>(d, w, d_field + 5 * fs, dt, st)))
+        return rc;
+    StepCoef sc;
+    for (int j = 0; j < 6; ++j) { sc.d[j] = TDSE_D[j]; sc.e[j] = TDSE_D[j] - TDSE_B[j]; }
+    const long long rows = (long long)d.nch * d.count;
+    const long long gx = (rows + 31) / 32;
+    const int gy = (d.NC / 2 + 7) / 8;
+    if (gx > 0x7fffffffLL || gy > 65535) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_step_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
+                       (size_t)rows * d.NC, sc, dt, w.err2, d_snap);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st)
+{
+    const long long rows = (long long)d.nch * d.count, total = rows * d.NC, blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, rows, d.NC, d.nscan, d_user, d_work);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st)
+{
+    const long long rows = (long long)d.nch * d.count, total = rows * 2 * d.nscan, blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_unpack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, rows, d.NC, d.nscan, d_work, d_user);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+}  // namespace bsp

@@ -6,6 +6,7 @@ Eigenvec_All.dat.  All arithmetic on matrices happens in libbspatom on the GPU; 
 dispatches, does the reference's integer bookkeeping on the spectra and formats."""
 import math
 import os
+from fractions import Fraction as _F
 from . import capi
 from .namelist import read_namelists
 
@@ -415,16 +416,10 @@ def read_matelem_all(path, nfields=1):
     return n1_max, z
 
 
-def dipole_matelem(prob, channels, n1_max, kind_pi=1, mph=0):
-    """Coupling matrix of the one-photon dipole operator between the states (l, n = 1..n1_max) of `channels` (a list of
-    (l, m)), laid out as TRANS_AMP lays out zT_fi for the beam cases: row / column index = il * n1_max + n (il = position
-    in `channels`), one component.  <n l m| c1 r |n' l' m'> in the length gauge (KIND_PI = 1) or the velocity-gauge
-    operator (KIND_PI = 2) with the angular factors of PhotoIon.f90:66-83; zero unless l' = l +- 1.  The reference
-    writes MatElem_All.dat only for its Gaussian / LG-beam branches (angular integrals outside SURVEY 8); this fills
-    the same file with the plane-wave couplings so that READ_COUP consumers can run on the GPU solver's output."""
-    import numpy as np
-    nlm = len(channels)
-    z = np.zeros((nlm * n1_max, nlm * n1_max, 1), dtype=np.complex128)
+def dipole_blocks(channels, kind_pi=1, mph=0):
+    """The nonzero blocks of the one-photon dipole coupling between `channels` (a list of (l, m)), upper triangle: a list of
+    (a_, b_, l0, lf, c0, coef) with a_ <= b_ the positions of the bra and the ket channel, l0 = l of the ket (initial), lf = l of
+    the bra (final), and the reference's angular factors (PhotoIon.f90:66-83): the block is c0 * <lf| coef . (r, 1/r, d/dr) |l0>."""
     blocks = []                                    # (a_, b_, initial channel, final channel, c0, coefficients)
     for a_, (li, mi) in enumerate(channels):
         for b_, (lj, mj) in enumerate(channels):
@@ -442,6 +437,20 @@ def dipole_matelem(prob, channels, n1_max, kind_pi=1, mph=0):
                 c1, c2 = (float(l0 + 1), -1.0) if lf == l0 + 1 else (float(l0), 1.0)
                 coef = [0.0, c1, c2]
             blocks.append((a_, b_, l0, lf, c0, coef))
+    return blocks
+
+
+def dipole_matelem(prob, channels, n1_max, kind_pi=1, mph=0):
+    """Coupling matrix of the one-photon dipole operator between the states (l, n = 1..n1_max) of `channels` (a list of
+    (l, m)), laid out as TRANS_AMP lays out zT_fi for the beam cases: row / column index = il * n1_max + n (il = position
+    in `channels`), one component.  <n l m| c1 r |n' l' m'> in the length gauge (KIND_PI = 1) or the velocity-gauge
+    operator (KIND_PI = 2) with the angular factors of PhotoIon.f90:66-83; zero unless l' = l +- 1.  The reference
+    writes MatElem_All.dat only for its Gaussian / LG-beam branches (angular integrals outside SURVEY 8); this fills
+    the same file with the plane-wave couplings so that READ_COUP consumers can run on the GPU solver's output."""
+    import numpy as np
+    nlm = len(channels)
+    z = np.zeros((nlm * n1_max, nlm * n1_max, 1), dtype=np.complex128)
+    blocks = dipole_blocks(channels, kind_pi, mph)
     if hasattr(prob, "dipole_matrix") and blocks:
         # every block of the file in one call (bspatom_dipole_matrix): D[p][nj - 1][n - 1], ket = initial, bra = final
         D = prob.dipole_matrix([(l0, lf) for _, _, l0, lf, _, _ in blocks], 1, n1_max, 1, n1_max,
@@ -453,6 +462,84 @@ def dipole_matelem(prob, channels, n1_max, kind_pi=1, mph=0):
         for nj in range(1, n1_max + 1):
             D = prob.dipole_elements(l0, nj, lf, 1, n1_max, coef)
             z[a_ * n1_max: (a_ + 1) * n1_max, b_ * n1_max + nj - 1, 0] = c0 * D
+    return z
+
+
+# ---- the TDSE in the eigenstate basis (Problem.tdse_propagate): tableau, field table, couplings, CSs/TDSE_COEFFs.dat --------
+# MOD_RK_PARAMS (Modules.f90:559-586) as exact fractions: a21 .. a65 (:568-572), b (:574-575, b6 = 0), c (:577-578), d (:580-581)
+RK_A = ((), (_F(2, 9),), (_F(1, 12), _F(1, 4)), (_F(69, 128), _F(-243, 128), _F(135, 64)),
+        (_F(-17, 12), _F(27, 4), _F(-27, 5), _F(16, 15)), (_F(65, 432), _F(-5, 16), _F(13, 16), _F(4, 27), _F(5, 144)))
+RK_B = (_F(1, 9), _F(0), _F(9, 20), _F(16, 45), _F(1, 12), _F(0))
+RK_C = (_F(0), _F(2, 9), _F(1, 3), _F(3, 4), _F(1), _F(5, 6))
+RK_D = (_F(47, 450), _F(0), _F(12, 25), _F(32, 225), _F(1, 30), _F(6, 25))
+
+
+def rk_nodes(t0, dt, nsteps):
+    """The (nsteps, 6) stage times t0 + (n + c_s) dt of Problem.tdse_propagate."""
+    import numpy as np
+    c = np.array([float(x) for x in RK_C])
+    return float(t0) + (np.arange(nsteps, dtype=np.float64)[:, None] + c[None, :]) * float(dt)
+
+
+def field_table(fns, t0, dt, nsteps):
+    """The field argument of Problem.tdse_propagate: complex (nsteps, 6, nscan), [n, s, q] = f_q(t0 + (n + c_s) dt).  fns: one entry
+    per scan, a callable of the array of times or an array of shape (nsteps, 6) already on rk_nodes(t0, dt, nsteps)."""
+    import numpy as np
+    t = rk_nodes(t0, dt, nsteps)
+    fns = list(fns)
+    out = np.zeros((nsteps, 6, len(fns)), dtype=np.complex128)
+    for q, f in enumerate(fns):
+        v = np.asarray(f(t) if callable(f) else f, dtype=np.complex128)
+        if v.shape != t.shape:
+            raise ValueError("scan %d: the field must give one value per stage time %s, got shape %s" % (q, t.shape, v.shape))
+        out[:, :, q] = v
+    return out
+
+
+def tdse_system(prob, channels, n0, count, kind_pi=1, mph=0):
+    """(E, pairs, D) of Problem.tdse_propagate for the states n0 .. n0+count-1 (1-based) of `channels`, a list of (l, m) of the
+    last solve: E (nch, count) from that solve, pairs = positions (ket channel, bra channel) of dipole_blocks, D (npairs, count,
+    count) = c0 * dipole_matrix in ONE call -- the blocks dipole_matelem writes to MatElem_All.dat, D[p, i, f] = z[bra f, ket i].
+    Length gauge (kind_pi = 1): drive with f = F(t); velocity gauge (2): with f = -i A(t)."""
+    import numpy as np
+    E_all, l_first = getattr(prob, "last_E", None), getattr(prob, "last_l0", 0)
+    if E_all is None:
+        raise ValueError("tdse_system needs the eigenvalues of the problem's last solve()")
+    E = np.stack([np.asarray(E_all[l - l_first][n0 - 1: n0 - 1 + count], dtype=np.float64) for l, _ in channels])
+    if E.shape != (len(channels), count):
+        raise ValueError("states %d .. %d are not in the last solve" % (n0, n0 + count - 1))
+    blocks = dipole_blocks(channels, kind_pi, mph)
+    pairs = [(b_, a_) for a_, b_, *_ in blocks]
+    if not blocks:
+        return E, pairs, np.zeros((0, count, count))
+    D = prob.dipole_matrix([(l0, lf) for _, _, l0, lf, _, _ in blocks], n0, count, n0, count,
+                           np.array([coef for *_, coef in blocks], dtype=np.float64))
+    D = np.array([c0 for *_, c0, _ in blocks], dtype=np.float64)[:, None, None] * D
+    return E, pairs, D
+
+
+def write_tdse_coeffs(path, a):
+    """`CSs/TDSE_COEFFs.dat` as READ_TDCOEFF reads it (ReadInputs.f90:453-467): one list-directed record `n Re Im` per state, in the
+    row order of MatElem_All.dat (channel position * count + n); a: complex (nch, count) or (nvec,); 17 significant digits, so
+    read_tdse_coeffs returns the same bits.  n is the state's number in its channel (the reader overwrites it, :464)."""
+    import numpy as np
+    a = np.asarray(a, dtype=np.complex128)
+    count = a.shape[-1]
+    with open(path, "w") as f:
+        for i, z in enumerate(a.reshape(-1)):
+            f.write(" %d %.16E %.16E\n" % (i % count + 1, z.real, z.imag))
+
+
+def read_tdse_coeffs(path, nvec):
+    """The nvec amplitudes of `CSs/TDSE_COEFFs.dat`, read the way READ_TDCOEFF does (list-directed `ni, fi(1), fi(2)`)."""
+    import numpy as np
+    z = np.zeros(nvec, dtype=np.complex128)
+    with open(path) as f:
+        for i in range(nvec):
+            t = f.readline().replace(",", " ").split()
+            if len(t) < 3:
+                raise ValueError("An Error Ocurred Reading the Probs: record %d" % (i + 1))
+            z[i] = complex(float(t[1].replace("D", "E")), float(t[2].replace("D", "E")))
     return z
 
 

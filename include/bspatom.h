@@ -228,6 +228,42 @@ int bspatom_wavefunctions(bspatom_problem *p, int l0, int nl, int n0, int count,
 int bspatom_wavefunctions_dev(bspatom_problem *p, int l0, int nl, int n0, int count, int npts, const double *r, double *U_dev,
                               double *dU_dev);
 
+/* ---- the TDSE in the basis of the field-free eigenstates (csrc/tdse.hip) ---------------------------------------------------- */
+/* What the blocks above are for: the sibling TDSE programs integrate i da/dt = (E + f(t) D) a in the eigenstate basis.  The reference
+ * ships the state arrays zf, zdfdt, zVtij (Modules.f90:238-246), the envelopes CHAMP (:330-396), the tableau MOD_RK_PARAMS (:559-586)
+ * and the reader of the result READ_TDCOEFF (ReadInputs.f90:453-467), not the integrator.  This is it, for nscan wave packets at once.
+ *   nch channels of count states: E[c*count + n]; npairs coupling blocks between channels ci[p] != cf[p] (0-based positions in E),
+ *   D[(p*count + i)*count + f], i a state of channel ci[p], f of cf[p] -- bspatom_dipole_matrix's layout with count_ini = count_fin;
+ *   nscan independent wave packets, scan q driven by its own complex scalar f_q(t).  For every q
+ *     i d a_c/dt = E_c .* a_c + sum_{p: cf[p]=c} f_q(t) (D_p^T a_ci[p]) + sum_{p: ci[p]=c} conj(f_q(t)) (D_p a_cf[p]),
+ *     (D_p^T a)[f] = sum_i D_p[i][f] a[i], (D_p a)[i] = sum_f D_p[i][f] a[f]:
+ *   every block enters with its Hermitian conjugate, the Hamiltonian is Hermitian for any complex f (length gauge: f = F(t) real;
+ *   velocity gauge: f = -i A(t) on the real a1/r + a2 d/dr blocks).  Pairs in any order and either orientation; a repeated pair adds.
+ * Integrator: nsteps fixed steps dt of the six-stage embedded pair of MOD_RK_PARAMS: y_s = a + dt sum_{j<s} A_sj k_j,
+ * k_s = -i H(t_n + c_s dt) y_s, c = (0, 2/9, 1/3, 3/4, 1, 5/6); a_{n+1} = a_n + dt sum_s d_s k_s with the 5th-order weights
+ * d = (47/450, 0, 12/25, 32/225, 1/30, 6/25); err[q] = max over steps, channels, states of dt |sum_s (d_s - b_s) k_s|,
+ * b = (1/9, 0, 9/20, 16/45, 1/12, 0).  No step-size control (a result is a function of its inputs alone); stability, dt max|E|, is the
+ * caller's business; amplitudes are not checked for finiteness.
+ * The library never evaluates a pulse: field[((n*6 + s)*nscan + q)*2 + {0,1}] = Re, Im of f_q(t0 + (n + c_s) dt).
+ *   a    [((q*nch + c)*count + n)*2 + {0,1}] (complex128 of shape (nscan, nch, count)); in: a(t0), out: a(t0 + nsteps dt)
+ *   snap the amplitudes after steps snap_every, 2 snap_every, .. in the same layout one after the other (nsteps / snap_every of them);
+ *        may be NULL;  err: nscan doubles, may be NULL.  nsteps = 0 returns a as given; npairs = 0 (ci, cf, D NULL) is allowed.
+ * The sums of an element run over the channel's pairs in ascending p and along each block ascending, on v_mfma_f64_16x16x4_f64; no
+ * split depends on nscan, nch, the pair list or the snapshots; no atomics on amplitudes: results are run-to-run bit-identical, a scan
+ * does not depend on the other scans of the call, a snapshot equals the result of the shorter run.  Seven launches per step on the
+ * problem's stream.  The problem gives the device and the stream only: no solve is needed.
+ * The host variant stages the field table and the snapshots through device buffers of at most 256 MiB together
+ * (bspatom_set_option("tdse_stage_mb", m) sets another bound; one step's worth at least); the result does not depend on the bound.
+ * BSPATOM_ERR_ARG: a null p, E, a, field (nsteps > 0), ci, cf or D (npairs > 0); nch, count or nscan < 1; nsteps < 0; npairs < 0;
+ * snap_every < 0; snap given with snap_every = 0; a channel index outside 0..nch-1; ci[p] == cf[p]; a dt that is not finite.
+ * The _dev variant: E_dev, D_dev, field_dev, a_dev, snap_dev in device memory of the problem's device; ci, cf, err host pointers. */
+int bspatom_tdse_propagate(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf,
+                           const double *D, int nscan, int nsteps, double dt, const double *field, double *a, int snap_every,
+                           double *snap, double *err);
+int bspatom_tdse_propagate_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                               const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                               double *a_dev, int snap_every, double *snap_dev, double *err);
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
@@ -243,8 +279,8 @@ int bspatom_last_timing(const bspatom_problem *p, double ms[6]);
  * times and launch counts per slot since the previous call into ms[] / launches[] (cap >= the slot count, which it returns)
  * and forgets them.  Slots: 0 rank-128 update (syr2k), 1 symm, 2 panel QR, 3 the small products of the panel chain,
  * 4 sb2sb_mfma_kernel, 5 sbr_rows_kernel<8> / <16> (sb16st_kernel with BSP_SB16_ROWS=0), 6 batched bisection, 7 Cholesky + standard form,
- * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip); bspatom_kernel_slot_name(i)
- * names them.  Launches on different streams overlap: the sums are sums of launch durations, not wall time. */
+ * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel (tdse.hip);
+ * bspatom_kernel_slot_name(i) names them.  Launches on different streams overlap: the sums are sums of launch durations, not wall time. */
 int bspatom_kernel_times(double *ms, int32_t *launches, int cap);
 const char *bspatom_kernel_slot_name(int slot);
 
