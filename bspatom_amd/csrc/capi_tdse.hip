@@ -1,5 +1,5 @@
-// capi_tdse.hip -- bspatom_tdse_propagate / _dev (include/bspatom.h): the argument checks, the per-channel entry lists, the
-// working buffers and the step loop of tdse.hip.  The problem handle gives the device and the stream; nothing of a solve is read.
+// capi_tdse.hip -- bspatom_tdse_propagate / _dev and bspatom_tdse_observe / _dev (include/bspatom.h): the argument checks, the
+// per-channel entry lists, the working buffers and the step loop of tdse.hip.  One code path: propagate is observe without rows.  The problem handle gives the device and the stream; nothing of a solve is read.
 #include <cmath>
 #include "capi_internal.h"
 
@@ -26,13 +26,16 @@ bool args_ok(const bspatom_problem *p, int nch, int count, const double *E, int 
 struct Plan {
     TdseDims d;
     DevArray<int> cptr, ent;
-    DevArray<double> aw, K;
+    DevArray<double> aw, K, part;
     DevArray<unsigned long long> err2;
-    size_t rows = 0;
-    int prepare(bspatom_problem *p, int nch, int count, int nscan, int npairs, const int32_t *ci, const int32_t *cf)
+    size_t rows = 0, odbl = 0;                 // odbl: doubles of one row of observables, [nscan][nch][4]
+    bool observing = false;
+    int prepare(bspatom_problem *p, int nch, int count, int nscan, int npairs, const int32_t *ci, const int32_t *cf, bool observing_)
     {
         d = {nch, count, nscan, tdse_columns(nscan)};
         rows = (size_t)nch * count;
+        odbl = (size_t)4 * nscan * nch;
+        observing = observing_;
         // channel c's entries in ascending p: (p, cf[p], 1) where ci[p] = c, (p, ci[p], 0) where cf[p] = c
         std::vector<int> cp(nch + 1, 0), en((size_t)6 * npairs + 3, 0);
         for (int q = 0; q < npairs; ++q) { ++cp[ci[q] + 1]; ++cp[cf[q] + 1]; }
@@ -48,16 +51,21 @@ struct Plan {
         if ((rc = cptr.put(cp.data(), cp.size())) || (rc = ent.put(en.data(), en.size())) || (rc = aw.alloc(rows * d.NC)) ||
             (rc = K.alloc(6 * rows * d.NC)) || (rc = err2.alloc(nscan)))
             return rc;
+        // the observing kernel's partials: one of 4 doubles per (channel, row tile of 64 states, scan slot)
+        if (observing && (rc = part.alloc((size_t)nch * ((count + 63) / 64) * (d.NC / 2) * 4))) return rc;
         return HIP_RC(hipMemsetAsync(err2.p, 0, (size_t)nscan * sizeof(unsigned long long), p->st));
     }
-    TdseBufs bufs(const double *d_E, const double *d_D) const { return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p}; }
-    // steps n0 .. n1-1; d_field: the table from step n0 on; d_snap (or null): where snapshot number s0 (from 0) goes, the later ones behind it
-    int run(bspatom_problem *p, const TdseBufs &w, int n0, int n1, double dt, const double *d_field, int snap_every, double *d_snap, int s0)
+    TdseBufs bufs(const double *d_E, const double *d_D) const { return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p, observing ? part.p : nullptr}; }
+    // steps n0 .. n1-1; d_field: the table from step n0 on; d_snap (or null): where snapshot number s0 (from 0) goes, the later ones behind it;
+    // d_obs (or null): where row j0 goes (row j = the amplitudes before step j obs_every), the later ones behind it
+    int run(bspatom_problem *p, const TdseBufs &w, int n0, int n1, double dt, const double *d_field, int snap_every, double *d_snap, int s0,
+            int obs_every, double *d_obs, int j0)
     {
         for (int n = n0; n < n1; ++n) {
-            double *sn = nullptr;
+            double *sn = nullptr, *ob = nullptr;
             if (d_snap && (n + 1) % snap_every == 0) sn = d_snap + ((size_t)((n + 1) / snap_every - 1 - s0)) * rows * d.nscan * 2;
-            const int rc = launch_tdse_step(d, w, d_field + (size_t)(n - n0) * 12 * d.nscan, dt, sn, p->st);
+            if (d_obs && n % obs_every == 0) ob = d_obs + (size_t)(n / obs_every - j0) * odbl;
+            const int rc = launch_tdse_step(d, w, d_field + (size_t)(n - n0) * 12 * d.nscan, dt, sn, ob, p->st);
             if (rc) return rc;
         }
         return BSP_OK;
@@ -77,6 +85,97 @@ struct Plan {
         return BSP_OK;
     }
 };
+
+// obs_every = 0: no observables (obs null).  Otherwise rows for the steps 0, obs_every, .. < nsteps, then the row of the final amplitudes.
+int run_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci, const int32_t *cf,
+            const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev, double *a_dev, int snap_every,
+            double *snap_dev, double *err, int obs_every, double *obs_dev)
+{
+    const bool observing = obs_every > 0;
+    if (nsteps == 0 && !observing) {
+        if (err) for (int q = 0; q < nscan; ++q) err[q] = 0.0;
+        return BSP_OK;
+    }
+    BSP_HIP(hipSetDevice(p->device));
+    Plan pl;
+    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf, observing);
+    if (!rc) rc = launch_tdse_pack(pl.d, a_dev, pl.aw.p, p->st);
+    const TdseBufs w = pl.bufs(E_dev, D_dev);
+    if (!rc) rc = pl.run(p, w, 0, nsteps, dt, field_dev, snap_every, snap_dev, 0, obs_every, obs_dev, 0);
+    if (!rc && observing) {
+        const size_t last = nsteps > 0 ? (size_t)(nsteps - 1) / obs_every + 1 : 0;
+        rc = launch_tdse_observe(pl.d, w, nullptr, obs_dev + last * pl.odbl, p->st);
+    }
+    if (!rc && nsteps > 0) rc = launch_tdse_unpack(pl.d, pl.aw.p, a_dev, p->st);
+    if ((rc = drain(p, rc))) return rc;
+    return pl.errors(dt, err);
+}
+
+int run_host(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf, const double *D,
+             int nscan, int nsteps, double dt, const double *field, double *a, int snap_every, double *snap, double *err, int obs_every,
+             double *obs)
+{
+    const bool observing = obs_every > 0;
+    if (nsteps == 0 && !observing) {
+        if (err) for (int q = 0; q < nscan; ++q) err[q] = 0.0;
+        return BSP_OK;
+    }
+    BSP_HIP(hipSetDevice(p->device));
+    const size_t rows = (size_t)nch * count, adbl = rows * nscan * 2, fdbl = (size_t)12 * nscan;     // doubles of a snapshot, of a step's field
+    const size_t odbl = (size_t)4 * nscan * nch;                                                      // of a row of observables
+    // steps per group: the field of g steps, the (at most g / snap_every + 1) snapshots and the (at most (g - 1) / obs_every + 1)
+    // observed steps among them within the bound, one step at least
+    const bool snapping = snap && snap_every > 0;
+    const size_t bound = tdse_stage_bytes() / sizeof(double);
+    auto snaps_of = [&](size_t g) { return snapping ? g / snap_every + 1 : (size_t)0; };
+    auto obs_of = [&](size_t g) { return observing && g > 0 ? (g - 1) / obs_every + 1 : (size_t)0; };
+    auto need = [&](size_t g) { return g * fdbl + snaps_of(g) * adbl + obs_of(g) * odbl; };
+    const size_t per_step = fdbl + adbl + (observing ? odbl : 0);
+    size_t g = bound / fdbl;
+    if (g > (size_t)nsteps) g = nsteps;
+    while (g > 1 && need(g) > bound) {
+        const size_t over = need(g) - bound;
+        const size_t dec = over / per_step > 1 ? over / per_step : 1;
+        g = g > dec ? g - dec : 1;
+    }
+    if (g < 1) g = 1;
+    Plan pl;
+    DevArray<double> dE, dD, da, dfield, dsnap, dobs;
+    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf, observing);
+    if (!rc) rc = dE.put(E, rows);
+    if (!rc && npairs > 0) rc = dD.put(D, (size_t)npairs * count * count);
+    if (!rc) rc = da.put(a, adbl);
+    if (!rc && nsteps > 0) rc = dfield.alloc(g * fdbl);
+    if (!rc && snapping) rc = dsnap.alloc(snaps_of(g) * adbl);
+    if (!rc && observing) rc = dobs.alloc((obs_of(g) > 0 ? obs_of(g) : 1) * odbl);
+    if (!rc) rc = launch_tdse_pack(pl.d, da.p, pl.aw.p, p->st);
+    const TdseBufs w = pl.bufs(dE.p, dD.p);
+    for (int n0 = 0; !rc && n0 < nsteps; n0 += (int)g) {
+        const int n1 = n0 + (int)g < nsteps ? n0 + (int)g : nsteps;
+        rc = HIP_RC(hipMemcpyAsync(dfield.p, field + (size_t)n0 * fdbl, (size_t)(n1 - n0) * fdbl * sizeof(double), hipMemcpyHostToDevice, p->st));
+        const int s0 = snapping ? n0 / snap_every : 0, s1 = snapping ? n1 / snap_every : 0;
+        // rows j0 .. j1-1: the observed steps j obs_every of n0 .. n1-1
+        const int j0 = observing ? (n0 + obs_every - 1) / obs_every : 0, j1 = observing ? (n1 + obs_every - 1) / obs_every : 0;
+        if (!rc) rc = pl.run(p, w, n0, n1, dt, dfield.p, snap_every, snapping ? dsnap.p : nullptr, s0, obs_every, observing ? dobs.p : nullptr, j0);
+        if (!rc && s1 > s0)
+            rc = HIP_RC(hipMemcpyAsync(snap + (size_t)s0 * adbl, dsnap.p, (size_t)(s1 - s0) * adbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        if (!rc && j1 > j0)
+            rc = HIP_RC(hipMemcpyAsync(obs + (size_t)j0 * odbl, dobs.p, (size_t)(j1 - j0) * odbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc && observing) {
+        const size_t last = nsteps > 0 ? (size_t)(nsteps - 1) / obs_every + 1 : 0;
+        rc = launch_tdse_observe(pl.d, w, nullptr, dobs.p, p->st);
+        if (!rc) rc = HIP_RC(hipMemcpyAsync(obs + last * odbl, dobs.p, odbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc && nsteps > 0) {
+        rc = launch_tdse_unpack(pl.d, pl.aw.p, da.p, p->st);
+        if (!rc) rc = HIP_RC(hipMemcpyAsync(a, da.p, adbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if ((rc = drain(p, rc))) return rc;
+    return pl.errors(dt, err);
+}
+
+bool obs_args_ok(int obs_every, const double *obs) { return obs_every >= 0 && (obs_every == 0 ? obs == nullptr : obs != nullptr); }
 }  // namespace
 
 extern "C" int bspatom_tdse_propagate_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
@@ -84,18 +183,7 @@ extern "C" int bspatom_tdse_propagate_dev(bspatom_problem *p, int nch, int count
                                           const double *field_dev, double *a_dev, int snap_every, double *snap_dev, double *err)
 {
     if (!args_ok(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev)) return BSP_ERR_ARG;
-    if (nsteps == 0) {
-        if (err) for (int q = 0; q < nscan; ++q) err[q] = 0.0;
-        return BSP_OK;
-    }
-    BSP_HIP(hipSetDevice(p->device));
-    Plan pl;
-    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf);
-    if (!rc) rc = launch_tdse_pack(pl.d, a_dev, pl.aw.p, p->st);
-    if (!rc) rc = pl.run(p, pl.bufs(E_dev, D_dev), 0, nsteps, dt, field_dev, snap_every, snap_dev, 0);
-    if (!rc) rc = launch_tdse_unpack(pl.d, pl.aw.p, a_dev, p->st);
-    if ((rc = drain(p, rc))) return rc;
-    return pl.errors(dt, err);
+    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, 0, nullptr);
 }
 
 extern "C" int bspatom_tdse_propagate(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
@@ -103,44 +191,27 @@ extern "C" int bspatom_tdse_propagate(bspatom_problem *p, int nch, int count, co
                                       double *a, int snap_every, double *snap, double *err)
 {
     if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap)) return BSP_ERR_ARG;
-    if (nsteps == 0) {
-        if (err) for (int q = 0; q < nscan; ++q) err[q] = 0.0;
-        return BSP_OK;
-    }
-    BSP_HIP(hipSetDevice(p->device));
-    const size_t rows = (size_t)nch * count, adbl = rows * nscan * 2, fdbl = (size_t)12 * nscan;     // doubles of a snapshot, of a step's field
-    // steps per group: the field of g steps and the (at most g / snap_every + 1) snapshots among them within the bound, one step at least
-    const bool snapping = snap && snap_every > 0;
-    const size_t bound = tdse_stage_bytes() / sizeof(double);
-    auto snaps_of = [&](size_t g) { return snapping ? g / snap_every + 1 : (size_t)0; };
-    size_t g = bound / fdbl;
-    if (g > (size_t)nsteps) g = nsteps;
-    while (g > 1 && g * fdbl + snaps_of(g) * adbl > bound) {
-        const size_t over = g * fdbl + snaps_of(g) * adbl - bound;
-        const size_t dec = over / (fdbl + adbl) > 1 ? over / (fdbl + adbl) : 1;
-        g = g > dec ? g - dec : 1;
-    }
-    if (g < 1) g = 1;
-    Plan pl;
-    DevArray<double> dE, dD, da, dfield, dsnap;
-    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf);
-    if (!rc) rc = dE.put(E, rows);
-    if (!rc && npairs > 0) rc = dD.put(D, (size_t)npairs * count * count);
-    if (!rc) rc = da.put(a, adbl);
-    if (!rc) rc = dfield.alloc(g * fdbl);
-    if (!rc && snapping) rc = dsnap.alloc(snaps_of(g) * adbl);
-    if (!rc) rc = launch_tdse_pack(pl.d, da.p, pl.aw.p, p->st);
-    const TdseBufs w = pl.bufs(dE.p, dD.p);
-    for (int n0 = 0; !rc && n0 < nsteps; n0 += (int)g) {
-        const int n1 = n0 + (int)g < nsteps ? n0 + (int)g : nsteps;
-        rc = HIP_RC(hipMemcpyAsync(dfield.p, field + (size_t)n0 * fdbl, (size_t)(n1 - n0) * fdbl * sizeof(double), hipMemcpyHostToDevice, p->st));
-        const int s0 = snapping ? n0 / snap_every : 0, s1 = snapping ? n1 / snap_every : 0;
-        if (!rc) rc = pl.run(p, w, n0, n1, dt, dfield.p, snap_every, snapping ? dsnap.p : nullptr, s0);
-        if (!rc && s1 > s0)
-            rc = HIP_RC(hipMemcpyAsync(snap + (size_t)s0 * adbl, dsnap.p, (size_t)(s1 - s0) * adbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
-    }
-    if (!rc) rc = launch_tdse_unpack(pl.d, pl.aw.p, da.p, p->st);
-    if (!rc) rc = HIP_RC(hipMemcpyAsync(a, da.p, adbl * sizeof(double), hipMemcpyDeviceToHost, p->st));
-    if ((rc = drain(p, rc))) return rc;
-    return pl.errors(dt, err);
+    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, 0, nullptr);
+}
+
+extern "C" int bspatom_tdse_observe_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                                        const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                                        double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev)
+{
+    if (!args_ok(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev) ||
+        !obs_args_ok(obs_every, obs_dev))
+        return BSP_ERR_ARG;
+    if (obs_every == 0)
+        return bspatom_tdse_propagate_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err);
+    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, obs_every, obs_dev);
+}
+
+extern "C" int bspatom_tdse_observe(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
+                                    const int32_t *cf, const double *D, int nscan, int nsteps, double dt, const double *field, double *a,
+                                    int snap_every, double *snap, double *err, int obs_every, double *obs)
+{
+    if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap) || !obs_args_ok(obs_every, obs))
+        return BSP_ERR_ARG;
+    if (obs_every == 0) return bspatom_tdse_propagate(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err);
+    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs);
 }

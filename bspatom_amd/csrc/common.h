@@ -291,12 +291,17 @@ struct TdseBufs {
     const double *E, *D;         // [nch][count]; [npairs][count][count]
     double *a, *K;               // working amplitudes; the six k_s, each nch * count * NC doubles
     unsigned long long *err2;    // [nscan] bit patterns of max |sum_s (d_s - b_s) k_s|^2, zeroed by the caller
+    double *part;                // observables: [nch][ceil(count / 64)][NC / 2][4] partials of the row tiles (null: nothing is observed)
 };
 extern const double TDSE_A[6][5], TDSE_D[6], TDSE_B[6];
 int tdse_columns(int nscan);
 // one step: six stage launches and the step kernel; d_field: the 6 * nscan complex values of this step; d_snap: null, or where the
-// new amplitudes go in the caller's layout [nscan][nch][count] complex
-int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, hipStream_t st);
+// new amplitudes go in the caller's layout [nscan][nch][count] complex; d_obs: null, or where the observables of the amplitudes
+// BEFORE the step go, [nscan][nch][4] (then stage 0 is the observing kernel, followed by the reduction: eight launches)
+int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, double *d_obs, hipStream_t st);
+// the observables of w.a into d_row [nscan][nch][4]: tdse_observe_kernel and the reduction of its row-tile partials.  d_field: the
+// stage-0 field of a step that follows, whose k_0 the kernel then leaves exactly as the plain stage does; null: the measurement alone
+int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *d_field, double *d_row, hipStream_t st);
 int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st);
 int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st);
 

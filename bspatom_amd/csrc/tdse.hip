@@ -3,7 +3,8 @@
 // for nscan wave packets at once, fixed steps of the embedded six-stage 4(5) Runge-Kutta pair of the reference (MOD_RK_PARAMS,
 // Modules.f90:559-586; the state arrays zf, zdfdt, zVtij at :238-246).  Seven launches per step: one stage kernel per stage, which
 // forms its operand y_s = a + dt sum_j A_sj k_j while it loads it and leaves k_s = -i H(t_n + c_s dt) y_s, then one kernel for the
-// step, the error estimate and the snapshot.
+// step, the error estimate and the snapshot.  bspatom_tdse_observe: on an observed step stage 0 runs as tdse_observe_kernel, which also
+// measures a(t_n) (populations, E |a|^2, the coupling expectation value per channel), followed by tdse_obs_reduce_kernel: eight launches.
 //
 // Working layout: the amplitudes of channel c are a real matrix [count][NC], column 2q = Re, 2q + 1 = Im of scan q, NC = 2 nscan
 // rounded up to 16 (zero columns); a, k_0 .. k_5 are [nch][count][NC] each.  A coupling block times these columns is a real
@@ -64,13 +65,23 @@ __device__ __forceinline__ void load_y(double (&v)[S + 1], const double *__restr
 //   entry with cf[p] = c:  accT += D_p^T y_ci   -- the A tile is contiguous along M in memory (D_p[i][f], f = output row)
 //   entry with ci[p] = c:  accN += D_p y_cf     -- contiguous along K; staged through the column permutation lds_swz
 // Epilogue per scan: h = E y + f accT + conj(f) accN, k_s = -i h.
-template <int S, int TN>
-__global__ __launch_bounds__(256) void tdse_stage_kernel(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
-                                                        const int *__restrict__ ent, const double *__restrict__ E,
-                                                        const double *__restrict__ D, const double *__restrict__ a,
-                                                        double *__restrict__ K, size_t kstride, const double *__restrict__ fld,
-                                                        StageCoef cf, double dt)
+//
+// OBS (stage 0 only, y_0 = a(t_n)): the epilogue also measures.  Before the field enters, accT of channel c is
+// U = sum_{p: cf[p] = c} D_p^T a_ci[p], so per row f of scan q the lane pair (Re, Im) holds everything of
+//   |a|^2,  E |a|^2,  conj(a) U = (y_re u_re + y_im u_im) + i (y_re u_im - y_im u_re):
+// every lane forms y y, E (y y), y u and +- y u' (u' the neighbour's u; - on the Im lane) of its component, chained by fma over its
+// four rows r = 0 .. 3; then lane + (lane ^ 16), + (lane ^ 32) (the rows (lane >> 4) of the wave), + (lane ^ 1) (Re + Im), the
+// four waves through LDS as ((w0 + w1) + w2) + w3, and one partial of 4 doubles per (channel, row tile, scan) goes to
+// part[((c tm + im) NC/2 + q) 4 + k].  The tree is fixed by count alone; rows beyond count enter as zeros; scans q >= nscan are
+// not written.  fld == nullptr: measure only (the row after the last step) -- the same instructions, so the same bits.
+template <int S, int TN, bool OBS>
+__device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
+                                                const int *__restrict__ ent, const double *__restrict__ E,
+                                                const double *__restrict__ D, const double *__restrict__ a,
+                                                double *__restrict__ K, size_t kstride, const double *__restrict__ fld,
+                                                StageCoef cf, double dt, double *__restrict__ part)
 {
+    static_assert(!OBS || S == 0, "only stage 0 runs on a(t_n)");
     constexpr int NB = 16 * TN, TLDB = NB + 16, BEL = TBK * NB / 256;        // B-tile elements per thread: 1 or 2
     __shared__ double As[TBK * TLDA];
     __shared__ double Bs[TBK * TLDB];
@@ -157,13 +168,15 @@ __global__ __launch_bounds__(256) void tdse_stage_kernel(int count, int NC, int 
     // epilogue: this lane holds column col (Re of scan col / 2 if even, Im if odd) of rows (lane >> 4) + 4 r; the other component of the
     // same scan is in lane ^ 1.  Every lane forms its own component of h; k_s = -i h = (Im h, -Re h) is then the neighbour's value.
     double *Ks = K + (size_t)S * kstride;
+    const bool stepping = !OBS || fld != nullptr;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int col = n0 + j * 16 + (lane & 15);
         const int q = col >> 1, odd = col & 1;
         const bool cok = col < NC, fok = q < nscan;
-        const double fre = fld[fok ? 2 * q : 0], fim = fld[fok ? 2 * q + 1 : 0];
+        const double fre = stepping ? fld[fok ? 2 * q : 0] : 0.0, fim = stepping ? fld[fok ? 2 * q + 1 : 0] : 0.0;
         const double fr = fok ? fre : 0.0, fi = fok ? (odd ? fim : -fim) : 0.0;
+        double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int gm = m0 + wave * 16 + (lane >> 4) + 4 * r;
@@ -183,9 +196,80 @@ __global__ __launch_bounds__(256) void tdse_stage_kernel(int count, int NC, int 
             h = fma(fr, w, h);
             h = fma(-fi, wp, h);
             const double hp = __shfl_xor(h, 1);
-            if (ok) Ks[idx] = odd ? -hp : hp;
+            if (ok && stepping) Ks[idx] = odd ? -hp : hp;
+            if constexpr (OBS) {
+                const double yy = y * y;
+                t0 = fma(y, y, t0);
+                t1 = fma(ok ? en : 0.0, yy, t1);
+                t2 = fma(y, u, t2);
+                t3 = fma(y, up, t3);
+            }
+        }
+        if constexpr (OBS) {
+            double t[4] = {t0, t1, t2, odd ? -t3 : t3};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                t[k] += __shfl_xor(t[k], 16);
+                t[k] += __shfl_xor(t[k], 32);
+                t[k] += __shfl_xor(t[k], 1);
+            }
+            // As is free after the last barrier of the main loop: [wave][j][scan of the block of 8][k]
+            if (lane < 16 && !odd) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) As[((wave * TN + j) * 8 + (lane >> 1)) * 4 + k] = t[k];
+            }
         }
     }
+    if constexpr (OBS) {
+        __syncthreads();
+        if (tid < TN * 32) {
+            const int j = tid >> 5, s8 = (tid >> 2) & 7, k = tid & 3;
+            double s = As[((0 * TN + j) * 8 + s8) * 4 + k];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) s += As[((w * TN + j) * 8 + s8) * 4 + k];
+            const int q = ((n0 + j * 16) >> 1) + s8;
+            if (q < nscan) part[(((size_t)c * tm + im) * (NC >> 1) + q) * 4 + k] = s;
+        }
+    }
+}
+
+template <int S, int TN>
+__global__ __launch_bounds__(256) void tdse_stage_kernel(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
+                                                        const int *__restrict__ ent, const double *__restrict__ E,
+                                                        const double *__restrict__ D, const double *__restrict__ a,
+                                                        double *__restrict__ K, size_t kstride, const double *__restrict__ fld,
+                                                        StageCoef cf, double dt)
+{
+    tdse_stage_body<S, TN, false>(count, NC, nscan, tm, tn, cptr, ent, E, D, a, K, kstride, fld, cf, dt, nullptr);
+}
+
+// stage 0 with the measuring epilogue: k_0 exactly as tdse_stage_kernel<0, TN> leaves it (fld == nullptr: no k_0, the measurement alone)
+template <int TN>
+__global__ __launch_bounds__(256) void tdse_observe_kernel(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
+                                                          const int *__restrict__ ent, const double *__restrict__ E,
+                                                          const double *__restrict__ D, const double *__restrict__ a,
+                                                          double *__restrict__ K, const double *__restrict__ fld,
+                                                          double *__restrict__ part)
+{
+    tdse_stage_body<0, TN, true>(count, NC, nscan, tm, tn, cptr, ent, E, D, a, K, 0, fld, StageCoef{}, 0.0, part);
+}
+
+// One thread per (scan, channel): the row-tile partials in ascending tile order, written in the caller's layout row[(q nch + c) 4 + k]
+__global__ __launch_bounds__(256) void tdse_obs_reduce_kernel(int nch, int tm, int ncq, int nscan, const double *__restrict__ part,
+                                                             double *__restrict__ row)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)nscan * nch) return;
+    const int q = (int)(t / nch), c = (int)(t - (long long)q * nch);
+    const double *p0 = part + (((size_t)c * tm) * ncq + q) * 4;
+    double s[4] = {p0[0], p0[1], p0[2], p0[3]};
+    for (int im = 1; im < tm; ++im) {
+        const double *pi = p0 + (size_t)im * ncq * 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] += pi[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) row[(size_t)t * 4 + k] = s[k];
 }
 
 // ---- the step: a += dt sum_s d_s k_s, the error estimate, the snapshot ------------------------------------------------------
@@ -292,11 +376,38 @@ static int launch_stage_s(const TdseDims &d, const TdseBufs &w, const double *fl
     return BSP_OK;
 }
 
-int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, hipStream_t st)
+int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld, double *d_row, hipStream_t st)
+{
+    const int tm = (d.count + TBM - 1) / TBM;
+    {
+        KScope ks_(KS_TDSE, st);
+        if (d.NC == 16) {
+            const long long grid = (long long)d.nch * tm;
+            if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+            hipLaunchKernelGGL((tdse_observe_kernel<1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, 1, w.cptr, w.ent,
+                               w.E, w.D, w.a, w.K, fld, w.part);
+        } else {
+            const int tn = (d.NC + 31) / 32;
+            const long long grid = (long long)d.nch * tm * tn;
+            if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+            hipLaunchKernelGGL((tdse_observe_kernel<2>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent,
+                               w.E, w.D, w.a, w.K, fld, w.part);
+        }
+        BSP_HIP(hipGetLastError());
+    }
+    const long long blocks = ((long long)d.nscan * d.nch + 255) / 256;
+    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_obs_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d.nch, tm, d.NC / 2, d.nscan, w.part, d_row);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, double *d_obs, hipStream_t st)
 {
     const size_t fs = (size_t)2 * d.nscan;
     int rc;
-    if ((rc = launch_stage_s<0>(d, w, d_field, dt, st)) || (rc = launch_stage_s<1>(d, w, d_field + fs, dt, st)) ||
+    if ((rc = d_obs ? launch_tdse_observe(d, w, d_field, d_obs, st) : launch_stage_s<0>(d, w, d_field, dt, st)) ||
+        (rc = launch_stage_s<1>(d, w, d_field + fs, dt, st)) ||
         (rc = launch_stage_s<2>(d, w, d_field + 2 * fs, dt, st)) || (rc = launch_stage_s<3>(d, w, d_field + 3 * fs, dt, st)) ||
         (rc = launch_stage_s<4>(d, w, d_field + 4 * fs, dt, st)) || (rc = launch_stage_s<5>(d, w, d_field + 5 * fs, dt, st)))
         return rc;

@@ -496,6 +496,23 @@ def field_table(fns, t0, dt, nsteps):
     return out
 
 
+def obs_steps(nsteps, obs_every):
+    """The step numbers n_j of the rows of Problem.tdse_observe: 0, obs_every, 2 obs_every, .. < nsteps, then nsteps; row j
+    describes a(t0 + n_j dt).  nsteps = 0: the one row [0]."""
+    if nsteps < 0 or obs_every < 1:
+        raise ValueError("obs_steps needs nsteps >= 0 and obs_every >= 1")
+    return [0] if nsteps == 0 else list(range(0, nsteps, obs_every)) + [nsteps]
+
+
+def tdse_expectations(obs):
+    """(norm, <H0>, 2 Re z, 2 Im z), each (nobs, nscan), of the rows obs (nobs, nscan, nch, 4) of Problem.tdse_observe: the sums over
+    the channels of pop, sum E |a|^2 and z_c.  <H_int> = 2 Re(f z); length gauge: <D> = 2 Re z; velocity gauge (f = -i A on the
+    real blocks): 2 Im z."""
+    import numpy as np
+    s = np.asarray(obs, dtype=np.float64).sum(axis=-2)
+    return s[..., 0], s[..., 1], 2.0 * s[..., 2], 2.0 * s[..., 3]
+
+
 def tdse_system(prob, channels, n0, count, kind_pi=1, mph=0):
     """(E, pairs, D) of Problem.tdse_propagate for the states n0 .. n0+count-1 (1-based) of `channels`, a list of (l, m) of the
     last solve: E (nch, count) from that solve, pairs = positions (ket channel, bra channel) of dipole_blocks, D (npairs, count,

@@ -264,6 +264,38 @@ int bspatom_tdse_propagate_dev(bspatom_problem *p, int nch, int count, const dou
                                const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
                                double *a_dev, int snap_every, double *snap_dev, double *err);
 
+/* The same run with its observables: populations, the field-free energy and the coupling expectation value of every channel, on
+ * every obs_every-th step, without a snapshot and without another read of D.  The first 16 arguments are bspatom_tdse_propagate's.
+ * Observed steps: n = 0, obs_every, 2 obs_every, .. < nsteps, and always n = nsteps as the last row:
+ *   nobs = (nsteps - 1) / obs_every + 2 for nsteps >= 1, nobs = 1 for nsteps = 0; row j describes a(t0 + n_j dt); when obs_every
+ *   divides nsteps the rows form a uniform time grid with both ends.  nsteps = 0 is a real call: one row for a as given, no field
+ *   needed -- the expectation value of any block operator over any set of wave packets (acceleration form of the dipole: pass the
+ *   snapshots as scans and blocks from bspatom_operator_matrix).
+ *   obs[((j*nscan + q)*nch + c)*4 + k], sums over the count states n of channel c of scan q:
+ *     k = 0     pop = sum_n |a|^2
+ *     k = 1     sum_n E[c][n] |a|^2
+ *     k = 2, 3  Re, Im of z_c = sum_{p: cf[p] = c} sum_{i,f} conj(a[cf[p]][f]) D_p[i][f] a[ci[p]][i]
+ *   With z = sum_c z_c the interaction energy is <H_int> = 2 Re(f z): length gauge <D> = 2 Re z; a velocity-gauge drive
+ *   f = -i A on the real blocks gives 2 Im z.  sum_c pop is the norm, sum_c obs[..1] is <H0>.
+ * How: on an observed step the first stage runs as tdse_observe_kernel -- stage 0's operand is a(t_n), and before the field enters its
+ * epilogue the accumulator of channel c holds sum_{p: cf[p] = c} D_p^T a_ci[p] -- followed by one small kernel that adds the
+ * partials of the 64-state row tiles: eight launches on an observed step, seven otherwise, two after the last step.
+ * Guarantees:
+ *   a, snap and err are bit-identical to bspatom_tdse_propagate* on the same inputs, whatever obs_every is;
+ *   a row depends on (E, D, the pair list, count) and that scan's amplitudes alone: not on nscan, the other scans, obs_every, nsteps,
+ *   the snapshots or the staging bound;
+ *   no floating-point atomics: every sum runs through a tree fixed by count and the channel's entry list, run-to-run bit-identical;
+ *   the last row (a measurement with no step after it) has the bits that a stage-0 measurement of the same amplitudes has.
+ * The host variant stages the rows with the field and the snapshots under the same bound (tdse_stage_mb).
+ * BSPATOM_ERR_ARG: everything bspatom_tdse_propagate names; obs_every < 0; obs given with obs_every = 0; obs_every >= 1 with obs NULL.
+ * obs_every = 0 with obs NULL is bspatom_tdse_propagate*.  The _dev variant: obs_dev in device memory, written in place. */
+int bspatom_tdse_observe(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf,
+                         const double *D, int nscan, int nsteps, double dt, const double *field, double *a, int snap_every,
+                         double *snap, double *err, int obs_every, double *obs);
+int bspatom_tdse_observe_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                             const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                             double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev);
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
@@ -279,7 +311,7 @@ int bspatom_last_timing(const bspatom_problem *p, double ms[6]);
  * times and launch counts per slot since the previous call into ms[] / launches[] (cap >= the slot count, which it returns)
  * and forgets them.  Slots: 0 rank-128 update (syr2k), 1 symm, 2 panel QR, 3 the small products of the panel chain,
  * 4 sb2sb_mfma_kernel, 5 sbr_rows_kernel<8> / <16> (sb16st_kernel with BSP_SB16_ROWS=0), 6 batched bisection, 7 Cholesky + standard form,
- * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel (tdse.hip);
+ * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel and tdse_observe_kernel (tdse.hip);
  * bspatom_kernel_slot_name(i) names them.  Launches on different streams overlap: the sums are sums of launch durations, not wall time. */
 int bspatom_kernel_times(double *ms, int32_t *launches, int cap);
 const char *bspatom_kernel_slot_name(int slot);
