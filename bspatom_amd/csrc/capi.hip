@@ -66,6 +66,8 @@ const OptName OPT_TABLE[] = {
     {"cw_streams", "BSP_CW_STREAMS", &Options::cw_streams},
     {"cw_chunk_min", "BSP_CW_CHUNK_MIN", &Options::cw_chunk_min},
     {"sb8_wgs", "BSP_SB8_WGS", &Options::sb8_wgs},
+    {"sbr_phased", "BSP_SBR_PHASED", &Options::sbr_phased},
+    {"sbr_lag", "BSP_SBR_LAG", &Options::sbr_lag},
     {"fused_probe", "BSP_FUSED_PROBE", &Options::fused_probe},
     {"dipole_stage_mb", "BSP_DIPOLE_STAGE_MB", &Options::dipole_stage_mb},
     {"wf_stage_mb", "BSP_WF_STAGE_MB", &Options::wf_stage_mb},

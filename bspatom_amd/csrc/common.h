@@ -85,6 +85,11 @@ struct Options {
     int cw_band8 = 1;            // BSP_CW_BAND8: 1 = the band reduction hands over the band of half-width 8 it really leaves (one 8 x 8 block
                                  // made triangular at the end) and the chase runs on tiles of 8; 0 = half-width 15, tiles of 16 (as first built)
     int sb8_wgs = 0;             // BSP_SB8_WGS: workgroups of the tiles-of-8 chase per CU the rings are sized for (0 = what fits: 2)
+    int sbr_phased = 1;          // BSP_SBR_PHASED: tiles-of-8 chase: 1 = the step loop of a chasing wave in three parts (ramp-up, a branch-free
+                                 // steady part, ramp-down; sbr2.hip), 0 = one general loop (the cross-check); bit-identical results
+    int sbr_lag = 0;             // BSP_SBR_LAG: tiles-of-8 chase, the data-moving wave's lag (steps between the request of a column and the
+                                 // wait for it): 0 = short in the passes where the ring is bound by its stagger, long elsewhere; 1 = always
+                                 // long; 2 = always short; bit-identical results
     int cw_ipw = 0;              // BSP_CW_IPW: items per wave of crawford_item4_kernel (0 = 4; 1, 2: experiment 9; bit-identical results)
     int cw_ldspad = 0;           // BSP_CW_LDSPAD: KB of unused dynamic LDS per workgroup of crawford_item4_kernel (timing experiment: occupancy)
     int cw_onediv = 0;           // BSP_CW_ONEDIV: reflectors of the band route's RQ loop in the one-division form (A/B switch)

@@ -866,6 +866,7 @@ __global__ __launch_bounds__(576) void sb16st_kernel(int n, int npad, int batch,
 // was) and 8 (half-width <= 8: what the band route's reduction really leaves, crawford.hip).  With B = 8 an item is owned by HALF a
 // DPP row, a wave runs EIGHT sweeps and a pass sixteen; a window column has 16 rows; everything else is the same program.
 constexpr int NCW4 = 6, SB16R_THREADS = (NCW4 + 1) * 64;
+constexpr int SBR_MLAG_SHORT = 2;                       // the short lag of the tiles-of-8 chase (4 and 1 were measured: profiles/r11_chase8_phased.txt)
 // window element at BYTE offset `off` (the tile addresses of the chasing waves are kept in bytes: as indices every access
 // paid a shift, 16 vector instructions per step of a role)
 __device__ __forceinline__ double &ldsb(double *Lw, int off) { return *reinterpret_cast<double *>(reinterpret_cast<char *>(Lw) + off); }
@@ -878,7 +879,11 @@ struct Rw {
     static constexpr int NSW = 2 * RPW;                // sweeps of a pass: two groups of RPW
     static constexpr int MLAG = B == 16 ? 4 : 8;       // steps between the request of a column and the wait for it (about the latency of HBM)
     static constexpr int LP0 = B * (MLAG + 3);         // columns in the window when a pass starts
-    static constexpr int Z = WCOLS * WR;               // z of the diagonal-tile waves [2 groups][RPW items][B]
+    // The short lag (B = 8): what a pass is run with when the ring is bound by its stagger (launch_sb16st).  A follower
+    // pass can start LAG NSW + 2 lag + 5 steps behind its leader: 69 with the long lag, 57 with this one (publish period included)
+    static constexpr int MLAGS = B == 16 ? MLAG : SBR_MLAG_SHORT;
+    static constexpr int STAGGER = LAG * NSW + 2 * MLAG + 5;
+    static constexpr int Z = WCOLS * WR;              // z of the diagonal-tile waves [2 groups][RPW items][B]
     static constexpr int DUMP = Z + 128;               // target of masked stores [6 waves][RPW items][B]
     static constexpr int XS = DUMP + 384;              // exchange slots [2 parities][NSW sweeps][2 B]: v (B), tau, padding
     static constexpr int XPAR = NSW * 2 * B;           // one parity's slots (256 for both B)
@@ -1032,7 +1037,7 @@ __global__ void band_tail_zero_kernel(int n, int npad, int wr, double *__restric
 // at the end of the step, a literal count: the counter is in order over loads and stores and a step issues 4 + 8 resp. 1 + 2 of
 // them, one more with the poll) and are first touched two steps after that.  Columns leave the window with plain stores, at most
 // B per step.
-template <int B, int PH>
+template <int B, int PH, int MLAG>
 __device__ __forceinline__ void mover_step(double *Lw, double *__restrict__ AB, const int n, const int npad, const int LP,
                                            const int RP, const int RPn, const int RPold, const int ps, const int lane,
                                            const unsigned long long *pollp, unsigned long long *pubp, unsigned long long &pw,
@@ -1083,11 +1088,18 @@ __device__ __forceinline__ void mover_step(double *Lw, double *__restrict__ AB, 
     // All but the operations of the last MLAG steps complete: the columns requested MLAG steps ago are in the window, and the
     // stores of that step have reached the L2 -- the columns left of RPold, progress for the member that runs the next pass.  (Two
     // steps were not enough at B = 16: a step is shorter than half the latency of HBM and the wave waited for it every time.)
-    if (B == 16) asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+    // The literal count: MLAG steps of 12 (B = 16) resp. 3 (B = 8) operations.  The long lags do not count the polls (two in eight
+    // steps: the wait is a little stricter than it says); the short lag counts the polls that lie inside its window (one in four
+    // steps, at phase 1), or it would wait for a request only MLAG - 1 steps old.
+    constexpr int OPS = (B == 16 ? 12 : 3) * MLAG;
+    constexpr bool SHORT = MLAG < Rw<B>::MLAG;
+    constexpr int NPOLL = !SHORT ? 0 : (MLAG >= 4 ? MLAG / 4 : (((PH + 3) & 3) < MLAG ? 1 : 0));   // phases PH - MLAG + 1 .. PH that are 1
+    if (SHORT && NPOLL && pollp) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS + NPOLL) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
     MV_STAMP(2)                                                     // the wait for the operations of MLAG steps ago
 #undef MV_STAMP
-    if (PH == 3 && pubp && lane == 0)
+    // progress every fourth step; every second one with the short lag (the follower's start waits for it)
+    if ((PH == 3 || (SHORT && PH == 1)) && pubp && lane == 0)
         __hip_atomic_store(pubp, ((unsigned long long)ps << 32) + (unsigned)RPold, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (PH == 3 && pollp) {
         const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ptmp), hi = __builtin_amdgcn_readfirstlane((unsigned)(ptmp >> 32));
@@ -1097,7 +1109,11 @@ __device__ __forceinline__ void mover_step(double *Lw, double *__restrict__ AB, 
 
 // barrier of a chasing wave whose loads for the next step may still be in flight; its stores may not (LDS operations of a wave
 // complete in order: with more than 15 (B = 16) resp. 7 (B = 8) load instructions behind the last store -- 16 / 24 resp. 8 / 12 in
-// the code as compiled -- that many outstanding means the stores are done)
+// the code as compiled -- that many outstanding means the stores are done).  B = 8, re-read in the code as compiled with the phased
+// loop: role 1 has 8 ds_read_b64 (the tile) behind its last store in every body; role 0 has 4 ds_read2_b64 (v, tau) + 8 ds_read_b64
+// (the tile) = 12 in the general and the wrapping body and 4 + 4 ds_read2_b64 = 8 in the plain steady body, where the tile's addresses
+// are one register and immediates and the loads pair up.  8 is the least the count of 7 allows: whoever makes these loads wider
+// lowers the count with them.
 template <int B>
 __device__ __forceinline__ void stores_done_barrier()
 {
@@ -1105,14 +1121,61 @@ __device__ __forceinline__ void stores_done_barrier()
     else asm volatile("s_waitcnt lgkmcnt(7)\n\ts_barrier" ::: "memory");
 }
 
-// DIAG: the instrumented instance (BSP_SB2ST_DIAG; `diag` non-null); the other carries no stamp, no test for one
-template <int B, bool DIAG = false>
-__global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad, int batch, double *__restrict__ ABall,
-                                                                 double *__restrict__ dall, double *__restrict__ eall,
-                                                                 long long *diag, Sb16Ctl *ctl, int P, int *status, int force_abort)
+// One pass of the data-moving wave with the lag MLAG (the window holds B (MLAG + 3) columns when the pass starts).  pd (DIAG instance,
+// workgroup 0): the pass's own stamps -- steps, ticks of the whole loop, ticks of "poll check and requests", where a follower waits for
+// its leader
+template <int B, bool DIAG, int MLAG>
+__device__ __forceinline__ void mover_pass(double *Lw, double *__restrict__ AB, const int n, const int npad, const int s0,
+                                           const int nsteps, const int ps, const int lane, const unsigned long long *pollp,
+                                           unsigned long long *pubp, Sb16Ctl *C, int *status, long long (&dacc)[5], long long *pd)
+{
+    constexpr int NSW = Rw<B>::NSW;
+    unsigned long long pw = 0, ptmp = 0;                  // the partner's progress word as last seen / as last requested
+    int RP = s0, LP = s0 + B * (MLAG + 3), RPold = s0;    // RPold: RP MLAG steps ago
+    long long dt0 = 0;
+    const long long tp0 = DIAG ? (long long)__builtin_amdgcn_s_memtime() : 0, w0 = dacc[1];
+#define SB16R_MSTEP(PH) \
+    if (t + PH < nsteps) { \
+        int RPn = s0 + NSW + B * ((t + PH) - LAG * (NSW - 1) - 1);   /* columns leaving: left of the trailing sweep's tiles */ \
+        if (RPn > n) RPn = n; \
+        if (RPn < RP) RPn = RP; \
+        { int r4 = s0 + NSW + B * ((t + PH - MLAG) - LAG * (NSW - 1) - 1);      /* RPn of MLAG steps ago */ \
+          RPold = r4 > n ? n : (r4 < s0 ? s0 : r4); } \
+        mover_step<B, PH, MLAG>(Lw, AB, n, npad, LP + B * PH, RP, RPn, RPold, ps, lane, pollp, pubp, pw, ptmp, C, status, DIAG, dacc); \
+        if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime(); \
+        RP = RPn; \
+        lds_only_barrier(); \
+        if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; } \
+    }
+    for (int t = 0; t < nsteps; t += 4) {
+        SB16R_MSTEP(0) SB16R_MSTEP(1) SB16R_MSTEP(2) SB16R_MSTEP(3)
+        LP += 4 * B;
+    }
+#undef SB16R_MSTEP
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (DIAG && pd && lane == 0) {
+        pd[0] = nsteps; pd[1] = (long long)__builtin_amdgcn_s_memtime() - tp0; pd[2] = dacc[1] - w0;
+    }
+}
+
+// DIAG: the instrumented instance (BSP_SB2ST_DIAG; `diag` non-null); the other carries no stamp, no test for one.
+// PHASED (B = 8): the step loop of a chasing wave in three parts.  A wave's eight items start three steps apart and end three steps
+// apart; in between -- steps tA <= t < tB, nearly all of a long pass -- every item of the wave is active and has a successor, and the
+// general body's tests (is the item active, has it a successor, does its sweep start next step, which barrier) all come out the same
+// way.  The steady part runs a body without them: the slot parity is toggled, the tile address is one running base per lane (a tile
+// advances B columns = B WR 8 bytes a step, modulo the ring), and whether a tile of the wave straddles the ring's end is read from a
+// 64-bit mask built once per pass (the ring is 512 columns, a tile advances 8 per step: the pattern repeats every 64 steps).  The
+// arithmetic of a step (chase4_*) and every address it uses are those of the general body: bit-identical results.
+constexpr int SBR_PASSDIAG = 256;                        // per-pass stamps of workgroup 0 behind the 45 per-wave ones, four words each
+template <int B, bool DIAG, bool PHASED>
+__device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double *__restrict__ ABall, double *__restrict__ dall,
+                                              double *__restrict__ eall, long long *diag, Sb16Ctl *ctl, int P, int *status,
+                                              int force_abort, int lagmode)
 {
     using W = Rw<B>;
     constexpr int WSH = W::WSH, WR = W::WR, RPW = W::RPW, NSW = W::NSW, MLAG = W::MLAG, LP0 = W::LP0;
+    constexpr int RINGB = WCOLS * WR * 8, STEPB = B * WR * 8;   // bytes of the ring of window columns, of the B columns a tile advances per step
+    static_assert(!PHASED || B == 8, "the phased step loop is built for tiles of 8");
     extern __shared__ double lds[];
     double *Lw = lds;
     // the whole batch waits for the slowest channel: first on a SIMD shared with a long-running wave of another kernel (as the band
@@ -1170,16 +1233,29 @@ __global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad
     const int npass = (n - 2 + NSW - 1) / NSW;
     for (int ps = w; ps < npass; ps += stride) {
         const int s0 = ps * NSW;
-        int RP = s0, LP = s0 + LP0;                       // columns leave the window left of RP; LP is the next one to be requested
-        if (pollp && ps > 0) {                            // the first LP0 + B columns of this pass, as the pass before left them
+        const int nsteps = (n - s0 - 1 + B - 1) / B + LAG * (NSW - 1);
+        // A ring whose passes are shorter than its members' staggers put together is bound by the stagger: its members idle between
+        // passes, and the steps the long lag spends on hiding the latency of HBM cost wall time one for one.  Such a pass runs with the
+        // short lag.  The rule depends on ps, n and the ring size alone: every member finds the same answer for a pass, and the
+        // results do not depend on it (the lag decides when a column is requested, never what is computed).
+        const bool shortp = W::MLAGS < MLAG && (lagmode == 2 || (lagmode == 0 && stride > 1 && nsteps < stride * W::STAGGER));
+        const int lp0 = shortp ? B * (W::MLAGS + 3) : LP0;
+        int RP = s0, LP = s0 + lp0;                       // columns leave the window left of RP; LP is the next one to be requested
+        const long long tw0 = DIAG ? (long long)__builtin_amdgcn_s_memtime() : 0;
+        if (pollp && ps > 0) {                            // the first lp0 + B columns of this pass, as the pass before left them
             if (tid == 0) {
-                const int need = s0 + LP0 + B < n ? s0 + LP0 + B : n;
+                const int need = s0 + lp0 + B < n ? s0 + lp0 + B : n;
                 s16_wait(pollp, ((unsigned long long)(ps - 1) << 32) + (unsigned)need, C, status);
             }
             __syncthreads();
             asm volatile("buffer_inv sc1" ::: "memory");
         }
-        for (int idx = tid; idx < LP0 * WR; idx += SB16R_THREADS) {
+        long long *pd = nullptr;                          // DIAG: this pass's stamps (workgroup 0: member 0 of channel 0)
+        if (DIAG && blockIdx.x == 0 && (ps - w) / stride < SBR_PASSDIAG) {
+            pd = diag + 45 + 4 * ((ps - w) / stride);
+            if (wv == NCW4 && lane == 0) pd[3] = (long long)__builtin_amdgcn_s_memtime() - tw0;    // the wait for the pass to start
+        }
+        for (int idx = tid; idx < lp0 * WR; idx += SB16R_THREADS) {
             const int c = s0 + (idx >> WSH), d = idx & (WR - 1);
             Lw[((c & (WCOLS - 1)) << WSH) + d] = c + d < n ? AB[(size_t)c * LD + d] : 0.0;
         }
@@ -1189,33 +1265,10 @@ __global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad
             const int hx = ((s0 & (WCOLS - 1)) << WSH) + 1 + j;
             next_reflector<B>(Lw, Lw[hx], j, W::XS, hx * 8);
         }
-        const int nsteps = (n - s0 - 1 + B - 1) / B + LAG * (NSW - 1);
-#define SB16R_RPN(t) \
-        int RPn = s0 + NSW + B * ((t) - LAG * (NSW - 1) - 1);   /* columns leaving: left of the trailing sweep's tiles */ \
-        if (RPn > n) RPn = n; \
-        if (RPn < RP) RPn = RP;
         if (wv == NCW4) {                                 // the last wave moves data and does nothing else
-            unsigned long long pw = 0, ptmp = 0;          // the partner's progress word as last seen / as last requested
-            int RPold = RP;                               // RP MLAG steps ago
             __syncthreads();
-#define SB16R_MSTEP(PH) \
-            if (t + PH < nsteps) { \
-                SB16R_RPN(t + PH) \
-                { int r4 = s0 + NSW + B * ((t + PH - MLAG) - LAG * (NSW - 1) - 1);      /* RPn of MLAG steps ago */ \
-                  RPold = r4 > n ? n : (r4 < s0 ? s0 : r4); } \
-                mover_step<B, PH>(Lw, AB, n, npad, LP + B * PH, RP, RPn, RPold, ps, lane, pollp, pubp, pw, ptmp, C, status, DIAG, dacc); \
-                if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime(); \
-                RP = RPn; \
-                lds_only_barrier(); \
-                if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; } \
-            }
-            for (int t = 0; t < nsteps; t += 4) {
-                SB16R_MSTEP(0) SB16R_MSTEP(1) SB16R_MSTEP(2) SB16R_MSTEP(3)
-                LP += 4 * B;
-            }
-#undef SB16R_MSTEP
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            LP = s0 + LP0;
+            if (shortp) mover_pass<B, DIAG, W::MLAGS>(Lw, AB, n, npad, s0, nsteps, ps, lane, pollp, pubp, C, status, dacc, pd);
+            else mover_pass<B, DIAG, MLAG>(Lw, AB, n, npad, s0, nsteps, ps, lane, pollp, pubp, C, status, dacc, pd);
         } else {
             // Roles 0 and 1 fetch the tile of their NEXT item at the end of a step, behind their stores: both tiles are final by
             // then (the lag of three leaves the diagonal tile of item k + 1 untouched from the step before item k runs, tools/proto_sbr.py;
@@ -1226,6 +1279,30 @@ __global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad
             const int s4 = s0 + sw;
             const bool live = s4 < n - 2;
             const int xs0 = W::XS + sw * 2 * B;
+            // item g of the wave at step t: sweep s0 + sw, item k4 = t - LAG sw, first row r04 = r04b + B t
+            const int r04b = s4 + 1 - B * LAG * sw;
+            // The steady part [tA, tB) of this wave (uniform): from the step its last sweep starts (k4 >= 0 for all) to the step the tile
+            // of its first sweep's successor leaves the matrix (r04 + B < n for all; the first sweep of the wave is the furthest along).
+            // An empty range (short passes: n - s0 below ~8 LAG RPW) leaves everything to the general body.
+            int tA = nsteps, tB = nsteps;
+            unsigned long long wmask = 0;                 // bit (t & 63): the tile some item of the wave fetches at step t straddles the ring's end
+            if (PHASED) {
+                const int sw0 = RPW * grp, x = n - s0 - 1 - B - sw0 + B * LAG * sw0;
+                tA = LAG * (sw0 + RPW - 1);
+                tB = s0 + sw0 + RPW - 1 < n - 2 && x > 0 ? (x - 1) / B + 1 : 0;
+                if (tB > nsteps) tB = nsteps;
+                if (tA > nsteps) tA = nsteps;
+                if (tB < tA) tB = tA;
+                // the tile fetched at step t has first row r04b + B (t + 1): it wraps when that is 512 - B + 1 .. 511 modulo 512, which
+                // happens (unless the row is a multiple of 8 for every t) at t = 63 - (r04b + B + 512) / 8 modulo 64
+                const int basep = r04b + B + WCOLS;                                  // > 0
+                const int tw = (63 - (basep >> 3)) & 63, wr = (basep & 7) != 0;
+#pragma unroll
+                for (int q = 0; q < RPW; ++q) {
+                    const int twq = __builtin_amdgcn_readlane(tw, B * q), wrq = __builtin_amdgcn_readlane(wr, B * q);
+                    wmask |= (unsigned long long)wrq << twq;
+                }
+            }
             if (role == 0) {
                 double bt[B], v[B], tq = 0.0;
                 int at[B];
@@ -1237,9 +1314,9 @@ __global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad
                     tq = Lw[xs0 + B];
                 }
                 __syncthreads();
-                for (int t = 0; t < nsteps; ++t) {
+                auto general_step = [&](const int t) {
                     if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
-                    const int k4 = t - LAG * sw, r04 = s4 + 1 + B * k4;   // item g of the wave: sweep s0 + sw, item t - 3 sw
+                    const int k4 = t - LAG * sw, r04 = r04b + B * t;   // item g of the wave: sweep s0 + sw, item t - 3 sw
                     const bool act = k4 >= 0 && live && r04 < n, actN = k4 >= -1 && live && r04 + B < n;
                     const int xw = xs0 + (((t + 1) & 1) << 8);
                     if (act) {
@@ -1264,20 +1341,66 @@ __global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad
                     if (__builtin_amdgcn_ballot_w64(actN) != 0) stores_done_barrier<B>();
                     else lds_only_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
+                };
+                for (int t = 0; t < tA; ++t) general_step(t);
+                if (PHASED && tB > tA) {
+                    // a step is plain when neither the tile it updates (fetched the step before) nor the one it fetches wraps
+                    const unsigned long long wm2 = wmask | (wmask << 1) | (wmask >> 63);
+                    int a0 = ((((r04b + B * tA) & (WCOLS - 1)) << WSH) + B + j) * 8;     // next_tile_addr of the item of step tA
+                    int xw = xs0 + (((tA + 1) & 1) << 8);
+                    for (int t = tA; t < tB; ++t) {
+                        if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
+                        if (!((wm2 >> (t & 63)) & 1)) {
+                            int af[B];
+#pragma unroll
+                            for (int i = 0; i < B; ++i) af[i] = a0;
+                            chase4_next<B>(Lw, bt, v, tq, af, j, xw);
+                            a0 = (a0 + STEPB) & (RINGB - 1);
+#pragma unroll
+                            for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
+                            tq = Lw[xw + B];
+#pragma unroll
+                            for (int i = 0; i < B; ++i) bt[i] = ldsb(Lw, a0 + (WR - 1) * 8 * i);
+                            asm volatile("; plain step" ::: "memory");      // two texts: the bodies stay apart (merged, the loads would go
+                        } else {                                             // through eight address registers in both)
+                            int ag[B];
+                            const int r04 = r04b + B * t;
+                            next_tile_addr<B, false>(r04, j, ag);
+                            chase4_next<B>(Lw, bt, v, tq, ag, j, xw);
+                            next_tile_addr<B, false>(r04 + B, j, ag);
+                            a0 = (a0 + STEPB) & (RINGB - 1);
+#pragma unroll
+                            for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
+                            tq = Lw[xw + B];
+#pragma unroll
+                            for (int i = 0; i < B; ++i) bt[i] = ldsb(Lw, ag[i] + (WR - 1) * 8 * i);
+                            asm volatile("; wrapping step" ::: "memory");
+                        }
+                        xw ^= 256;
+                        if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
+                        stores_done_barrier<B>();            // every item has a successor: the loads are behind the stores in both bodies
+                        if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
+                    }
+                    next_tile_addr<B, false>(r04b + B * tB, j, at);      // the tiles fetched in the last steady step, for the general body
                 }
+                for (int t = tB; t < nsteps; ++t) general_step(t);
             } else if (role == 1) {
                 double d[B];
                 int ad[B], offD[B];
-                for (int i = 0; i < B; ++i) { d[i] = 0.0; ad[i] = 0; offD[i] = (i >= j ? (WR - 1) * j + i : (WR - 1) * i + j) * 8; }
+                // formed once per pass from an opaque copy of j: hoisted out of the pass loop, these eight lane constants of one role
+                // would hold registers in all of them, and the phased instance has none to spare beside two workgroups per CU
+                int jo = j;
+                if (PHASED) asm volatile("" : "+v"(jo));
+                for (int i = 0; i < B; ++i) { d[i] = 0.0; ad[i] = 0; offD[i] = (i >= jo ? (WR - 1) * jo + i : (WR - 1) * i + jo) * 8; }
                 if (sw == 0 && live && s4 + 1 < n) {
                     diag_tile_addr<B, false>(s4 + 1, j, offD, ad);
 #pragma unroll
                     for (int i = 0; i < B; ++i) d[i] = ldsb(Lw, ad[i]);
                 }
                 __syncthreads();
-                for (int t = 0; t < nsteps; ++t) {
+                auto general_step = [&](const int t) {
                     if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
-                    const int k4 = t - LAG * sw, r04 = s4 + 1 + B * k4;
+                    const int k4 = t - LAG * sw, r04 = r04b + B * t;
                     const bool act = k4 >= 0 && live && r04 < n, actN = k4 >= -1 && live && r04 + B < n;
                     if (act) chase4_diag<B>(Lw, d, ad, j, xs0 + ((t & 1) << 8), zi, dumpi);
                     const bool wrapN = __builtin_amdgcn_ballot_w64(actN && ((r04 + B) & (WCOLS - 1)) > WCOLS - B) != 0;
@@ -1291,25 +1414,68 @@ __global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad
                     if (__builtin_amdgcn_ballot_w64(actN) != 0) stores_done_barrier<B>();
                     else lds_only_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
+                };
+                for (int t = 0; t < tA; ++t) general_step(t);
+                if (PHASED && tB > tA) {
+                    // ad stays an array here (its offsets offD are lane values, not immediates); what goes is the bookkeeping
+                    int ud = (((r04b + B * tA) & (WCOLS - 1)) << WSH) * 8;               // the diagonal tile's column, item of step tA
+                    int xr = xs0 + ((tA & 1) << 8);
+                    for (int t = tA; t < tB; ++t) {
+                        if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
+                        chase4_diag<B>(Lw, d, ad, j, xr, zi, dumpi);
+                        ud = (ud + STEPB) & (RINGB - 1);
+                        if ((wmask >> (t & 63)) & 1) {
+                            diag_tile_addr<B, false>(r04b + B * (t + 1), j, offD, ad);
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < B; ++i) ad[i] = ud + offD[i];
+                            // the sums are formed HERE: sunk below the join (one add per element, its first operand chosen per body) the
+                            // plain step pays eight moves for them
+                            asm volatile("; plain step" : "+v"(ad[0]), "+v"(ad[1]), "+v"(ad[2]), "+v"(ad[3]), "+v"(ad[4]), "+v"(ad[5]), "+v"(ad[6]), "+v"(ad[7]));
+                        }
+#pragma unroll
+                        for (int i = 0; i < B; ++i) d[i] = ldsb(Lw, ad[i]);
+                        xr ^= 256;
+                        if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
+                        stores_done_barrier<B>();
+                        if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
+                    }
                 }
+                for (int t = tB; t < nsteps; ++t) general_step(t);
             } else {
                 __syncthreads();
-                for (int t = 0; t < nsteps; ++t) {
+                auto general_step = [&](const int t) {
                     if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
-                    const int k4 = t - LAG * sw, r04 = s4 + 1 + B * k4;
+                    const int k4 = t - LAG * sw, r04 = r04b + B * t;
                     if (k4 > 0 && live && r04 < n) chase4_bulge<B>(Lw, r04, r04 - B, j, xs0 + ((t & 1) << 8), dumpi);
                     if (DIAG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
                     lds_only_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
+                };
+                // steady for this role from tA + 1 (k4 > 0 for all); r04 < n follows from r04 + B < n
+                const int tA2 = tA + 1 < tB ? tA + 1 : tB;
+                for (int t = 0; t < tA2; ++t) general_step(t);
+                if (PHASED && tB > tA2) {
+                    int r04 = r04b + B * tA2, xr = xs0 + ((tA2 & 1) << 8);
+                    for (int t = tA2; t < tB; ++t) {
+                        if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
+                        chase4_bulge<B>(Lw, r04, r04 - B, j, xr, dumpi);
+                        r04 += B; xr ^= 256;
+                        if (DIAG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
+                        lds_only_barrier();
+                        if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
+                    }
                 }
+                for (int t = tB; t < nsteps; ++t) general_step(t);
             }
         }
-        if (wv != NCW4 && nsteps > 0) {                   // the chasing waves do not track RP step by step: its value after the last one
-            SB16R_RPN(nsteps - 1)
+        if (nsteps > 0) {                                 // RP after the last step (the chasing waves do not track it step by step)
+            int RPn = s0 + NSW + B * ((nsteps - 1) - LAG * (NSW - 1) - 1);   // columns that left: left of the trailing sweep's tiles
+            if (RPn > n) RPn = n;
+            if (RPn < RP) RPn = RP;
             RP = RPn;
         }
         LP += 4 * B * ((nsteps + 3) / 4);                 // what was requested (far beyond n by the end of a pass)
-#undef SB16R_RPN
         __syncthreads();
         int hi = LP < n ? LP : n;
         for (int idx = tid; idx < (hi - RP) * WR; idx += SB16R_THREADS) {
@@ -1331,6 +1497,23 @@ __global__ __launch_bounds__(SB16R_THREADS) void sbr_rows_kernel(int n, int npad
         ee[jj] = jj < n - 1 ? AB[(size_t)jj * LD + 1] : 0.0;
     }
 }
+
+// The kernels: sbr_rows_kernel is what runs by default (B = 8: the phased loop), sbr_rows_general_kernel<8> the cross-check with one
+// general step loop (BSP_SBR_PHASED=0).  Four waves per SIMD (B = 8: two workgroups of seven waves on a CU) leave a wave 128
+// registers; the compiler is told so, or a few registers more would silently halve the occupancy.
+#define SBR_ROWS_ARGS int n, int npad, int batch, double *__restrict__ ABall, double *__restrict__ dall, double *__restrict__ eall, \
+                      long long *diag, Sb16Ctl *ctl, int P, int *status, int force_abort, int lagmode
+template <int B, bool DIAG = false>
+__global__ __launch_bounds__(SB16R_THREADS) __attribute__((amdgpu_waves_per_eu(B == 8 ? 4 : 2))) void sbr_rows_kernel(SBR_ROWS_ARGS)
+{
+    sbr_rows_body<B, DIAG, B == 8>(n, npad, batch, ABall, dall, eall, diag, ctl, P, status, force_abort, lagmode);
+}
+template <int B, bool DIAG = false>
+__global__ __launch_bounds__(SB16R_THREADS) __attribute__((amdgpu_waves_per_eu(B == 8 ? 4 : 2))) void sbr_rows_general_kernel(SBR_ROWS_ARGS)
+{
+    sbr_rows_body<B, DIAG, false>(n, npad, batch, ABall, dall, eall, diag, ctl, P, status, force_abort, lagmode);
+}
+#undef SBR_ROWS_ARGS
 
 }  // namespace
 
@@ -1380,14 +1563,11 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
     if (!attr) {
         BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sb16st_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     SB16_LDS));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sbr_rows_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Rw<16>::LDS));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sbr_rows_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Rw<8>::LDS));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sbr_rows_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Rw<16>::LDS));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sbr_rows_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Rw<8>::LDS));
+        const void *const rk16[] = {reinterpret_cast<const void *>(sbr_rows_kernel<16, false>), reinterpret_cast<const void *>(sbr_rows_kernel<16, true>)};
+        const void *const rk8[] = {reinterpret_cast<const void *>(sbr_rows_kernel<8, false>), reinterpret_cast<const void *>(sbr_rows_kernel<8, true>),
+                                   reinterpret_cast<const void *>(sbr_rows_general_kernel<8, false>), reinterpret_cast<const void *>(sbr_rows_general_kernel<8, true>)};
+        for (const void *f : rk16) BSP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, Rw<16>::LDS));
+        for (const void *f : rk8) BSP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, Rw<8>::LDS));
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(sbr_rows_kernel<8, false>), SB16R_THREADS,
                                                          Rw<8>::LDS) == hipSuccess && nb >= 1) wg8 = nb > 2 ? 2 : nb;
@@ -1436,26 +1616,30 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
     }
     const int nblk = P > 1 ? ((batch + 7) / 8) * 8 * P : batch;
     const int fab = opts().sb2st_force_abort;
+    const bool phased = opts().sbr_phased != 0;            // tiles of 8 only: the step loop in three parts / the lag of the data-moving wave
+    const int lagmode = opts().sbr_lag;
     auto launch = [&](long long *dbuf) {
         if (rows) hipLaunchKernelGGL(band_tail_zero_kernel, dim3(batch), dim3(256), 0, st, n, npad, 2 * hb, d_AB);
-        if (hb == 8 && dbuf)
-            hipLaunchKernelGGL((sbr_rows_kernel<8, true>), dim3(nblk), dim3(SB16R_THREADS), Rw<8>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf,
-                               d_ctl, P, d_status, fab);
-        else if (hb == 8)
-            hipLaunchKernelGGL((sbr_rows_kernel<8, false>), dim3(nblk), dim3(SB16R_THREADS), Rw<8>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf,
-                               d_ctl, P, d_status, fab);
+#define SBR_LAUNCH(K, ...) hipLaunchKernelGGL((K<__VA_ARGS__>), dim3(nblk), dim3(SB16R_THREADS), Rw<8>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf, \
+                                              d_ctl, P, d_status, fab, lagmode)
+        if (hb == 8 && dbuf && phased) SBR_LAUNCH(sbr_rows_kernel, 8, true);
+        else if (hb == 8 && dbuf) SBR_LAUNCH(sbr_rows_general_kernel, 8, true);
+        else if (hb == 8 && phased) SBR_LAUNCH(sbr_rows_kernel, 8, false);
+        else if (hb == 8) SBR_LAUNCH(sbr_rows_general_kernel, 8, false);
+#undef SBR_LAUNCH
         else if (rows && dbuf)
             hipLaunchKernelGGL((sbr_rows_kernel<16, true>), dim3(nblk), dim3(SB16R_THREADS), Rw<16>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf,
-                               d_ctl, P, d_status, fab);
+                               d_ctl, P, d_status, fab, 1);
         else if (rows)
             hipLaunchKernelGGL((sbr_rows_kernel<16, false>), dim3(nblk), dim3(SB16R_THREADS), Rw<16>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf,
-                               d_ctl, P, d_status, fab);
+                               d_ctl, P, d_status, fab, 1);
         else
             hipLaunchKernelGGL(sb16st_kernel, dim3(nblk), dim3(576), SB16_LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf, d_ctl, P,
                                d_status, fab);
     };
     if (opts().sb2st_diag) {                                // cycles per phase of the chasing waves (workgroup 0)
-        long long *dbuf = nullptr, h[45];
+        static long long h[45 + 4 * SBR_PASSDIAG];
+        long long *dbuf = nullptr;
         BSP_HIP(hipMalloc(reinterpret_cast<void **>(&dbuf), sizeof(h)));
         BSP_HIP(hipMemsetAsync(dbuf, 0, sizeof(h), st));
         launch(dbuf);
@@ -1470,6 +1654,14 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
             fprintf(stderr, "sb16st wave %d: %lld steps; s_memtime ticks per step: chase item %.0f, rest + barrier %.0f (mover wave: columns out %.0f, block in %.0f)\n",
                     w, h[w * 5 + 4], (double)h[w * 5 + 2] / steps, (double)h[w * 5 + 3] / steps, (double)h[w * 5] / steps,
                     (double)h[w * 5 + 1] / steps);
+        }
+        // the passes of workgroup 0 (member 0 of channel 0; rows kernel, tiles of 8 and 16): where a follower waits for its leader, in steps of
+        // the pass's own average length
+        for (int q = 0; q < SBR_PASSDIAG && h[45 + 4 * q] > 0; ++q) {
+            const long long *pq = h + 45 + 4 * q;
+            const double tick = (double)pq[1] / (double)pq[0];
+            fprintf(stderr, "sb16st pass %d of workgroup 0: %lld steps, %.0f ticks per step; waited %.1f steps for its start, %.1f steps in poll check + requests\n",
+                    q, pq[0], tick, (double)pq[3] / tick, (double)pq[2] / tick);
         }
         return BSP_OK;
     }
