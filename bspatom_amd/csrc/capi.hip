@@ -44,6 +44,8 @@ const OptName OPT_TABLE[] = {
     {"bisect_ept", "BSP_BISECT_EPT", &Options::bisect_ept},
     {"bisect_tail", "BSP_BISECT_TAIL", &Options::bisect_tail},
     {"bisect_secant", "BSP_BISECT_SECANT", &Options::bisect_secant},
+    {"bisect_pair", "BSP_BISECT_PAIR", &Options::bisect_pair},
+    {"bisect_diag", "BSP_BISECT_DIAG", &Options::bisect_diag},
     {"no_eigvec_prefetch", "BSP_NO_EIGVEC_PREFETCH", &Options::no_eigvec_prefetch},
     {"vec_early", "BSP_VEC_EARLY", &Options::vec_early},
     {"vec_own_cu", "BSP_VEC_OWN_CU", &Options::vec_own_cu},

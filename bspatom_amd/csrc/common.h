@@ -56,6 +56,9 @@ struct Options {
                                  // (tridiag.hip; ~22 rounds instead of ~50); 0 = bisection only; >= 2: as 1, and the value is the
                                  // fraction of a workgroup's 1024 eigenvalues (1 / value) left to the multisection tail (1 = 8)
     int bisect_tail = 1;         // BSP_BISECT_TAIL: 0 = lock-step bisection to the end (no multisection tail), for A/B timing
+    int bisect_pair = 1;         // BSP_BISECT_PAIR: a workgroup of bisect3_kernel runs two logical workgroups of its channel, x and x + ceil(nw / 2),
+                                 // one after the other -- 1 = when there are more workgroups than CUs, 0 = never, 2 = always; bit-identical results
+    int bisect_diag = 0;         // BSP_BISECT_DIAG: instrumented bisect3_kernel: placement, wall-clock stamps and rounds of every workgroup (stderr)
     int no_eigvec_prefetch = 0;
     int vec_early = 1;           // BSP_VEC_EARLY: band route, the consumed eigenvector's eigenvalue from the pencil's inertia right after the assembly (bandsect.hip); 0: from the tridiagonal matrix at the end; 2: as 1 with the check made to fail
     int vec_own_cu = 1;          // BSP_VEC_OWN_CU: the early vector's workgroup asks for a CU's whole LDS (eigvec.hip::early_vector_kernel) -- 1: for batches of more than 32 channels (capi.hip), 2: always, 0: never

@@ -351,6 +351,12 @@ __device__ __forceinline__ bool bracket_final(double lo, double hi)
     return (mid <= lo) || (mid >= hi) || (hi - lo <= 2.0 * 2.220446049250313e-16 * fmax(fabs(lo), fabs(hi)) + 1e-300);
 }
 
+// a value that is the same in every lane, moved to scalar registers (bit for bit)
+__device__ __forceinline__ double uniform_double(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
 // dynamic LDS of bisect3_kernel<EPT, TPB> for n rows (ng = TPB * EPT evaluation slots)
 static size_t bisect3_lds_bytes(int n, int ng)
 {
@@ -360,11 +366,21 @@ static size_t bisect3_lds_bytes(int n, int ng)
 
 // TPB threads per workgroup: 512 = two waves per SIMD sharing one LDS copy of the matrix (one wave per SIMD reaches
 // only ~60 % of the fp64 vector rate: tools/microbench/mfma_f64_peak, v_fma_f64 line)
-template <int EPT, int TPB>
+//
+// pair_stride > 0: the workgroup runs TWO logical workgroups of its channel one after the other, bx = blockIdx.x and bx + pair_stride
+// (the second only if it exists), on one set-up: the quarters of a spectrum do not cost the same (the one next to zero takes 1.5 x the
+// rounds of the middle ones, tools/sim_bisect_rounds.py) and a grid of more workgroups than CUs left the placement of slow beside
+// slow to the dispatcher.  A logical workgroup keeps its slots, its slot-to-eigenvalue map and its tail list, so every
+// eigenvalue sees the same points in the same order: the spectra do not depend on pair_stride, bit for bit.
+// DIAG: the instrumented instance (BSP_BISECT_DIAG; `diag` non-null): a record per logical workgroup; the other carries no stamp, no
+// test for one.
+constexpr int BISECT_DIAG_WORDS = 8;   // x, channel, HW_REG_XCC_ID, HW_REG_HW_ID, wall clock at its start and end, lock-step rounds, tail rounds
+template <int EPT, int TPB, bool DIAG = false>
 __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const double *__restrict__ dall,
                                                      const double *__restrict__ eall, double *wall, long ldw, int tail,
-                                                     double2 *gtail, int nl, int hybrid_arg)
+                                                     double2 *gtail, int nl, int hybrid_arg, int pair_stride, long long *diag)
 {
+    long long dt0 = DIAG ? (long long)wall_clock64() : 0;
     // (eight eigenvalues per thread, BSP_BISECT_EPT=8, an A/B of round 1: plain bisection -- the secant rounds' state does not fit its registers)
     const int hybrid = EPT > 4 ? 0 : hybrid_arg;
     extern __shared__ double2 sde[];
@@ -383,14 +399,14 @@ __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const doub
     int *lm = cg + NG;
     __shared__ double red[2 * NW];
     __shared__ int sK;
-    const int tid = threadIdx.x;
+    const int tid0 = threadIdx.x;
     const size_t ch = blockIdx.y;
     const double *dg = dall + ch * (size_t)ldn, *eg = eall + ch * (size_t)ldn;
     double *wout = wall + ch * (size_t)ldw;
     // the rows that do not fit the LDS: every workgroup of a channel writes the same values to the channel's slice
     double2 *gt = gtail ? gtail + ch * (size_t)(np + 1) : nullptr;
     double gl = 1e300, gu = -1e300;
-    for (int i = tid; i < n; i += TPB) {
+    for (int i = tid0; i < n; i += TPB) {
         const double di = dg[i];
         const double el = (i > 0) ? fabs(eg[i - 1]) : 0.0;
         const double er = (i < n - 1) ? fabs(eg[i]) : 0.0;
@@ -402,7 +418,7 @@ __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const doub
         gl = fmin(gl, __shfl_xor(gl, off));
         gu = fmax(gu, __shfl_xor(gu, off));
     }
-    if ((tid & 63) == 0) { red[tid >> 6] = gl; red[NW + (tid >> 6)] = gu; }
+    if ((tid0 & 63) == 0) { red[tid0 >> 6] = gl; red[NW + (tid0 >> 6)] = gu; }
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < NW; ++q) { gl = fmin(gl, red[q]); gu = fmax(gu, red[NW + q]); }
@@ -411,8 +427,8 @@ __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const doub
     if (!(tnorm > 0.0)) tnorm = 1.0;                   // the zero matrix
     int kexp;
     (void)frexp(tnorm, &kexp);                         // tnorm = f 2^kexp, f in [0.5, 1)
-    const double sc = ldexp(1.0, -kexp), isc = ldexp(1.0, kexp);
-    for (int i = tid; i <= np; i += TPB) {
+    const double sc = ldexp(1.0, -kexp), isc_v = ldexp(1.0, kexp);
+    for (int i = tid0; i <= np; i += TPB) {
         // row i of the scaled matrix with its coupling to row i-1.  Padding rows: d = 2, coupling at the floor.
         const double di = (i < n) ? dg[i] * sc : 2.0;
         const double ev = (i >= 1 && i < n) ? (eg[i - 1] * sc) : 0.0;
@@ -424,226 +440,256 @@ __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const doub
     gl = gl * sc - 2.1 * eps * n - 1e-300;             // scaled Gershgorin interval, widened as dstebz does
     gu = gu * sc + 2.1 * eps * n + 1e-300;
 
-    const int mbase = blockIdx.x * NG + tid;           // eigenvalue indices mbase + TPB c
-    double lo[EPT], hi[EPT];
-    int clo[EPT], chi[EPT];                            // count(lo) <= m < count(hi): the bracket is ISOLATING when chi - clo = 1
-    float lflo[EPT], lfhi[EPT];                        // log2 |p_n| at the ends (3e38: not known)
-    if (!hybrid) {
-        // first level: NG interior points x_j = gl + (gu - gl) (j+1)/(NG+1), j = tid + TPB c
-        const double w = gu - gl;
-        double xg[EPT];
-        int cc[EPT];
+    // the same in every lane, and live through both items: in scalar registers
+    gl = uniform_double(gl); gu = uniform_double(gu);
+    const double isc = uniform_double(isc_v);
+    const int nwl = (n + NG - 1) / NG;                 // logical workgroups of a channel
+#pragma unroll 1
+    for (int item = 0; item < 2; ++item) {
+        const int bx = blockIdx.x + item * pair_stride;    // the logical workgroup: eigenvalues bx NG .. bx NG + NG - 1
+        if (item) {
+            if (pair_stride == 0 || bx >= nwl) break;
+            __syncthreads();                               // the first one's last reads of its tail list: the slot arrays are used again
+            if (DIAG) dt0 = (long long)wall_clock64();
+        }
+        int drounds = 0, dtail = 0;
+        // the thread's number, opaque to the compiler: the slot addresses it forms from it are the same for both items, and hoisted in front
+        // of the loop they stayed live through it (20 registers: the kernel left its 128, and with them two workgroups per CU)
+        int tid = tid0;
+        asm volatile("" : "+v"(tid));
+        const int mbase = bx * NG + tid;                   // eigenvalue indices mbase + TPB c
+        double lo[EPT], hi[EPT];
+        int clo[EPT], chi[EPT];                            // count(lo) <= m < count(hi): the bracket is ISOLATING when chi - clo = 1
+        float lflo[EPT], lfhi[EPT];                        // log2 |p_n| at the ends (3e38: not known)
+        if (!hybrid) {
+            // first level: NG interior points x_j = gl + (gu - gl) (j+1)/(NG+1), j = tid + TPB c
+            const double w = gu - gl;
+            double xg[EPT];
+            int cc[EPT];
 #pragma unroll
-        for (int c = 0; c < EPT; ++c) xg[c] = gl + w * ((double)(tid + TPB * c + 1) * (1.0 / (NG + 1)));
-        sturm_counts3<EPT>(de, np, xg, cc, gt, nlr);
+            for (int c = 0; c < EPT; ++c) xg[c] = gl + w * ((double)(tid + TPB * c + 1) * (1.0 / (NG + 1)));
+            if (DIAG) ++drounds;
+            sturm_counts3<EPT>(de, np, xg, cc, gt, nlr);
 #pragma unroll
-        for (int c = 0; c < EPT; ++c) cg[tid + TPB * c] = cc[c];
+            for (int c = 0; c < EPT; ++c) cg[tid + TPB * c] = cc[c];
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < EPT; ++c) {
+                const int m = mbase + TPB * c;
+                int L = -1, R = NG;                        // count(x_L) <= m < count(x_R), with x_{-1} = gl, x_NG = gu
+                while (R - L > 1) {
+                    const int mid = (L + R) >> 1;
+                    if (cg[mid] > m) R = mid; else L = mid;
+                }
+                lo[c] = (L < 0) ? gl : gl + w * ((double)(L + 1) * (1.0 / (NG + 1)));
+                hi[c] = (R >= NG) ? gu : gl + w * ((double)(R + 1) * (1.0 / (NG + 1)));
+                clo[c] = (L < 0) ? 0 : cg[L];
+                chi[c] = (R >= NG) ? n : cg[R];
+            }
+        }
+        bool done[EPT];
+        if (hybrid) {
+            // Lock-step rounds with a SAFEGUARDED SECANT step (round 4).  The Sturm recurrence delivers p_n(x) with its count: once a
+            // bracket holds ONE eigenvalue (chi - clo = 1) and p_n is known at both ends, the next point is the regula falsi estimate
+            //   x = lo + (hi - lo) r / (1 + r),  r = |p_n(lo)| / |p_n(hi)| = 2^(lflo - lfhi),
+            // in its Illinois form: an end that survives two estimates in a row has its value halved, so both ends close in on the
+            // eigenvalue (superlinearly) and the bracket itself collapses.  The COUNT alone decides which end a point replaces (the
+            // invariant count(lo) <= m < count(hi) never rests on the value), three rounds that have not halved the bracket between
+            // them are followed by a bisection, and the stopping rule is the bisection's: the result is a point of a bracket
+            // narrower than 2 eps |x|, as before -- after ~19 evaluations instead of ~49 (tools/sim_secant.py on C4's spectra: 99 %
+            // within 25; single precision in log2 |p_n| costs nothing).
+            //
+            // SHARED POINTS: while a bracket still holds several eigenvalues of this workgroup -- numbers a .. b - 1, q = b - a of them;
+            // they all carry the same bracket -- eigenvalue a + r takes point r + 1 of q + 1 equal parts of it, every point of the round
+            // goes to LDS with its count and its log2 |p_n| (slot = eigenvalue number, so a bracket's points are the slots a .. b - 1, in
+            // ascending order), and every one of the q eigenvalues takes the tightest bracket that ALL q counts allow: the bracket
+            // shrinks q + 1 fold where the midpoint halved it.  The first level (everything in the Gershgorin interval: a uniform grid
+            // of NG points) is the first round of the same rule; on the graded spectra of the B-spline pencils, where a tenth of that
+            // grid's cells hold all the eigenvalues, the next two rounds do what took ten bisections (tools/sim_grid.py: 11 - 15
+            // evaluations per eigenvalue instead of 17 - 19).  Any point with count <= m is a lower end for eigenvalue m and any with
+            // count > m an upper end, whoever evaluated it: nothing rests on the brackets of a cell being the same or on the counts
+            // being monotone -- a point is taken if it lies strictly inside the bracket the eigenvalue's OWN point has left.
+            double *xs = llo;                              // the round's points, by slot (the tail's list and counts reuse the bytes)
+            float *lfs = (float *)(xs + NG);
+            unsigned short *cs = (unsigned short *)(lfs + NG);       // n <= 65535 (launch_bisect)
+            const int m0 = bx * NG, m1 = min(m0 + NG, n);
+            float wref[EPT];                              // the bracket's width when it last halved
+            int st[EPT];                                  // bits 0-1: the end the last estimate replaced (1 hi, 2 lo); bits 2..: rounds since wref
+#pragma unroll
+            for (int c = 0; c < EPT; ++c) {
+                wref[c] = 3e38f; st[c] = 0;
+                lo[c] = gl; hi[c] = gu; clo[c] = 0; chi[c] = n; lflo[c] = 3e38f; lfhi[c] = 3e38f;
+            }
+            for (int it = 0; it < 200; ++it) {
+                double x[EPT];
+                bool sec[EPT];
+                int rng[EPT];                             // shared point: slots s0 | s1 << 16 of the bracket's points, else 0
+#pragma unroll
+                for (int c = 0; c < EPT; ++c) {
+                    const int m = mbase + TPB * c;
+                    const double wd = hi[c] - lo[c];
+                    done[c] = (m >= n) || bracket_final(lo[c], hi[c]);
+                    if ((float)wd <= 0.5f * wref[c]) { wref[c] = (float)wd; st[c] &= 3; }
+                    const bool slow = (st[c] >> 2) >= 3;
+                    st[c] += 4;
+                    x[c] = 0.5 * (lo[c] + hi[c]); sec[c] = false; rng[c] = 0;
+                    const int a = max(clo[c], m0), b = min(chi[c], m1);
+                    if (chi[c] - clo[c] == 1 && lflo[c] < 1e38f && lfhi[c] < 1e38f && !slow && !done[c]) {
+                        const double tiny = 2.0 * 2.220446049250313e-16 * fmax(fabs(lo[c]), fabs(hi[c]));
+                        const float dl = fminf(fmaxf(lflo[c] - lfhi[c], -60.0f), 60.0f);
+                        const double r = (double)exp2f(dl);
+                        const double xe = fmin(fmax(lo[c] + wd * (r / (1.0 + r)), lo[c] + tiny), hi[c] - tiny);
+                        if (xe > lo[c] && xe < hi[c]) { x[c] = xe; sec[c] = true; }
+                    } else if (b - a > 1 && m >= a && m < b && !slow && !done[c]) {
+                        const double xq = msect_point(lo[c], wd, m - a, 1.0 / (double)(b - a + 1));
+                        if (xq > lo[c] && xq < hi[c]) { x[c] = xq; rng[c] = (a - m0) | ((b - m0) << 16); }
+                    }
+                }
+                // on to the multisection tail once few enough brackets are left for it to have many points in each (NG / hybrid slots:
+                // the stragglers of these rounds are brackets that are still WIDE, and the tail shrinks a bracket by P + 1 per round)
+                int tot = 0;
+#pragma unroll
+                for (int c = 0; c < EPT; ++c) tot += __syncthreads_count(!done[c]);     // (and: last round's reads of xs, cs, lfs are over)
+                if (tot <= (tail ? NG / hybrid : 0)) break;
+                int cnt[EPT];
+                float lf[EPT];
+                if (DIAG) ++drounds;
+                sturm_counts3<EPT, true>(de, np, x, cnt, gt, nlr, lf);
+#pragma unroll
+                for (int c = 0; c < EPT; ++c) {
+                    xs[tid + TPB * c] = x[c]; cs[tid + TPB * c] = (unsigned short)cnt[c]; lfs[tid + TPB * c] = lf[c];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int c = 0; c < EPT; ++c) {
+                    if (done[c]) continue;
+                    const int m = mbase + TPB * c;
+                    const bool up = cnt[c] > m;                                    // x is above eigenvalue m: it replaces hi
+                    const int last = st[c] & 3;
+                    if (up) {
+                        hi[c] = x[c]; chi[c] = cnt[c]; lfhi[c] = lf[c];
+                        if (sec[c] && last == 1 && lflo[c] < 1e38f) lflo[c] -= 1.0f;   // Illinois: lo survived two estimates
+                    } else {
+                        lo[c] = x[c]; clo[c] = cnt[c]; lflo[c] = lf[c];
+                        if (sec[c] && last == 2 && lfhi[c] < 1e38f) lfhi[c] -= 1.0f;
+                    }
+                    st[c] = (st[c] & ~3) | (sec[c] ? (up ? 1 : 2) : 0);
+                    if (rng[c]) {
+                        // the other points of the bracket: L = the last slot before R with count <= m, R = the first found with count > m
+                        // (the search's own tests guarantee both counts; -1 / s1: none)
+                        const int s0 = rng[c] & 0xffff, s1 = rng[c] >> 16;
+                        int L = s0 - 1, R = s1;
+                        while (R - L > 1) {
+                            const int mid = (L + R) >> 1;
+                            if ((int)cs[mid] > m) R = mid; else L = mid;
+                        }
+                        if (R < s1) { const double xr = xs[R]; if (xr > lo[c] && xr < hi[c]) { hi[c] = xr; chi[c] = cs[R]; lfhi[c] = lfs[R]; } }
+                        if (L >= s0) { const double xl = xs[L]; if (xl > lo[c] && xl < hi[c]) { lo[c] = xl; clo[c] = cs[L]; lflo[c] = lfs[L]; } }
+                    }
+                }
+            }
+            __syncthreads();                               // the tail's list goes where the points were
+        } else
+        // lock-step bisection until every thread has at most EPT/2 unfinished eigenvalues (<= KC in the workgroup)
+        for (int it = 0; it < 160; ++it) {
+            double mid[EPT];
+            int nun = 0;
+#pragma unroll
+            for (int c = 0; c < EPT; ++c) {
+                mid[c] = 0.5 * (lo[c] + hi[c]);
+                done[c] = (mbase + TPB * c >= n) || bracket_final(lo[c], hi[c]);
+                nun += done[c] ? 0 : 1;
+            }
+            if (!__syncthreads_or(nun > (tail ? EPT / 2 : 0))) break;
+            int cnt[EPT];
+            if (DIAG) ++drounds;
+            sturm_counts3<EPT>(de, np, mid, cnt, gt, nlr);
+#pragma unroll
+            for (int c = 0; c < EPT; ++c) {
+                if (!done[c]) {
+                    if (cnt[c] > mbase + TPB * c) hi[c] = mid[c]; else lo[c] = mid[c];
+                }
+            }
+        }
+        // the tail: compact the unfinished into the list, store the finished
+        if (tid == 0) sK = 0;
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < EPT; ++c) {
             const int m = mbase + TPB * c;
-            int L = -1, R = NG;                        // count(x_L) <= m < count(x_R), with x_{-1} = gl, x_NG = gu
-            while (R - L > 1) {
-                const int mid = (L + R) >> 1;
-                if (cg[mid] > m) R = mid; else L = mid;
-            }
-            lo[c] = (L < 0) ? gl : gl + w * ((double)(L + 1) * (1.0 / (NG + 1)));
-            hi[c] = (R >= NG) ? gu : gl + w * ((double)(R + 1) * (1.0 / (NG + 1)));
-            clo[c] = (L < 0) ? 0 : cg[L];
-            chi[c] = (R >= NG) ? n : cg[R];
+            done[c] = (m >= n) || bracket_final(lo[c], hi[c]);
+            if (!done[c]) {
+                const int pos = atomicAdd(&sK, 1);
+                if (pos < kcap) { llo[pos] = lo[c]; lhi[pos] = hi[c]; lm[pos] = m; }
+                else wout[m] = 0.5 * (lo[c] + hi[c]) * isc;      // cannot happen (<= EPT/2 per thread); never lose a value
+            } else if (m < n) wout[m] = 0.5 * (lo[c] + hi[c]) * isc;
         }
-    }
-    bool done[EPT];
-    if (hybrid) {
-        // Lock-step rounds with a SAFEGUARDED SECANT step (round 4).  The Sturm recurrence delivers p_n(x) with its count: once a
-        // bracket holds ONE eigenvalue (chi - clo = 1) and p_n is known at both ends, the next point is the regula falsi estimate
-        //   x = lo + (hi - lo) r / (1 + r),  r = |p_n(lo)| / |p_n(hi)| = 2^(lflo - lfhi),
-        // in its Illinois form: an end that survives two estimates in a row has its value halved, so both ends close in on the
-        // eigenvalue (superlinearly) and the bracket itself collapses.  The COUNT alone decides which end a point replaces (the
-        // invariant count(lo) <= m < count(hi) never rests on the value), three rounds that have not halved the bracket between
-        // them are followed by a bisection, and the stopping rule is the bisection's: the result is a point of a bracket
-        // narrower than 2 eps |x|, as before -- after ~19 evaluations instead of ~49 (tools/sim_secant.py on C4's spectra: 99 %
-        // within 25; single precision in log2 |p_n| costs nothing).
-        //
-        // SHARED POINTS: while a bracket still holds several eigenvalues of this workgroup -- numbers a .. b - 1, q = b - a of them;
-        // they all carry the same bracket -- eigenvalue a + r takes point r + 1 of q + 1 equal parts of it, every point of the round
-        // goes to LDS with its count and its log2 |p_n| (slot = eigenvalue number, so a bracket's points are the slots a .. b - 1, in
-        // ascending order), and every one of the q eigenvalues takes the tightest bracket that ALL q counts allow: the bracket
-        // shrinks q + 1 fold where the midpoint halved it.  The first level (everything in the Gershgorin interval: a uniform grid
-        // of NG points) is the first round of the same rule; on the graded spectra of the B-spline pencils, where a tenth of that
-        // grid's cells hold all the eigenvalues, the next two rounds do what took ten bisections (tools/sim_grid.py: 11 - 15
-        // evaluations per eigenvalue instead of 17 - 19).  Any point with count <= m is a lower end for eigenvalue m and any with
-        // count > m an upper end, whoever evaluated it: nothing rests on the brackets of a cell being the same or on the counts
-        // being monotone -- a point is taken if it lies strictly inside the bracket the eigenvalue's OWN point has left.
-        double *xs = llo;                              // the round's points, by slot (the tail's list and counts reuse the bytes)
-        float *lfs = (float *)(xs + NG);
-        unsigned short *cs = (unsigned short *)(lfs + NG);       // n <= 65535 (launch_bisect)
-        const int m0 = blockIdx.x * NG, m1 = min(m0 + NG, n);
-        float wref[EPT];                              // the bracket's width when it last halved
-        int st[EPT];                                  // bits 0-1: the end the last estimate replaced (1 hi, 2 lo); bits 2..: rounds since wref
-#pragma unroll
-        for (int c = 0; c < EPT; ++c) {
-            wref[c] = 3e38f; st[c] = 0;
-            lo[c] = gl; hi[c] = gu; clo[c] = 0; chi[c] = n; lflo[c] = 3e38f; lfhi[c] = 3e38f;
-        }
-        for (int it = 0; it < 200; ++it) {
+        __syncthreads();
+        for (int round = 0; round < 128; ++round) {
+            const int K = min(sK, kcap);                   // uniform: written before the last barrier
+            if (K == 0) break;
+            const int P = NG / K;                          // >= 2 points inside every bracket
+            const double rp = 1.0 / (double)(P + 1);
             double x[EPT];
-            bool sec[EPT];
-            int rng[EPT];                             // shared point: slots s0 | s1 << 16 of the bracket's points, else 0
+            int cc[EPT];
 #pragma unroll
             for (int c = 0; c < EPT; ++c) {
-                const int m = mbase + TPB * c;
-                const double wd = hi[c] - lo[c];
-                done[c] = (m >= n) || bracket_final(lo[c], hi[c]);
-                if ((float)wd <= 0.5f * wref[c]) { wref[c] = (float)wd; st[c] &= 3; }
-                const bool slow = (st[c] >> 2) >= 3;
-                st[c] += 4;
-                x[c] = 0.5 * (lo[c] + hi[c]); sec[c] = false; rng[c] = 0;
-                const int a = max(clo[c], m0), b = min(chi[c], m1);
-                if (chi[c] - clo[c] == 1 && lflo[c] < 1e38f && lfhi[c] < 1e38f && !slow && !done[c]) {
-                    const double tiny = 2.0 * 2.220446049250313e-16 * fmax(fabs(lo[c]), fabs(hi[c]));
-                    const float dl = fminf(fmaxf(lflo[c] - lfhi[c], -60.0f), 60.0f);
-                    const double r = (double)exp2f(dl);
-                    const double xe = fmin(fmax(lo[c] + wd * (r / (1.0 + r)), lo[c] + tiny), hi[c] - tiny);
-                    if (xe > lo[c] && xe < hi[c]) { x[c] = xe; sec[c] = true; }
-                } else if (b - a > 1 && m >= a && m < b && !slow && !done[c]) {
-                    const double xq = msect_point(lo[c], wd, m - a, 1.0 / (double)(b - a + 1));
-                    if (xq > lo[c] && xq < hi[c]) { x[c] = xq; rng[c] = (a - m0) | ((b - m0) << 16); }
-                }
+                const int s = tid + TPB * c, e = s / P, q = s - e * P;
+                x[c] = 2.0;                                // idle slot: a point above the spectrum
+                if (e < K) { const double a = llo[e]; x[c] = msect_point(a, lhi[e] - a, q, rp); }
             }
-            // on to the multisection tail once few enough brackets are left for it to have many points in each (NG / hybrid slots:
-            // the stragglers of these rounds are brackets that are still WIDE, and the tail shrinks a bracket by P + 1 per round)
-            int tot = 0;
+            if (DIAG) ++dtail;
+            sturm_counts3<EPT>(de, np, x, cc, gt, nlr);
 #pragma unroll
-            for (int c = 0; c < EPT; ++c) tot += __syncthreads_count(!done[c]);     // (and: last round's reads of xs, cs, lfs are over)
-            if (tot <= (tail ? NG / hybrid : 0)) break;
-            int cnt[EPT];
-            float lf[EPT];
-            sturm_counts3<EPT, true>(de, np, x, cnt, gt, nlr, lf);
-#pragma unroll
-            for (int c = 0; c < EPT; ++c) {
-                xs[tid + TPB * c] = x[c]; cs[tid + TPB * c] = (unsigned short)cnt[c]; lfs[tid + TPB * c] = lf[c];
-            }
+            for (int c = 0; c < EPT; ++c) cg[tid + TPB * c] = cc[c];
             __syncthreads();
+            double nlo[EPT / 2], nhi[EPT / 2];
+            int nm[EPT / 2];
+            bool keep[EPT / 2];
 #pragma unroll
-            for (int c = 0; c < EPT; ++c) {
-                if (done[c]) continue;
-                const int m = mbase + TPB * c;
-                const bool up = cnt[c] > m;                                    // x is above eigenvalue m: it replaces hi
-                const int last = st[c] & 3;
-                if (up) {
-                    hi[c] = x[c]; chi[c] = cnt[c]; lfhi[c] = lf[c];
-                    if (sec[c] && last == 1 && lflo[c] < 1e38f) lflo[c] -= 1.0f;   // Illinois: lo survived two estimates
-                } else {
-                    lo[c] = x[c]; clo[c] = cnt[c]; lflo[c] = lf[c];
-                    if (sec[c] && last == 2 && lfhi[c] < 1e38f) lfhi[c] -= 1.0f;
-                }
-                st[c] = (st[c] & ~3) | (sec[c] ? (up ? 1 : 2) : 0);
-                if (rng[c]) {
-                    // the other points of the bracket: L = the last slot before R with count <= m, R = the first found with count > m
-                    // (the search's own tests guarantee both counts; -1 / s1: none)
-                    const int s0 = rng[c] & 0xffff, s1 = rng[c] >> 16;
-                    int L = s0 - 1, R = s1;
+            for (int j = 0; j < EPT / 2; ++j) {
+                const int e = tid + TPB * j;
+                keep[j] = false;
+                if (e < K) {
+                    const double a = llo[e], b = lhi[e], w = b - a;
+                    const int m = lm[e];
+                    const int *ce = cg + e * P;
+                    int L = -1, R = P;                     // count(point L) <= m < count(point R); -1 = a, P = b
                     while (R - L > 1) {
                         const int mid = (L + R) >> 1;
-                        if ((int)cs[mid] > m) R = mid; else L = mid;
+                        if (ce[mid] > m) R = mid; else L = mid;
                     }
-                    if (R < s1) { const double xr = xs[R]; if (xr > lo[c] && xr < hi[c]) { hi[c] = xr; chi[c] = cs[R]; lfhi[c] = lfs[R]; } }
-                    if (L >= s0) { const double xl = xs[L]; if (xl > lo[c] && xl < hi[c]) { lo[c] = xl; clo[c] = cs[L]; lflo[c] = lfs[L]; } }
+                    nlo[j] = (L < 0) ? a : msect_point(a, w, L, rp);
+                    nhi[j] = (R >= P) ? b : msect_point(a, w, R, rp);
+                    nm[j] = m;
+                    if (bracket_final(nlo[j], nhi[j]) || !(nhi[j] - nlo[j] < w)) wout[m] = 0.5 * (nlo[j] + nhi[j]) * isc;
+                    else keep[j] = true;
                 }
             }
-        }
-        __syncthreads();                               // the tail's list goes where the points were
-    } else
-    // lock-step bisection until every thread has at most EPT/2 unfinished eigenvalues (<= KC in the workgroup)
-    for (int it = 0; it < 160; ++it) {
-        double mid[EPT];
-        int nun = 0;
+            __syncthreads();                               // every read of the list and of cg is done
+            if (tid == 0) sK = 0;
+            __syncthreads();
 #pragma unroll
-        for (int c = 0; c < EPT; ++c) {
-            mid[c] = 0.5 * (lo[c] + hi[c]);
-            done[c] = (mbase + TPB * c >= n) || bracket_final(lo[c], hi[c]);
-            nun += done[c] ? 0 : 1;
-        }
-        if (!__syncthreads_or(nun > (tail ? EPT / 2 : 0))) break;
-        int cnt[EPT];
-        sturm_counts3<EPT>(de, np, mid, cnt, gt, nlr);
-#pragma unroll
-        for (int c = 0; c < EPT; ++c) {
-            if (!done[c]) {
-                if (cnt[c] > mbase + TPB * c) hi[c] = mid[c]; else lo[c] = mid[c];
-            }
-        }
-    }
-    // the tail: compact the unfinished into the list, store the finished
-    if (tid == 0) sK = 0;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < EPT; ++c) {
-        const int m = mbase + TPB * c;
-        done[c] = (m >= n) || bracket_final(lo[c], hi[c]);
-        if (!done[c]) {
-            const int pos = atomicAdd(&sK, 1);
-            if (pos < kcap) { llo[pos] = lo[c]; lhi[pos] = hi[c]; lm[pos] = m; }
-            else wout[m] = 0.5 * (lo[c] + hi[c]) * isc;      // cannot happen (<= EPT/2 per thread); never lose a value
-        } else if (m < n) wout[m] = 0.5 * (lo[c] + hi[c]) * isc;
-    }
-    __syncthreads();
-    for (int round = 0; round < 128; ++round) {
-        const int K = min(sK, kcap);                   // uniform: written before the last barrier
-        if (K == 0) break;
-        const int P = NG / K;                          // >= 2 points inside every bracket
-        const double rp = 1.0 / (double)(P + 1);
-        double x[EPT];
-        int cc[EPT];
-#pragma unroll
-        for (int c = 0; c < EPT; ++c) {
-            const int s = tid + TPB * c, e = s / P, q = s - e * P;
-            x[c] = 2.0;                                // idle slot: a point above the spectrum
-            if (e < K) { const double a = llo[e]; x[c] = msect_point(a, lhi[e] - a, q, rp); }
-        }
-        sturm_counts3<EPT>(de, np, x, cc, gt, nlr);
-#pragma unroll
-        for (int c = 0; c < EPT; ++c) cg[tid + TPB * c] = cc[c];
-        __syncthreads();
-        double nlo[EPT / 2], nhi[EPT / 2];
-        int nm[EPT / 2];
-        bool keep[EPT / 2];
-#pragma unroll
-        for (int j = 0; j < EPT / 2; ++j) {
-            const int e = tid + TPB * j;
-            keep[j] = false;
-            if (e < K) {
-                const double a = llo[e], b = lhi[e], w = b - a;
-                const int m = lm[e];
-                const int *ce = cg + e * P;
-                int L = -1, R = P;                     // count(point L) <= m < count(point R); -1 = a, P = b
-                while (R - L > 1) {
-                    const int mid = (L + R) >> 1;
-                    if (ce[mid] > m) R = mid; else L = mid;
+            for (int j = 0; j < EPT / 2; ++j) {
+                if (keep[j]) {
+                    const int pos = atomicAdd(&sK, 1);
+                    llo[pos] = nlo[j]; lhi[pos] = nhi[j]; lm[pos] = nm[j];
                 }
-                nlo[j] = (L < 0) ? a : msect_point(a, w, L, rp);
-                nhi[j] = (R >= P) ? b : msect_point(a, w, R, rp);
-                nm[j] = m;
-                if (bracket_final(nlo[j], nhi[j]) || !(nhi[j] - nlo[j] < w)) wout[m] = 0.5 * (nlo[j] + nhi[j]) * isc;
-                else keep[j] = true;
             }
+            __syncthreads();
         }
-        __syncthreads();                               // every read of the list and of cg is done
-        if (tid == 0) sK = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < EPT / 2; ++j) {
-            if (keep[j]) {
-                const int pos = atomicAdd(&sK, 1);
-                llo[pos] = nlo[j]; lhi[pos] = nhi[j]; lm[pos] = nm[j];
-            }
+        {   // round limit (not reached: every round shrinks every bracket): store what is left
+            const int K = min(sK, kcap);
+            for (int e = tid; e < K; e += TPB) wout[lm[e]] = 0.5 * (llo[e] + lhi[e]) * isc;
         }
-        __syncthreads();
-    }
-    {   // round limit (not reached: every round shrinks every bracket): store what is left
-        const int K = min(sK, kcap);
-        for (int e = tid; e < K; e += TPB) wout[lm[e]] = 0.5 * (llo[e] + lhi[e]) * isc;
+        if (DIAG && tid == 0) {
+            long long *rec = diag + (ch * (size_t)nwl + bx) * BISECT_DIAG_WORDS;
+            rec[0] = bx; rec[1] = (long long)ch;
+            rec[2] = (long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xfu);      // HW_REG_XCC_ID
+            rec[3] = (long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_REG_HW_ID: CU bits 8-11, SH 12, SE 13-15
+            rec[4] = dt0; rec[5] = (long long)wall_clock64();
+            rec[6] = drounds; rec[7] = dtail;
+        }
     }
 }
 
@@ -875,24 +921,75 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
         BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
         attr_set = true;
     }
     const dim3 grid((n + 256 * EPT - 1) / (256 * EPT), batch);
-    KScope kt(KS_BISECT, st);
-    if (variant == 1) hipLaunchKernelGGL(bisect_kernel, grid, dim3(256), lds, st, n, ldn, d_d, d_e, d_w, ldw);
-    else if (variant == 2) hipLaunchKernelGGL(bisect2_kernel, grid, dim3(256), lds, st, n, ldn, d_d, d_e, d_w, ldw);
-    else {
-        const dim3 g3((n + ng - 1) / ng, batch);
-        const int tail = opts().bisect_tail;
-        // (the secant rounds keep a point's count in 16 bits: beyond that size plain bisection)
-        const int hyb = n > 65535 ? 0 : (opts().bisect_secant == 1 ? 8 : (opts().bisect_secant >= 4 ? opts().bisect_secant : (opts().bisect_secant >= 2 ? 4 : 0)));
-        if (mode == 512) hipLaunchKernelGGL((bisect3_kernel<4, 512>), g3, dim3(512), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb);
-        else if (mode == 1024) hipLaunchKernelGGL((bisect3_kernel<2, 1024>), g3, dim3(1024), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb);
-        else if (mode == 8) hipLaunchKernelGGL((bisect3_kernel<8, 256>), g3, dim3(256), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb);
-        else if (mode == 21) hipLaunchKernelGGL((bisect3_kernel<2, 256>), g3, dim3(256), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb);
-        else if (mode == 22) hipLaunchKernelGGL((bisect3_kernel<2, 512>), g3, dim3(512), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb);
-        else hipLaunchKernelGGL((bisect3_kernel<4, 256>), g3, dim3(256), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb);
+    if (variant == 1 || variant == 2) {
+        KScope kt(KS_BISECT, st);
+        if (variant == 1) hipLaunchKernelGGL(bisect_kernel, grid, dim3(256), lds, st, n, ldn, d_d, d_e, d_w, ldw);
+        else hipLaunchKernelGGL(bisect2_kernel, grid, dim3(256), lds, st, n, ldn, d_d, d_e, d_w, ldw);
+        BSP_HIP(hipGetLastError());
+        return BSP_OK;
     }
+    // Two logical workgroups per hardware workgroup, x and x + ceil(nw / 2), once there are more workgroups than CUs: they would share
+    // CUs anyway, and the dispatcher deals them out so that the slow quarters of the spectra share theirs.  The rule
+    // looks at the batch size -- allowed here because the schedule cannot change a bit of the result.
+    // BSP_BISECT_PAIR: 1 = by this rule, 0 = never, 2 = always.
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        BSP_HIP(hipGetDevice(&dev));
+        BSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    }
+    const int nw = (n + ng - 1) / ng;
+    const int pmode = opts().bisect_pair;
+    const int pair_stride = (pmode == 2 || (pmode == 1 && (long)nw * batch > cus)) ? (nw + 1) / 2 : 0;
+    const dim3 g3(pair_stride ? pair_stride : nw, batch);
+    // (measured with BSP_BISECT_DIAG, 128 channels of n = 4096: the 256 paired workgroups land on 256 different CUs although two would fit
+    // one CU's LDS -- no request for more LDS than the arrays need, profiles/r12_bisect_pairs.txt)
+    const int tail = opts().bisect_tail;
+    // (the secant rounds keep a point's count in 16 bits: beyond that size plain bisection)
+    const int hyb = n > 65535 ? 0 : (opts().bisect_secant == 1 ? 8 : (opts().bisect_secant >= 4 ? opts().bisect_secant : (opts().bisect_secant >= 2 ? 4 : 0)));
+#define BISECT3_LAUNCH(E, T, D, dbuf) hipLaunchKernelGGL((bisect3_kernel<E, T, D>), g3, dim3(T), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb, \
+                                                         pair_stride, dbuf)
+    if (opts().bisect_diag) {                              // a record per logical workgroup, on stderr (tools/bisect_balance.py reads them)
+        if (mode != 22) {
+            fprintf(stderr, "bspatom: BSP_BISECT_DIAG is built for the default workgroup shape only (512 x 2)\n");
+            return BSP_ERR_UNSUPPORTED;
+        }
+        const size_t words = (size_t)nw * batch * BISECT_DIAG_WORDS;
+        std::vector<long long> h(words);
+        long long *dbuf = nullptr;
+        BSP_HIP(hipMalloc(reinterpret_cast<void **>(&dbuf), words * sizeof(long long)));
+        BSP_HIP(hipMemsetAsync(dbuf, 0, words * sizeof(long long), st));
+        BISECT3_LAUNCH(2, 512, true, dbuf);
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) { hipFree(dbuf); BSP_HIP(le); }
+        BSP_HIP(hipStreamSynchronize(st));
+        BSP_HIP(hipMemcpy(h.data(), dbuf, words * sizeof(long long), hipMemcpyDeviceToHost));
+        hipFree(dbuf);
+        int dev = 0, khz = 0;
+        BSP_HIP(hipGetDevice(&dev));
+        BSP_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
+        fprintf(stderr, "bisect3 diag: n %d batch %d nw %d pair_stride %d grid %u x %u lds %zu cus %d wall_khz %d\n", n, batch, nw, pair_stride,
+                g3.x, g3.y, lds3, cus, khz);
+        for (size_t r = 0; r < (size_t)nw * batch; ++r) {
+            const long long *q = h.data() + r * BISECT_DIAG_WORDS;
+            fprintf(stderr, "bisect3 wg: x %lld ch %lld xcc %lld hwid 0x%llx t0 %lld t1 %lld rounds %lld tail %lld\n", q[0], q[1], q[2], q[3], q[4], q[5],
+                    q[6], q[7]);
+        }
+        return BSP_OK;
+    }
+    KScope kt(KS_BISECT, st);
+    if (mode == 512) BISECT3_LAUNCH(4, 512, false, nullptr);
+    else if (mode == 1024) BISECT3_LAUNCH(2, 1024, false, nullptr);
+    else if (mode == 8) BISECT3_LAUNCH(8, 256, false, nullptr);
+    else if (mode == 21) BISECT3_LAUNCH(2, 256, false, nullptr);
+    else if (mode == 22) BISECT3_LAUNCH(2, 512, false, nullptr);
+    else BISECT3_LAUNCH(4, 256, false, nullptr);
+#undef BISECT3_LAUNCH
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }

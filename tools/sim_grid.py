@@ -23,7 +23,9 @@ def final(lo, hi):
     mid = 0.5 * (lo + hi)
     return (mid <= lo) | (mid >= hi) | (hi - lo <= 2 * eps * np.maximum(np.abs(lo), np.abs(hi)) + 1e-300)
 
-def simulate(lam, mode, wg):
+def simulate(lam, mode, wg, stop=None):
+    """stop: leave the rounds as the kernel does, once at most that many brackets are unfinished, and return also what it hands to the
+    tail: (scaled spectrum, lo, hi, eigenvalue numbers) of the unfinished (tools/sim_bisect_rounds.py)"""
     n = len(lam); nrm = max(abs(lam[0]), abs(lam[-1])); lam = lam / nrm
     gl = lam[0] - 1e-3; gu = lam[-1] + 1e-3; w = gu - gl
     count = lambda x: np.searchsorted(lam, x, side="left")
@@ -41,6 +43,7 @@ def simulate(lam, mode, wg):
     for it in range(200):
         done = final(lo, hi)
         left.append(int(np.sum(~done)))
+        if stop is not None and left[-1] <= stop: return evals, left, (lam, lo[~done], hi[~done], m[~done])
         if left[-1] == 0: break
         wd = hi - lo
         halved = wd <= 0.5 * wref
