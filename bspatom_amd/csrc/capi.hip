@@ -45,6 +45,8 @@ const OptName OPT_TABLE[] = {
     {"bisect_tail", "BSP_BISECT_TAIL", &Options::bisect_tail},
     {"bisect_secant", "BSP_BISECT_SECANT", &Options::bisect_secant},
     {"bisect_pair", "BSP_BISECT_PAIR", &Options::bisect_pair},
+    {"bisect_queue", "BSP_BISECT_QUEUE", &Options::bisect_queue},
+    {"bisect_queue_grid", "BSP_BISECT_QUEUE_GRID", &Options::bisect_queue_grid},
     {"bisect_diag", "BSP_BISECT_DIAG", &Options::bisect_diag},
     {"no_eigvec_prefetch", "BSP_NO_EIGVEC_PREFETCH", &Options::no_eigvec_prefetch},
     {"vec_early", "BSP_VEC_EARLY", &Options::vec_early},

@@ -58,6 +58,11 @@ struct Options {
     int bisect_tail = 1;         // BSP_BISECT_TAIL: 0 = lock-step bisection to the end (no multisection tail), for A/B timing
     int bisect_pair = 1;         // BSP_BISECT_PAIR: a workgroup of bisect3_kernel runs two logical workgroups of its channel, x and x + ceil(nw / 2),
                                  // one after the other -- 1 = when there are more workgroups than CUs, 0 = never, 2 = always; bit-identical results
+                                 // (only where the queue below does not take the launch)
+    int bisect_queue = 1;        // BSP_BISECT_QUEUE: the workgroups of bisect3_kernel claim their logical workgroups from a list, the first on a CU from
+                                 // its costly end, the second from its cheap end (tridiag.hip) -- 1 = when there are more logical workgroups than CUs
+                                 // (it then takes the place of the pairs), 0 = never, 2 = always; bit-identical results
+    int bisect_queue_grid = 0;   // BSP_BISECT_QUEUE_GRID: test hook: the queue launch has at most this many hardware workgroups (0 = no cap)
     int bisect_diag = 0;         // BSP_BISECT_DIAG: instrumented bisect3_kernel: placement, wall-clock stamps and rounds of every workgroup (stderr)
     int no_eigvec_prefetch = 0;
     int vec_early = 1;           // BSP_VEC_EARLY: band route, the consumed eigenvector's eigenvalue from the pencil's inertia right after the assembly (bandsect.hip); 0: from the tridiagonal matrix at the end; 2: as 1 with the check made to fail

@@ -7,6 +7,7 @@
 //
 // count(x) = #{eigenvalues < x} from the LDL^T pivots q_i = (d_i - x) - e_{i-1}^2 / q_{i-1}
 // (LAPACK dstebz/dlaebz recurrence with the pivmin safeguard).
+#include <algorithm>
 #include <vector>
 #include "common.h"
 
@@ -374,11 +375,24 @@ static size_t bisect3_lds_bytes(int n, int ng)
 // eigenvalue sees the same points in the same order: the spectra do not depend on pair_stride, bit for bit.
 // DIAG: the instrumented instance (BSP_BISECT_DIAG; `diag` non-null): a record per logical workgroup; the other carries no stamp, no
 // test for one.
-constexpr int BISECT_DIAG_WORDS = 8;   // x, channel, HW_REG_XCC_ID, HW_REG_HW_ID, wall clock at its start and end, lock-step rounds, tail rounds
-template <int EPT, int TPB, bool DIAG = false>
+//
+// QUEUE (BSP_BISECT_QUEUE, launch_bisect): a 1-D grid of at most two hardware workgroups per CU, and every one of them CLAIMS its items
+// -- logical workgroups (x, channel) -- from a list in global memory until none is left.  The list is in the order of the expected
+// cost, costliest first: item i is channel i % batch of rank i / batch, and the ranks take x from the ends of the spectrum inwards
+// (nw - 1, 0, nw - 2, 1, ..).  The first workgroup to arrive on a CU (an atomic on the CU's word of the arrival table, the CU from
+// HW_REG_XCC_ID and HW_REG_HW_ID) claims from the head of the list, the second from its tail, so a CU that holds two starts a slow
+// item beside a fast one whatever the dispatcher does.  The placement only decides which end a workgroup draws from: every item is
+// handed out exactly once (`claimed` counts the claims, so head and tail cannot cross) wherever the workgroups sit, and no workgroup
+// waits for another.  What an item computes is what it computes in the other launches; the set-up is redone when the channel changes.
+constexpr int BISECT_DIAG_WORDS = 10;  // x, channel, HW_REG_XCC_ID, HW_REG_HW_ID, wall clock at its start and end, lock-step rounds, tail rounds,
+                                       // the hardware workgroup, its arrival number on its CU (queue launch; else -1)
+constexpr int BISECT_Q_CUS = 16 * 256; // words of the arrival table: HW_REG_XCC_ID (4 bits) x the CU, SH and SE bits of HW_REG_HW_ID (8)
+constexpr int BISECT_Q_WORDS = BISECT_Q_CUS + 4;   // .. and the words `claimed`, `head`, `tail`
+template <int EPT, int TPB, bool DIAG = false, bool QUEUE = false>
 __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const double *__restrict__ dall,
                                                      const double *__restrict__ eall, double *wall, long ldw, int tail,
-                                                     double2 *gtail, int nl, int hybrid_arg, int pair_stride, long long *diag)
+                                                     double2 *gtail, int nl, int hybrid_arg, int pair_stride, long long *diag,
+                                                     unsigned *qcnt, int items, int batch)
 {
     long long dt0 = DIAG ? (long long)wall_clock64() : 0;
     // (eight eigenvalues per thread, BSP_BISECT_EPT=8, an A/B of round 1: plain bisection -- the secant rounds' state does not fit its registers)
@@ -399,58 +413,94 @@ __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const doub
     int *lm = cg + NG;
     __shared__ double red[2 * NW];
     __shared__ int sK;
+    __shared__ int sItem, sSide;                       // QUEUE: the claimed item (-1: none left); the end of the list this workgroup claims from
     const int tid0 = threadIdx.x;
-    const size_t ch = blockIdx.y;
-    const double *dg = dall + ch * (size_t)ldn, *eg = eall + ch * (size_t)ldn;
-    double *wout = wall + ch * (size_t)ldw;
-    // the rows that do not fit the LDS: every workgroup of a channel writes the same values to the channel's slice
-    double2 *gt = gtail ? gtail + ch * (size_t)(np + 1) : nullptr;
-    double gl = 1e300, gu = -1e300;
-    for (int i = tid0; i < n; i += TPB) {
-        const double di = dg[i];
-        const double el = (i > 0) ? fabs(eg[i - 1]) : 0.0;
-        const double er = (i < n - 1) ? fabs(eg[i]) : 0.0;
-        gl = fmin(gl, di - el - er);
-        gu = fmax(gu, di + el + er);
-    }
+    size_t ch = blockIdx.y;
+    double *wout;
+    double2 *gt;
+    double gl, gu, isc;
+    // the set-up of a channel: Gershgorin bounds, scaling, the rows (d, e^2) to LDS (and to global memory beyond row nlr)
+    const auto channel_setup = [&]() __attribute__((always_inline)) {
+        const double *dg = dall + ch * (size_t)ldn, *eg = eall + ch * (size_t)ldn;
+        wout = wall + ch * (size_t)ldw;
+        // the rows that do not fit the LDS: every workgroup of a channel writes the same values to the channel's slice
+        gt = gtail ? gtail + ch * (size_t)(np + 1) : nullptr;
+        gl = 1e300; gu = -1e300;
+        for (int i = tid0; i < n; i += TPB) {
+            const double di = dg[i];
+            const double el = (i > 0) ? fabs(eg[i - 1]) : 0.0;
+            const double er = (i < n - 1) ? fabs(eg[i]) : 0.0;
+            gl = fmin(gl, di - el - er);
+            gu = fmax(gu, di + el + er);
+        }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        gl = fmin(gl, __shfl_xor(gl, off));
-        gu = fmax(gu, __shfl_xor(gu, off));
-    }
-    if ((tid0 & 63) == 0) { red[tid0 >> 6] = gl; red[NW + (tid0 >> 6)] = gu; }
-    __syncthreads();
+        for (int off = 32; off >= 1; off >>= 1) {
+            gl = fmin(gl, __shfl_xor(gl, off));
+            gu = fmax(gu, __shfl_xor(gu, off));
+        }
+        if ((tid0 & 63) == 0) { red[tid0 >> 6] = gl; red[NW + (tid0 >> 6)] = gu; }
+        __syncthreads();
 #pragma unroll
-    for (int q = 0; q < NW; ++q) { gl = fmin(gl, red[q]); gu = fmax(gu, red[NW + q]); }
-    const double eps = 2.220446049250313e-16;
-    double tnorm = fmax(fabs(gl), fabs(gu));
-    if (!(tnorm > 0.0)) tnorm = 1.0;                   // the zero matrix
-    int kexp;
-    (void)frexp(tnorm, &kexp);                         // tnorm = f 2^kexp, f in [0.5, 1)
-    const double sc = ldexp(1.0, -kexp), isc_v = ldexp(1.0, kexp);
-    for (int i = tid0; i <= np; i += TPB) {
-        // row i of the scaled matrix with its coupling to row i-1.  Padding rows: d = 2, coupling at the floor.
-        const double di = (i < n) ? dg[i] * sc : 2.0;
-        const double ev = (i >= 1 && i < n) ? (eg[i - 1] * sc) : 0.0;
-        const double2 row = make_double2(di, fmax(ev * ev, 1e-60));
-        if (i <= nlr) de[i] = row; else gt[i] = row;
-    }
-    if (gt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's stores have reached the L2 it reads them back from
-    __syncthreads();
-    gl = gl * sc - 2.1 * eps * n - 1e-300;             // scaled Gershgorin interval, widened as dstebz does
-    gu = gu * sc + 2.1 * eps * n + 1e-300;
+        for (int q = 0; q < NW; ++q) { gl = fmin(gl, red[q]); gu = fmax(gu, red[NW + q]); }
+        const double eps = 2.220446049250313e-16;
+        double tnorm = fmax(fabs(gl), fabs(gu));
+        if (!(tnorm > 0.0)) tnorm = 1.0;                   // the zero matrix
+        int kexp;
+        (void)frexp(tnorm, &kexp);                         // tnorm = f 2^kexp, f in [0.5, 1)
+        const double sc = ldexp(1.0, -kexp), isc_v = ldexp(1.0, kexp);
+        for (int i = tid0; i <= np; i += TPB) {
+            // row i of the scaled matrix with its coupling to row i-1.  Padding rows: d = 2, coupling at the floor.
+            const double di = (i < n) ? dg[i] * sc : 2.0;
+            const double ev = (i >= 1 && i < n) ? (eg[i - 1] * sc) : 0.0;
+            const double2 row = make_double2(di, fmax(ev * ev, 1e-60));
+            if (i <= nlr) de[i] = row; else gt[i] = row;
+        }
+        if (gt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's stores have reached the L2 it reads them back from
+        __syncthreads();
+        gl = gl * sc - 2.1 * eps * n - 1e-300;             // scaled Gershgorin interval, widened as dstebz does
+        gu = gu * sc + 2.1 * eps * n + 1e-300;
 
-    // the same in every lane, and live through both items: in scalar registers
-    gl = uniform_double(gl); gu = uniform_double(gu);
-    const double isc = uniform_double(isc_v);
+        // the same in every lane, and live through the items: in scalar registers
+        gl = uniform_double(gl); gu = uniform_double(gu);
+        isc = uniform_double(isc_v);
+    };
     const int nwl = (n + NG - 1) / NG;                 // logical workgroups of a channel
+    int side = -1;                                     // DIAG: the workgroup's arrival number on its CU
+    if (QUEUE) {
+        if (tid0 == 0) {
+            const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xfu;                 // HW_REG_XCC_ID
+            const unsigned cu = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 8) & 0xffu;         // HW_REG_HW_ID: CU bits 8-11, SH 12, SE 13-15
+            sSide = (int)atomicAdd(qcnt + xcc * 256 + cu, 1u);
+        }
+    } else
+        channel_setup();
 #pragma unroll 1
-    for (int item = 0; item < 2; ++item) {
-        const int bx = blockIdx.x + item * pair_stride;    // the logical workgroup: eigenvalues bx NG .. bx NG + NG - 1
-        if (item) {
-            if (pair_stride == 0 || bx >= nwl) break;
-            __syncthreads();                               // the first one's last reads of its tail list: the slot arrays are used again
-            if (DIAG) dt0 = (long long)wall_clock64();
+    for (int item = 0; QUEUE || item < 2; ++item) {
+        int bx;                                            // the logical workgroup: eigenvalues bx NG .. bx NG + NG - 1
+        if (QUEUE) {
+            // the previous item's last reads of its tail list and of sItem are over: the slot arrays are used again
+            if (item) __syncthreads();
+            if (tid0 == 0) {
+                int it = -1;
+                if (atomicAdd(qcnt + BISECT_Q_CUS, 1u) < (unsigned)items)     // `claimed`: at most `items` claims draw from the two ends
+                    it = (sSide & 1) ? items - 1 - (int)atomicAdd(qcnt + BISECT_Q_CUS + 2, 1u) : (int)atomicAdd(qcnt + BISECT_Q_CUS + 1, 1u);
+                sItem = it;
+            }
+            __syncthreads();
+            const int it = __builtin_amdgcn_readfirstlane(sItem);
+            if (it < 0) break;
+            if (DIAG) { dt0 = (long long)wall_clock64(); side = __builtin_amdgcn_readfirstlane(sSide); }
+            const int rank = it / batch;
+            bx = (rank & 1) ? (rank >> 1) : nwl - 1 - (rank >> 1);
+            const size_t chn = (size_t)(it - rank * batch);
+            if (item == 0 || chn != ch) { ch = chn; channel_setup(); }
+        } else {
+            bx = blockIdx.x + item * pair_stride;
+            if (item) {
+                if (pair_stride == 0 || bx >= nwl) break;
+                __syncthreads();                           // the first one's last reads of its tail list: the slot arrays are used again
+                if (DIAG) dt0 = (long long)wall_clock64();
+            }
         }
         int drounds = 0, dtail = 0;
         // the thread's number, opaque to the compiler: the slot addresses it forms from it are the same for both items, and hoisted in front
@@ -689,6 +739,7 @@ __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const doub
             rec[3] = (long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_REG_HW_ID: CU bits 8-11, SH 12, SE 13-15
             rec[4] = dt0; rec[5] = (long long)wall_clock64();
             rec[6] = drounds; rec[7] = dtail;
+            rec[8] = (long long)(blockIdx.x + gridDim.x * blockIdx.y); rec[9] = side;
         }
     }
 }
@@ -923,6 +974,10 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
         BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512, true, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
         attr_set = true;
     }
     const dim3 grid((n + 256 * EPT - 1) / (256 * EPT), batch);
@@ -945,15 +1000,39 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
     }
     const int nw = (n + ng - 1) / ng;
     const int pmode = opts().bisect_pair;
-    const int pair_stride = (pmode == 2 || (pmode == 1 && (long)nw * batch > cus)) ? (nw + 1) / 2 : 0;
-    const dim3 g3(pair_stride ? pair_stride : nw, batch);
+    // The item queue (bisect3_kernel, QUEUE): at most two hardware workgroups per CU claim the nw x batch logical workgroups from a list,
+    // the first on a CU from its costly end, the second from its cheap end.  It takes the pairing rule's place where it fires, under the
+    // same rule; the default workgroup shape only (the others keep their launch).
+    // BSP_BISECT_QUEUE: 1 = when nw x batch exceeds the CU count, 0 = never, 2 = always.  BSP_BISECT_QUEUE_GRID (test hook): at most
+    // this many hardware workgroups (0 = no cap), so that a small batch makes a workgroup run several items of several channels.
+    const int qmode = opts().bisect_queue;
+    const long items = (long)nw * batch;
+    const bool queue = mode == 22 && items < (1L << 30) && (qmode == 2 || (qmode == 1 && items > cus));
+    const int pair_stride = queue ? 0 : ((pmode == 2 || (pmode == 1 && items > cus)) ? (nw + 1) / 2 : 0);
+    int qgrid = (int)std::min(items, 2L * cus);
+    if (opts().bisect_queue_grid > 0) qgrid = std::min(qgrid, opts().bisect_queue_grid);
+    const dim3 g3 = queue ? dim3(qgrid, 1) : dim3(pair_stride ? pair_stride : nw, batch);
+    // the queue's counters (arrival table, claimed, head, tail): one small array PER STREAM like the rows above, zeroed on the stream in
+    // front of every launch
+    struct QCount { hipStream_t st; unsigned *p; };
+    static std::vector<QCount> g_qcounts;
+    unsigned *qcnt = nullptr;
+    if (queue) {
+        for (auto &x : g_qcounts) if (x.st == st) qcnt = x.p;
+        if (!qcnt) {
+            BSP_HIP(hipMalloc(reinterpret_cast<void **>(&qcnt), BISECT_Q_WORDS * sizeof(unsigned)));
+            g_qcounts.push_back({st, qcnt});
+        }
+        BSP_HIP(hipMemsetAsync(qcnt, 0, BISECT_Q_WORDS * sizeof(unsigned), st));
+    }
     // (measured with BSP_BISECT_DIAG, 128 channels of n = 4096: the 256 paired workgroups land on 256 different CUs although two would fit
     // one CU's LDS -- no request for more LDS than the arrays need, profiles/r12_bisect_pairs.txt)
     const int tail = opts().bisect_tail;
     // (the secant rounds keep a point's count in 16 bits: beyond that size plain bisection)
     const int hyb = n > 65535 ? 0 : (opts().bisect_secant == 1 ? 8 : (opts().bisect_secant >= 4 ? opts().bisect_secant : (opts().bisect_secant >= 2 ? 4 : 0)));
-#define BISECT3_LAUNCH(E, T, D, dbuf) hipLaunchKernelGGL((bisect3_kernel<E, T, D>), g3, dim3(T), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, hyb, \
-                                                         pair_stride, dbuf)
+#define BISECT3_LAUNCH_Q(E, T, D, Q, dbuf) hipLaunchKernelGGL((bisect3_kernel<E, T, D, Q>), g3, dim3(T), lds3, st, n, ldn, d_d, d_e, d_w, ldw, tail, gtail, nl, \
+                                                              hyb, pair_stride, dbuf, qcnt, (int)items, batch)
+#define BISECT3_LAUNCH(E, T, D, dbuf) BISECT3_LAUNCH_Q(E, T, D, false, dbuf)
     if (opts().bisect_diag) {                              // a record per logical workgroup, on stderr (tools/bisect_balance.py reads them)
         if (mode != 22) {
             fprintf(stderr, "bspatom: BSP_BISECT_DIAG is built for the default workgroup shape only (512 x 2)\n");
@@ -964,7 +1043,8 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
         long long *dbuf = nullptr;
         BSP_HIP(hipMalloc(reinterpret_cast<void **>(&dbuf), words * sizeof(long long)));
         BSP_HIP(hipMemsetAsync(dbuf, 0, words * sizeof(long long), st));
-        BISECT3_LAUNCH(2, 512, true, dbuf);
+        if (queue) BISECT3_LAUNCH_Q(2, 512, true, true, dbuf);
+        else BISECT3_LAUNCH(2, 512, true, dbuf);
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) { hipFree(dbuf); BSP_HIP(le); }
         BSP_HIP(hipStreamSynchronize(st));
@@ -973,12 +1053,12 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
         int dev = 0, khz = 0;
         BSP_HIP(hipGetDevice(&dev));
         BSP_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-        fprintf(stderr, "bisect3 diag: n %d batch %d nw %d pair_stride %d grid %u x %u lds %zu cus %d wall_khz %d\n", n, batch, nw, pair_stride,
-                g3.x, g3.y, lds3, cus, khz);
+        fprintf(stderr, "bisect3 diag: n %d batch %d nw %d pair_stride %d queue %d grid %u x %u lds %zu cus %d wall_khz %d\n", n, batch, nw, pair_stride,
+                queue ? 1 : 0, g3.x, g3.y, lds3, cus, khz);
         for (size_t r = 0; r < (size_t)nw * batch; ++r) {
             const long long *q = h.data() + r * BISECT_DIAG_WORDS;
-            fprintf(stderr, "bisect3 wg: x %lld ch %lld xcc %lld hwid 0x%llx t0 %lld t1 %lld rounds %lld tail %lld\n", q[0], q[1], q[2], q[3], q[4], q[5],
-                    q[6], q[7]);
+            fprintf(stderr, "bisect3 wg: x %lld ch %lld xcc %lld hwid 0x%llx t0 %lld t1 %lld rounds %lld tail %lld hwg %lld side %lld\n", q[0], q[1], q[2], q[3],
+                    q[4], q[5], q[6], q[7], q[8], q[9]);
         }
         return BSP_OK;
     }
@@ -987,9 +1067,11 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
     else if (mode == 1024) BISECT3_LAUNCH(2, 1024, false, nullptr);
     else if (mode == 8) BISECT3_LAUNCH(8, 256, false, nullptr);
     else if (mode == 21) BISECT3_LAUNCH(2, 256, false, nullptr);
+    else if (mode == 22 && queue) BISECT3_LAUNCH_Q(2, 512, false, true, nullptr);
     else if (mode == 22) BISECT3_LAUNCH(2, 512, false, nullptr);
     else BISECT3_LAUNCH(4, 256, false, nullptr);
 #undef BISECT3_LAUNCH
+#undef BISECT3_LAUNCH_Q
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }

@@ -4,8 +4,11 @@ pencil (n = 4096, k = 9) with the instrumented kernel (option bisect_diag: a rec
 XCD, CU, wall-clock stamps, rounds), then
   1. duration and rounds by x (the quarter of the spectrum the workgroup owns);
   2. which x share a CU and an XCD;
-  3. per CU: the time it has a workgroup, against the kernel's time, and the rounds it runs.
-usage: tools/bisect_balance.py [--channels N] [name=value ...]      (e.g. bisect_pair=0)"""
+  3. per CU: the time it has a workgroup, against the kernel's time, and the rounds it runs;
+  4. for the queue launch (bisect_queue, the records then carry the hardware workgroup and its arrival number on its CU): items per
+     hardware workgroup, which x started together on a CU, and when the CUs of every such starting set were done.
+usage: tools/bisect_balance.py [--channels N] [--save FILE | --records FILE] [name=value ...]      (e.g. bisect_pair=0, bisect_queue=0)
+--save keeps the records as the library wrote them; --records reports on such a file instead of running a solve."""
 import os
 import sys
 import tempfile
@@ -55,8 +58,8 @@ def report(head, recs):
     tick_ms = 1.0 / float(head["wall_khz"])
     t_first = min(r["t0"] for r in recs); t_last = max(r["t1"] for r in recs)
     kernel = (t_last - t_first) * tick_ms
-    print("launch: n %s, %s channels, %s logical workgroups per channel, pair_stride %s, grid %s, %s bytes of LDS, %s CUs; first start to last end %.2f ms"
-          % (head["n"], head["batch"], head["nw"], head["pair_stride"], head["grid"], head["lds"], head["cus"], kernel))
+    print("launch: n %s, %s channels, %s logical workgroups per channel, pair_stride %s, queue %s, grid %s, %s bytes of LDS, %s CUs; first start to last end %.2f ms"
+          % (head["n"], head["batch"], head["nw"], head["pair_stride"], head.get("queue", "0"), head["grid"], head["lds"], head["cus"], kernel))
     print("1. by x: workgroups, duration in ms (mean / min / max), start after the first start (mean), lock-step + tail rounds (mean; max of the sum)")
     xs = sorted({r["x"] for r in recs})
     dur_x = {}
@@ -86,16 +89,40 @@ def report(head, recs):
         len(by_cu), head["cus"], kernel, 100 * busy.mean() / kernel, 100 * busy.min() / kernel, 100 * busy.max() / kernel))
     print("   rounds per CU: mean %.1f, min %d, max %d (max %.0f %% above the mean)" % (rsum.mean(), rsum.min(), rsum.max(),
                                                                                       100 * (rsum.max() / rsum.mean() - 1)))
+    if head.get("queue", "0") != "1":
+        return
+    by_hwg = defaultdict(list)
+    for r in recs:
+        by_hwg[r["hwg"]].append(r)
+    per = np.array([len(v) for v in by_hwg.values()])
+    sides = Counter(v[0]["side"] for v in by_hwg.values())
+    print("4. queue: %d hardware workgroups ran items, %.2f items each (max %d); arrival number on the CU -> workgroups: %s" % (
+        len(by_hwg), per.mean(), per.max(), "  ".join("%d: %d" % kv for kv in sorted(sides.items()))))
+    ends = defaultdict(list)                                       # the x that started together on a CU -> end of that CU's last item
+    for rr in by_cu.values():
+        firsts = [min(v, key=lambda r: r["t0"]) for v in by_hwg.values() if cu_of(v[0]) == cu_of(rr[0])]
+        start = tuple(r["x"] for r in sorted(firsts, key=lambda r: r["side"]))
+        ends[start].append((max(r["t1"] for r in rr) - t_first) * tick_ms)
+    print("   x that started together on a CU (by arrival) -> CUs, end of the CU's last item in ms (mean / max)")
+    for k, v in sorted(ends.items()):
+        print("   %-10s %4d   %.2f / %.2f" % (k, len(v), np.mean(v), np.max(v)))
 
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    chans, opts = 128, {}
+    chans, opts, save, records = 128, {}, None, None
     while args:
         a = args.pop(0)
         if a == "--channels": chans = int(args.pop(0))
+        elif a == "--save": save = args.pop(0)
+        elif a == "--records": records = args.pop(0)
         else:
             k, v = a.split("="); opts[k] = int(v)
+    if records:
+        head, recs = parse(open(records).read())
+        print("== records of %s" % records)
+        report(head, recs)
+        sys.exit(0)
     for k, v in opts.items():
         capi.set_option(k, v)
     prob = capi.Problem(capi.make_input(kind_grid=0, ra=0.0, rb=800.0, k=9, nfun=4096, n0_ini=1, l_ini=0, l_fin=127, zatom=1.0))
@@ -106,6 +133,9 @@ if __name__ == "__main__":
     finally:
         capi.set_option("bisect_diag", 0)
     prob.close()
+    if save:
+        with open(save, "w") as f:
+            f.write("".join(l + "\n" for l in text.splitlines() if l.startswith("bisect3 ")))
     head, recs = parse(text)
     if not head or not recs:
         sys.exit("no diagnostic records on stderr:\n" + text[-2000:])
