@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -84,6 +84,8 @@ def lib():
         L.bspatom_tdse_propagate_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp]
         L.bspatom_tdse_observe.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
         L.bspatom_tdse_observe_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
+        L.bspatom_tdse_lawson.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
+        L.bspatom_tdse_lawson_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -456,6 +458,45 @@ class Problem:
                                             float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
                                             C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
                                             C.c_void_p(obs_ptr) if obs_ptr else None), "bspatom_tdse_observe_dev")
+        return err
+
+    def tdse_lawson(self, E, pairs, D, a0, field, dt, obs_every=0, snap_every=0):
+        """tdse_propagate / tdse_observe with Lawson (integrating-factor) steps of the same tableau (bspatom_tdse_lawson): the free
+        evolution exp(-i E t) is exact, so the step is bounded by |f| ||D|| and not by dt max|E|.  The arguments and layouts are
+        tdse_observe's; obs_every = 0 propagates only.  Returns (a, err[, obs][, snaps]) as tdse_propagate / tdse_observe do, all in
+        the Schroedinger picture at step boundaries."""
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        nch, count = E.shape
+        ci, cf = self._tdse_pairs(pairs)
+        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
+        a = np.array(a0, dtype=np.complex128, order="C")
+        one = a.ndim == 2
+        a = np.ascontiguousarray(a.reshape(-1, nch, count))
+        nscan = a.shape[0]
+        field = np.ascontiguousarray(field, dtype=np.complex128)
+        nsteps = field.shape[0] if field.ndim == 3 else 0
+        assert field.shape == (nsteps, 6, nscan), (field.shape, nscan)
+        err = np.zeros(nscan)
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 4)) if obs_every > 0 else None
+        _chk(lib().bspatom_tdse_lawson(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
+                                       _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
+                                       _p(snaps), _p(err), obs_every, _p(obs)), "bspatom_tdse_lawson")
+        if one:
+            a = a[0]
+        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+
+    def tdse_lawson_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, obs_every=0, obs_ptr=None, snap_every=0,
+                        snap_ptr=None):
+        """tdse_lawson on device memory, the arguments of tdse_observe_dev (obs_every = 0 with obs_ptr None: no observables).
+        Returns err (nscan,) when the result is there."""
+        ci, cf = self._tdse_pairs(pairs)
+        err = np.zeros(nscan)
+        _chk(lib().bspatom_tdse_lawson_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
+                                           _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
+                                           float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
+                                           C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
+                                           C.c_void_p(obs_ptr) if obs_ptr else None), "bspatom_tdse_lawson_dev")
         return err
 
     def early_vector_state(self):

@@ -1,5 +1,6 @@
-// capi_tdse.hip -- bspatom_tdse_propagate / _dev and bspatom_tdse_observe / _dev (include/bspatom.h): the argument checks, the
-// per-channel entry lists, the working buffers and the step loop of tdse.hip.  One code path: propagate is observe without rows.  The problem handle gives the device and the stream; nothing of a solve is read.
+// capi_tdse.hip -- bspatom_tdse_propagate / _dev, bspatom_tdse_observe / _dev and bspatom_tdse_lawson / _dev (include/bspatom.h): the
+// argument checks, the per-channel entry lists, the working buffers and the step loop of tdse.hip.  One code path: propagate is observe
+// without rows, and the Lawson scheme is a flag that adds the phase table.  The problem handle gives the device and the stream; nothing of a solve is read.
 #include <cmath>
 #include "capi_internal.h"
 
@@ -26,7 +27,7 @@ bool args_ok(const bspatom_problem *p, int nch, int count, const double *E, int 
 struct Plan {
     TdseDims d;
     DevArray<int> cptr, ent;
-    DevArray<double> aw, K, part;
+    DevArray<double> aw, K, part, ph;
     DevArray<unsigned long long> err2;
     size_t rows = 0, odbl = 0;                 // odbl: doubles of one row of observables, [nscan][nch][4]
     bool observing = false;
@@ -55,7 +56,13 @@ struct Plan {
         if (observing && (rc = part.alloc((size_t)nch * ((count + 63) / 64) * (d.NC / 2) * 4))) return rc;
         return HIP_RC(hipMemsetAsync(err2.p, 0, (size_t)nscan * sizeof(unsigned long long), p->st));
     }
-    TdseBufs bufs(const double *d_E, const double *d_D) const { return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p, observing ? part.p : nullptr}; }
+    // the Lawson scheme: the phase table from the energies on the device, before bufs()
+    int phases(bspatom_problem *p, const double *d_E, double dt)
+    {
+        const int rc = ph.alloc((size_t)10 * rows);
+        return rc ? rc : launch_tdse_phases(d, d_E, dt, ph.p, p->st);
+    }
+    TdseBufs bufs(const double *d_E, const double *d_D) const { return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p, observing ? part.p : nullptr, ph.p}; }
     // steps n0 .. n1-1; d_field: the table from step n0 on; d_snap (or null): where snapshot number s0 (from 0) goes, the later ones behind it;
     // d_obs (or null): where row j0 goes (row j = the amplitudes before step j obs_every), the later ones behind it
     int run(bspatom_problem *p, const TdseBufs &w, int n0, int n1, double dt, const double *d_field, int snap_every, double *d_snap, int s0,
@@ -89,7 +96,7 @@ struct Plan {
 // obs_every = 0: no observables (obs null).  Otherwise rows for the steps 0, obs_every, .. < nsteps, then the row of the final amplitudes.
 int run_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci, const int32_t *cf,
             const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev, double *a_dev, int snap_every,
-            double *snap_dev, double *err, int obs_every, double *obs_dev)
+            double *snap_dev, double *err, int obs_every, double *obs_dev, bool lawson)
 {
     const bool observing = obs_every > 0;
     if (nsteps == 0 && !observing) {
@@ -100,6 +107,7 @@ int run_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npa
     Plan pl;
     int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf, observing);
     if (!rc) rc = launch_tdse_pack(pl.d, a_dev, pl.aw.p, p->st);
+    if (!rc && lawson && nsteps > 0) rc = pl.phases(p, E_dev, dt);
     const TdseBufs w = pl.bufs(E_dev, D_dev);
     if (!rc) rc = pl.run(p, w, 0, nsteps, dt, field_dev, snap_every, snap_dev, 0, obs_every, obs_dev, 0);
     if (!rc && observing) {
@@ -113,7 +121,7 @@ int run_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npa
 
 int run_host(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf, const double *D,
              int nscan, int nsteps, double dt, const double *field, double *a, int snap_every, double *snap, double *err, int obs_every,
-             double *obs)
+             double *obs, bool lawson)
 {
     const bool observing = obs_every > 0;
     if (nsteps == 0 && !observing) {
@@ -149,6 +157,7 @@ int run_host(bspatom_problem *p, int nch, int count, const double *E, int npairs
     if (!rc && snapping) rc = dsnap.alloc(snaps_of(g) * adbl);
     if (!rc && observing) rc = dobs.alloc((obs_of(g) > 0 ? obs_of(g) : 1) * odbl);
     if (!rc) rc = launch_tdse_pack(pl.d, da.p, pl.aw.p, p->st);
+    if (!rc && lawson && nsteps > 0) rc = pl.phases(p, dE.p, dt);
     const TdseBufs w = pl.bufs(dE.p, dD.p);
     for (int n0 = 0; !rc && n0 < nsteps; n0 += (int)g) {
         const int n1 = n0 + (int)g < nsteps ? n0 + (int)g : nsteps;
@@ -183,7 +192,7 @@ extern "C" int bspatom_tdse_propagate_dev(bspatom_problem *p, int nch, int count
                                           const double *field_dev, double *a_dev, int snap_every, double *snap_dev, double *err)
 {
     if (!args_ok(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev)) return BSP_ERR_ARG;
-    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, 0, nullptr);
+    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, 0, nullptr, false);
 }
 
 extern "C" int bspatom_tdse_propagate(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
@@ -191,7 +200,7 @@ extern "C" int bspatom_tdse_propagate(bspatom_problem *p, int nch, int count, co
                                       double *a, int snap_every, double *snap, double *err)
 {
     if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap)) return BSP_ERR_ARG;
-    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, 0, nullptr);
+    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, 0, nullptr, false);
 }
 
 extern "C" int bspatom_tdse_observe_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
@@ -203,7 +212,7 @@ extern "C" int bspatom_tdse_observe_dev(bspatom_problem *p, int nch, int count, 
         return BSP_ERR_ARG;
     if (obs_every == 0)
         return bspatom_tdse_propagate_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err);
-    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, obs_every, obs_dev);
+    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, obs_every, obs_dev, false);
 }
 
 extern "C" int bspatom_tdse_observe(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
@@ -213,5 +222,24 @@ extern "C" int bspatom_tdse_observe(bspatom_problem *p, int nch, int count, cons
     if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap) || !obs_args_ok(obs_every, obs))
         return BSP_ERR_ARG;
     if (obs_every == 0) return bspatom_tdse_propagate(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err);
-    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs);
+    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs, false);
+}
+
+extern "C" int bspatom_tdse_lawson_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                                       const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                                       double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev)
+{
+    if (!args_ok(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev) ||
+        !obs_args_ok(obs_every, obs_dev))
+        return BSP_ERR_ARG;
+    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, obs_every, obs_dev, true);
+}
+
+extern "C" int bspatom_tdse_lawson(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
+                                   const int32_t *cf, const double *D, int nscan, int nsteps, double dt, const double *field, double *a,
+                                   int snap_every, double *snap, double *err, int obs_every, double *obs)
+{
+    if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap) || !obs_args_ok(obs_every, obs))
+        return BSP_ERR_ARG;
+    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs, true);
 }

@@ -305,6 +305,7 @@ struct TdseBufs {
     double *a, *K;               // working amplitudes; the six k_s, each nch * count * NC doubles
     unsigned long long *err2;    // [nscan] bit patterns of max |sum_s (d_s - b_s) k_s|^2, zeroed by the caller
     double *part;                // observables: [nch][ceil(count / 64)][NC / 2][4] partials of the row tiles (null: nothing is observed)
+    const double *ph;            // Lawson steps: [5][nch][count][2] cos, sin of E c_s dt, s = 1 .. 5 (launch_tdse_phases); null: the plain scheme
 };
 extern const double TDSE_A[6][5], TDSE_D[6], TDSE_B[6];
 int tdse_columns(int nscan);
@@ -315,6 +316,8 @@ int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field
 // the observables of w.a into d_row [nscan][nch][4]: tdse_observe_kernel and the reduction of its row-tile partials.  d_field: the
 // stage-0 field of a step that follows, whose k_0 the kernel then leaves exactly as the plain stage does; null: the measurement alone
 int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *d_field, double *d_row, hipStream_t st);
+// the phase table of bspatom_tdse_lawson from d_E, once per call
+int launch_tdse_phases(const TdseDims &d, const double *d_E, double dt, double *d_ph, hipStream_t st);
 int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st);
 int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st);
 

@@ -5,6 +5,7 @@
 // forms its operand y_s = a + dt sum_j A_sj k_j while it loads it and leaves k_s = -i H(t_n + c_s dt) y_s, then one kernel for the
 // step, the error estimate and the snapshot.  bspatom_tdse_observe: on an observed step stage 0 runs as tdse_observe_kernel, which also
 // measures a(t_n) (populations, E |a|^2, the coupling expectation value per channel), followed by tdse_obs_reduce_kernel: eight launches.
+// bspatom_tdse_lawson: the integrating-factor form of the same tableau in the same launches (LAWSON below), after tdse_phase_kernel once.
 //
 // Working layout: the amplitudes of channel c are a real matrix [count][NC], column 2q = Re, 2q + 1 = Im of scan q, NC = 2 nscan
 // rounded up to 16 (zero columns); a, k_0 .. k_5 are [nch][count][NC] each.  A coupling block times these columns is a real
@@ -74,14 +75,22 @@ __device__ __forceinline__ void load_y(double (&v)[S + 1], const double *__restr
 // four waves through LDS as ((w0 + w1) + w2) + w3, and one partial of 4 doubles per (channel, row tile, scan) goes to
 // part[((c tm + im) NC/2 + q) 4 + k].  The tree is fixed by count alone; rows beyond count enter as zeros; scans q >= nscan are
 // not written.  fld == nullptr: measure only (the row after the last step) -- the same instructions, so the same bits.
-template <int S, int TN, bool OBS>
+//
+// LAWSON (bspatom_tdse_lawson): the stage of the integrating-factor form.  phs[(c count + n) 2 + {0, 1}] = cos, sin of
+// E[c][n] c_s dt, this stage's part of tdse_phase_kernel's table (s = 1 .. 5); R_s = cos - i sin.  The operand is y_s = R_s .* w_s, w_s what form_y
+// gives: Re and Im of a state sit in neighbouring columns of the B tile, and since NB is even the column parity of idx = tid + r 256 is
+// the lane's, so the partner is __shfl_xor(w, 1).  The epilogue leaves k_s = conj(R_s) .* (-i g), g = f accT + conj(f) accN without
+// the E .* y term: one shuffle serves both the -i exchange and the rotation.  R_0 = 1: stage 0 rotates nothing and reads no phase, so
+// the observing chains t0 .. t3 on y = a(t_n), en, u, up are those of the plain scheme, instruction for instruction.
+template <int S, int TN, bool OBS, bool LAWSON>
 __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
                                                 const int *__restrict__ ent, const double *__restrict__ E,
                                                 const double *__restrict__ D, const double *__restrict__ a,
                                                 double *__restrict__ K, size_t kstride, const double *__restrict__ fld,
-                                                StageCoef cf, double dt, double *__restrict__ part)
+                                                StageCoef cf, double dt, double *__restrict__ part, const double *__restrict__ phs)
 {
     static_assert(!OBS || S == 0, "only stage 0 runs on a(t_n)");
+    constexpr bool ROT = LAWSON && S > 0;                                     // R_0 = 1; phs: this stage's phases [nch][count][2]
     constexpr int NB = 16 * TN, TLDB = NB + 16, BEL = TBK * NB / 256;        // B-tile elements per thread: 1 or 2
     __shared__ double As[TBK * TLDA];
     __shared__ double Bs[TBK * TLDB];
@@ -103,6 +112,7 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
     }
 
     double ra[4], rb[BEL][S + 1];
+    [[maybe_unused]] double rc[ROT ? BEL : 1], rs[ROT ? BEL : 1];                            // cos, +- sin (+ on the Re lane) of the B-tile rows
     // the loads of iteration it = (entry, k-step): A tile 64 x 16 of D_p (either orientation), B tile 16 x NB of y of the other channel
     auto load = [&](int it) {
         const int e = e0 + it / ksteps, k0 = (it % ksteps) * TBK;
@@ -123,6 +133,14 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
             const int idx = tid + r * 256;
             const int kk = idx / NB, col = n0 + idx % NB, gk = k0 + kk;
             load_y<S>(rb[r], a, K, kstride, ((size_t)oc * count + gk) * NC + col, gk < count && col < NC);
+            if constexpr (ROT) {
+                // the phase of row gk of channel oc, from a clamped address like load_y's
+                const bool ok = gk < count;
+                const double *pp = phs + (ok ? ((size_t)oc * count + gk) * 2 : 0);
+                const double pc = pp[0], psn = pp[1];
+                rc[r] = ok ? pc : 0.0;
+                rs[r] = ok ? ((tid & 1) ? -psn : psn) : 0.0;
+            }
         }
         return nrm;
     };
@@ -137,7 +155,14 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
         for (int r = 0; r < BEL; ++r) {
             const int idx = tid + r * 256;
             const int kk = idx / NB, cc = idx % NB;
-            Bs[kk * TLDB + (cc ^ lds_swz(kk))] = form_y<S>(rb[r], cf, dt);
+            if constexpr (ROT) {
+                // y = R w: Re lane cos w_re + sin w_im, Im lane cos w_im - sin w_re
+                const double wv = form_y<S>(rb[r], cf, dt);
+                const double wo = __shfl_xor(wv, 1);
+                Bs[kk * TLDB + (cc ^ lds_swz(kk))] = fma(rs[r], wo, rc[r] * wv);
+            } else {
+                Bs[kk * TLDB + (cc ^ lds_swz(kk))] = form_y<S>(rb[r], cf, dt);
+            }
         }
     };
 
@@ -182,21 +207,37 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
             const int gm = m0 + wave * 16 + (lane >> 4) + 4 * r;
             const bool ok = cok && gm < count;
             const size_t idx = ((size_t)c * count + gm) * NC + col;
-            double v[S + 1];
-            load_y<S>(v, a, K, kstride, idx, ok);
-            const double y = form_y<S>(v, cf, dt);
-            const double en = E[ok ? (size_t)c * count + gm : 0];
+            [[maybe_unused]] double y = 0.0, en = 0.0;
+            if constexpr (!LAWSON || OBS) {
+                double v[S + 1];
+                load_y<S>(v, a, K, kstride, idx, ok);
+                y = form_y<S>(v, cf, dt);
+                en = E[ok ? (size_t)c * count + gm : 0];
+            }
             const double u = accT[0][j][r], w = accN[0][j][r];
             const double up = __shfl_xor(u, 1), wp = __shfl_xor(w, 1);
             // even lane: Re h = E y_re + (f_re u_re - f_im u_im) + (f_re w_re + f_im w_im)
             // odd lane:  Im h = E y_im + (f_re u_im + f_im u_re) + (f_re w_im - f_im w_re)
-            double h = en * y;
-            h = fma(fr, u, h);
+            // LAWSON: the same without E y
+            double h;
+            if constexpr (LAWSON) {
+                h = fr * u;
+            } else {
+                h = en * y;
+                h = fma(fr, u, h);
+            }
             h = fma(fi, up, h);
             h = fma(fr, w, h);
             h = fma(-fi, wp, h);
             const double hp = __shfl_xor(h, 1);
-            if (ok && stepping) Ks[idx] = odd ? -hp : hp;
+            if constexpr (ROT) {
+                // k = conj(R) (-i h) = (cos + i sin)(Im h - i Re h): Re lane cos hp + sin h, Im lane -cos hp + sin h
+                const double *pp = phs + (ok ? ((size_t)c * count + gm) * 2 : 0);
+                const double pc = pp[0], psn = pp[1];
+                if (ok) Ks[idx] = fma(psn, h, (odd ? -pc : pc) * hp);
+            } else {
+                if (ok && stepping) Ks[idx] = odd ? -hp : hp;
+            }
             if constexpr (OBS) {
                 const double yy = y * y;
                 t0 = fma(y, y, t0);
@@ -240,7 +281,18 @@ __global__ __launch_bounds__(256) void tdse_stage_kernel(int count, int NC, int 
                                                         double *__restrict__ K, size_t kstride, const double *__restrict__ fld,
                                                         StageCoef cf, double dt)
 {
-    tdse_stage_body<S, TN, false>(count, NC, nscan, tm, tn, cptr, ent, E, D, a, K, kstride, fld, cf, dt, nullptr);
+    tdse_stage_body<S, TN, false, false>(count, NC, nscan, tm, tn, cptr, ent, E, D, a, K, kstride, fld, cf, dt, nullptr, nullptr);
+}
+
+// the Lawson stage: phs = the phases of stage S (unused by stage 0); E is not read
+template <int S, int TN>
+__global__ __launch_bounds__(256) void tdse_lawson_stage_kernel(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
+                                                               const int *__restrict__ ent, const double *__restrict__ D,
+                                                               const double *__restrict__ a, double *__restrict__ K, size_t kstride,
+                                                               const double *__restrict__ fld, StageCoef cf, double dt,
+                                                               const double *__restrict__ phs)
+{
+    tdse_stage_body<S, TN, false, true>(count, NC, nscan, tm, tn, cptr, ent, nullptr, D, a, K, kstride, fld, cf, dt, nullptr, phs);
 }
 
 // stage 0 with the measuring epilogue: k_0 exactly as tdse_stage_kernel<0, TN> leaves it (fld == nullptr: no k_0, the measurement alone)
@@ -251,7 +303,36 @@ __global__ __launch_bounds__(256) void tdse_observe_kernel(int count, int NC, in
                                                           double *__restrict__ K, const double *__restrict__ fld,
                                                           double *__restrict__ part)
 {
-    tdse_stage_body<0, TN, true>(count, NC, nscan, tm, tn, cptr, ent, E, D, a, K, 0, fld, StageCoef{}, 0.0, part);
+    tdse_stage_body<0, TN, true, false>(count, NC, nscan, tm, tn, cptr, ent, E, D, a, K, 0, fld, StageCoef{}, 0.0, part, nullptr);
+}
+
+// the observing stage 0 of a Lawson step: the measurement of tdse_observe_kernel, k_0 as tdse_lawson_stage_kernel<0, TN> leaves it
+template <int TN>
+__global__ __launch_bounds__(256) void tdse_lawson_observe_kernel(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
+                                                                 const int *__restrict__ ent, const double *__restrict__ E,
+                                                                 const double *__restrict__ D, const double *__restrict__ a,
+                                                                 double *__restrict__ K, const double *__restrict__ fld,
+                                                                 double *__restrict__ part)
+{
+    tdse_stage_body<0, TN, true, true>(count, NC, nscan, tm, tn, cptr, ent, E, D, a, K, 0, fld, StageCoef{}, 0.0, part, nullptr);
+}
+
+// The phase table of a Lawson call, once per call: ph[((s - 1) rows + row) 2 + {0, 1}] = cos, sin of E[row] (c_s dt), s = 1 .. 5,
+// both products in fp64 (cdt[s - 1] = c_s dt comes from the host: one rounding).  The entry of s = 4 (c_4 = 1) also serves the step.
+struct PhaseCoef { double cdt[5]; };
+
+__global__ __launch_bounds__(256) void tdse_phase_kernel(long long rows, const double *__restrict__ E, PhaseCoef pc, double *__restrict__ ph)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows) return;
+    const double en = E[t];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        double sn, cs;
+        sincos(en * pc.cdt[s], &sn, &cs);
+        ph[((size_t)s * rows + t) * 2] = cs;
+        ph[((size_t)s * rows + t) * 2 + 1] = sn;
+    }
 }
 
 // One thread per (scan, channel): the row-tile partials in ascending tile order, written in the caller's layout row[(q nch + c) 4 + k]
@@ -276,11 +357,14 @@ __global__ __launch_bounds__(256) void tdse_obs_reduce_kernel(int nch, int tm, i
 // One thread per (state row, scan): 32 rows x 8 scans per workgroup, the 16 real columns of 8 scans contiguous.  err2[q] (bit
 // pattern of a non-negative double) takes the maximum of |sum_s (d_s - b_s) k_s|^2 with an integer atomic maximum: order-independent.
 // snap (or null): the new amplitudes in the caller's layout [nscan][nch * count] complex.
+// LAWSON: the update and the estimate from the k_s as they are, then a_{n+1} = R_4 .* (the sum), ph4 = the phases of s = 4 [rows][2];
+// what is stored and what the snapshot takes is the rotated value.
 struct StepCoef { double d[6], e[6]; };
 
-__global__ __launch_bounds__(256) void tdse_step_kernel(long long rows, int NC, int nscan, double *__restrict__ a,
-                                                       const double *__restrict__ K, size_t kstride, StepCoef sc, double dt,
-                                                       unsigned long long *__restrict__ err2, double *__restrict__ snap)
+template <bool LAWSON>
+__device__ __forceinline__ void tdse_step_body(long long rows, int NC, int nscan, double *__restrict__ a, const double *__restrict__ K,
+                                               size_t kstride, const StepCoef &sc, double dt, unsigned long long *__restrict__ err2,
+                                               double *__restrict__ snap, const double *__restrict__ ph4)
 {
     __shared__ double smax[4][8];
     const int tid = threadIdx.x, ql = tid & 7, lane = tid & 63, wave = tid >> 6;
@@ -303,7 +387,16 @@ __global__ __launch_bounds__(256) void tdse_step_kernel(long long rows, int NC, 
                 e[ri] = fma(sc.e[j], kj, e[ri]);
             }
             s[ri] = fma(dt, s[ri], a[idx + ri]);
-            a[idx + ri] = s[ri];
+            if constexpr (!LAWSON) a[idx + ri] = s[ri];
+        }
+        if constexpr (LAWSON) {
+            // (cos - i sin)(s_re + i s_im)
+            const double pc = ph4[(size_t)row * 2], psn = ph4[(size_t)row * 2 + 1];
+            const double re = fma(psn, s[1], pc * s[0]), im = fma(-psn, s[0], pc * s[1]);
+            s[0] = re;
+            s[1] = im;
+            a[idx] = re;
+            a[idx + 1] = im;
         }
         m2 = fma(e[0], e[0], e[1] * e[1]);
         if (snap && q < nscan) {
@@ -327,6 +420,21 @@ __global__ __launch_bounds__(256) void tdse_step_kernel(long long rows, int NC, 
         const int qq = blockIdx.y * 8 + tid;
         if (qq < nscan && m > 0.0) atomicMax(&err2[qq], (unsigned long long)__double_as_longlong(m));
     }
+}
+
+__global__ __launch_bounds__(256) void tdse_step_kernel(long long rows, int NC, int nscan, double *__restrict__ a,
+                                                       const double *__restrict__ K, size_t kstride, StepCoef sc, double dt,
+                                                       unsigned long long *__restrict__ err2, double *__restrict__ snap)
+{
+    tdse_step_body<false>(rows, NC, nscan, a, K, kstride, sc, dt, err2, snap, nullptr);
+}
+
+__global__ __launch_bounds__(256) void tdse_lawson_step_kernel(long long rows, int NC, int nscan, double *__restrict__ a,
+                                                              const double *__restrict__ K, size_t kstride, StepCoef sc, double dt,
+                                                              unsigned long long *__restrict__ err2, double *__restrict__ snap,
+                                                              const double *__restrict__ ph4)
+{
+    tdse_step_body<true>(rows, NC, nscan, a, K, kstride, sc, dt, err2, snap, ph4);
 }
 
 // caller's layout a[((q nch + c) count + n) 2 + ri]  <->  working layout; pad columns are written as zeros
@@ -360,15 +468,22 @@ static int launch_stage_s(const TdseDims &d, const TdseBufs &w, const double *fl
     const int tm = (d.count + TBM - 1) / TBM;
     const size_t ks = (size_t)d.nch * d.count * d.NC;
     KScope ks_(KS_TDSE, st);
-    if (d.NC == 16) {
-        const long long grid = (long long)d.nch * tm;
-        if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL((tdse_stage_kernel<S, 1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, 1, w.cptr, w.ent,
+    const int tn = d.NC == 16 ? 1 : (d.NC + 31) / 32;
+    const long long grid = (long long)d.nch * tm * tn;
+    if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    if (w.ph) {
+        // Lawson: the phases of stage S (stage 0 has none)
+        const double *phs = S > 0 ? w.ph + (size_t)(S - 1) * d.nch * d.count * 2 : nullptr;
+        if (d.NC == 16)
+            hipLaunchKernelGGL((tdse_lawson_stage_kernel<S, 1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr,
+                               w.ent, w.D, w.a, w.K, ks, fld, cf, dt, phs);
+        else
+            hipLaunchKernelGGL((tdse_lawson_stage_kernel<S, 2>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr,
+                               w.ent, w.D, w.a, w.K, ks, fld, cf, dt, phs);
+    } else if (d.NC == 16) {
+        hipLaunchKernelGGL((tdse_stage_kernel<S, 1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent,
                            w.E, w.D, w.a, w.K, ks, fld, cf, dt);
     } else {
-        const int tn = (d.NC + 31) / 32;
-        const long long grid = (long long)d.nch * tm * tn;
-        if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((tdse_stage_kernel<S, 2>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent,
                            w.E, w.D, w.a, w.K, ks, fld, cf, dt);
     }
@@ -381,18 +496,15 @@ int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld,
     const int tm = (d.count + TBM - 1) / TBM;
     {
         KScope ks_(KS_TDSE, st);
-        if (d.NC == 16) {
-            const long long grid = (long long)d.nch * tm;
-            if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
-            hipLaunchKernelGGL((tdse_observe_kernel<1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, 1, w.cptr, w.ent,
-                               w.E, w.D, w.a, w.K, fld, w.part);
-        } else {
-            const int tn = (d.NC + 31) / 32;
-            const long long grid = (long long)d.nch * tm * tn;
-            if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
-            hipLaunchKernelGGL((tdse_observe_kernel<2>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent,
-                               w.E, w.D, w.a, w.K, fld, w.part);
-        }
+        const int tn = d.NC == 16 ? 1 : (d.NC + 31) / 32;
+        const long long grid = (long long)d.nch * tm * tn;
+        if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+        // a Lawson step's stage 0 leaves another k_0; a measurement alone (fld null) is the same kernel for both schemes
+        const bool lawson = w.ph && fld;
+        auto kern = d.NC == 16 ? (lawson ? tdse_lawson_observe_kernel<1> : tdse_observe_kernel<1>)
+                               : (lawson ? tdse_lawson_observe_kernel<2> : tdse_observe_kernel<2>);
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent, w.E, w.D, w.a, w.K, fld,
+                           w.part);
         BSP_HIP(hipGetLastError());
     }
     const long long blocks = ((long long)d.nscan * d.nch + 255) / 256;
@@ -417,8 +529,25 @@ int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field
     const long long gx = (rows + 31) / 32;
     const int gy = (d.NC / 2 + 7) / 8;
     if (gx > 0x7fffffffLL || gy > 65535) return BSP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(tdse_step_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
-                       (size_t)rows * d.NC, sc, dt, w.err2, d_snap);
+    if (w.ph)
+        hipLaunchKernelGGL(tdse_lawson_step_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
+                           (size_t)rows * d.NC, sc, dt, w.err2, d_snap, w.ph + (size_t)3 * rows * 2);
+    else
+        hipLaunchKernelGGL(tdse_step_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
+                           (size_t)rows * d.NC, sc, dt, w.err2, d_snap);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+int launch_tdse_phases(const TdseDims &d, const double *d_E, double dt, double *d_ph, hipStream_t st)
+{
+    const double c[5] = {2.0 / 9.0, 1.0 / 3.0, 3.0 / 4.0, 1.0, 5.0 / 6.0};      // c_1 .. c_5: the doubles nearest the fractions
+    PhaseCoef pc;
+    for (int s = 0; s < 5; ++s) pc.cdt[s] = c[s] * dt;
+    const long long rows = (long long)d.nch * d.count, blocks = (rows + 255) / 256;
+    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    KScope ks_(KS_TDSE, st);
+    hipLaunchKernelGGL(tdse_phase_kernel, dim3((unsigned)blocks), dim3(256), 0, st, rows, d_E, pc, d_ph);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }

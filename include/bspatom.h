@@ -243,7 +243,7 @@ int bspatom_wavefunctions_dev(bspatom_problem *p, int l0, int nl, int n0, int co
  * k_s = -i H(t_n + c_s dt) y_s, c = (0, 2/9, 1/3, 3/4, 1, 5/6); a_{n+1} = a_n + dt sum_s d_s k_s with the 5th-order weights
  * d = (47/450, 0, 12/25, 32/225, 1/30, 6/25); err[q] = max over steps, channels, states of dt |sum_s (d_s - b_s) k_s|,
  * b = (1/9, 0, 9/20, 16/45, 1/12, 0).  No step-size control (a result is a function of its inputs alone); stability, dt max|E|, is the
- * caller's business; amplitudes are not checked for finiteness.
+ * caller's business (bspatom_tdse_lawson below removes that bound); amplitudes are not checked for finiteness.
  * The library never evaluates a pulse: field[((n*6 + s)*nscan + q)*2 + {0,1}] = Re, Im of f_q(t0 + (n + c_s) dt).
  *   a    [((q*nch + c)*count + n)*2 + {0,1}] (complex128 of shape (nscan, nch, count)); in: a(t0), out: a(t0 + nsteps dt)
  *   snap the amplitudes after steps snap_every, 2 snap_every, .. in the same layout one after the other (nsteps / snap_every of them);
@@ -296,6 +296,40 @@ int bspatom_tdse_observe_dev(bspatom_problem *p, int nch, int count, const doubl
                              const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
                              double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev);
 
+/* The same run with Lawson (integrating-factor) steps of the same tableau: within a step b = exp(+i E tau) a is propagated, so the
+ * free evolution is exact and the stability limit comes from |f| ||D|| alone, not from dt max|E|.  The 18 arguments, nobs, the row
+ * layout, the field table, the staging under tdse_stage_mb and BSPATOM_ERR_ARG are bspatom_tdse_observe's; obs_every = 0 with obs NULL
+ * propagates only.  a, snap and the rows are Schroedinger-picture amplitudes at step boundaries, as in the calls above.
+ * The scheme, with A, d, b the tableau above and c = (0, 2/9, 1/3, 3/4, 1, 5/6):
+ *   theta_s[c][n] = E[c][n] * (c_s * dt), both products in fp64, c_s the double nearest the fraction;
+ *   R_s = cos theta_s - i sin theta_s from the device's fp64 sincos;  R_0 = 1 exactly (stage 0 rotates nothing)
+ *   w_s = a_n + dt sum_{j<s} A_sj kappa_j                      (the sums of the plain scheme, in the same order)
+ *   y_s = R_s .* w_s                                           (the operand of the products)
+ *   g_s[c] = sum_{p: cf[p]=c} f_q(t_n + c_s dt) D_p^T y_s[ci[p]] + sum_{p: ci[p]=c} conj(f_q) D_p y_s[cf[p]]
+ *   kappa_s = conj(R_s) .* (-i g_s)                            (no E .* y term)
+ *   a_{n+1} = R_4 .* (a_n + dt sum_s d_s kappa_s)              (c_4 = 1: R_4 = exp(-i E dt))
+ *   err[q] = max over steps, channels, states of dt |sum_s (d_s - b_s) kappa_s|
+ * One small kernel builds the table of the R_s (five complex entries per state, s = 1 .. 5; the entry of s = 4 also serves the step)
+ * once per call from E on the problem's stream; then seven launches per step, eight on an observed one, as above, with the same
+ * products and the same reads of D; every element pays one complex rotation in the operand load and one in the epilogue.
+ * Guarantees:
+ *   results are run-to-run bit-identical (no floating-point atomics, no split of a sum, no summation order that depends on nscan, nch,
+ *   the pair list, the snapshots, obs_every or the staging bound); a scan does not depend on the other scans of the call;
+ *   a snapshot equals the result of the shorter run, and a run continued from a snapshot equals the long run;
+ *   a, snap and err do not depend on obs_every or the staging bound;
+ *   an observed row has the bits of a bspatom_tdse_observe call with nsteps = 0 on the same amplitudes;
+ *   with npairs = 0, err is exactly 0 and |a| changes only by the rounding of the rotations;
+ *   a call with nsteps = 0 returns what bspatom_tdse_observe* returns, bit for bit.
+ * What the scheme does not give: accuracy still needs a dt that resolves the field and the Bohr frequencies E_i - E_j between
+ * populated, coupled states.  What is removed is the stability bound from states that carry no population.  The result is not that
+ * of bspatom_tdse_propagate bit for bit: both are 5th-order approximations of the same solution. */
+int bspatom_tdse_lawson(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf,
+                        const double *D, int nscan, int nsteps, double dt, const double *field, double *a, int snap_every,
+                        double *snap, double *err, int obs_every, double *obs);
+int bspatom_tdse_lawson_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                            const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                            double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev);
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
@@ -311,7 +345,7 @@ int bspatom_last_timing(const bspatom_problem *p, double ms[6]);
  * times and launch counts per slot since the previous call into ms[] / launches[] (cap >= the slot count, which it returns)
  * and forgets them.  Slots: 0 rank-128 update (syr2k), 1 symm, 2 panel QR, 3 the small products of the panel chain,
  * 4 sb2sb_mfma_kernel, 5 sbr_rows_kernel<8> / <16> (sb16st_kernel with BSP_SB16_ROWS=0), 6 batched bisection, 7 Cholesky + standard form,
- * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel and tdse_observe_kernel (tdse.hip);
+ * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel and tdse_observe_kernel, their Lawson variants and tdse_phase_kernel (tdse.hip);
  * bspatom_kernel_slot_name(i) names them.  Launches on different streams overlap: the sums are sums of launch durations, not wall time. */
 int bspatom_kernel_times(double *ms, int32_t *launches, int cap);
 const char *bspatom_kernel_slot_name(int slot);
