@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -86,6 +86,8 @@ def lib():
         L.bspatom_tdse_observe_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
         L.bspatom_tdse_lawson.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
         L.bspatom_tdse_lawson_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
+        L.bspatom_tdse_static.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+        L.bspatom_tdse_static_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -497,6 +499,69 @@ class Problem:
                                            float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
                                            C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
                                            C.c_void_p(obs_ptr) if obs_ptr else None), "bspatom_tdse_lawson_dev")
+        return err
+
+    @staticmethod
+    def _tdse_static(static, count=None):
+        """(si, sf, skind, W or None) of a static argument (spairs, skind, W); None or empty lists: no static block"""
+        if static is None:
+            return (np.zeros(0, dtype=np.int32),) * 3 + (None,)
+        spairs, skind, W = static
+        si, sf = Problem._tdse_pairs(spairs)
+        skind = np.ascontiguousarray(np.asarray(skind, dtype=np.int32).reshape(-1))
+        if len(skind) != len(si):
+            raise ValueError("static: %d pairs but %d kinds" % (len(si), len(skind)))
+        if count is not None:
+            W = np.ascontiguousarray(W, dtype=np.float64).reshape(len(si), count, count)
+        return si, sf, skind, W
+
+    def tdse_static(self, E, pairs, D, a0, field, dt, static, scheme=1, obs_every=0, snap_every=0):
+        """tdse_observe / tdse_lawson with static blocks beside the driven couplings (bspatom_tdse_static): static = (spairs, skind, W),
+        spairs [(si, sf)] channel positions (si == sf allowed: an in-channel block), skind[j] 0 (+ W_j^T a_si) or 1 (- i W_j^T a_si,
+        an absorber when W_j is symmetric positive), W (nstat, count, count), W[j, i, f] between state i of si and state f of sf
+        (operator_matrix's layout; host.tdse_absorber builds the absorber).  A block acts on channel sf alone, without a conjugate
+        partner and without the field.  scheme: 1 = Lawson steps, 0 = the plain tableau.  Returns (a, err[, obs][, snaps]) as
+        tdse_lawson does; obs: (nobs, nscan, nch, 6), [..., :4] as tdse_observe, [..., 4:] = Re, Im of s_c = conj(a_c) . S_c
+        (host.tdse_static_rates, host.tdse_yield)."""
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        nch, count = E.shape
+        ci, cf = self._tdse_pairs(pairs)
+        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
+        si, sf, skind, W = self._tdse_static(static, count)
+        a = np.array(a0, dtype=np.complex128, order="C")
+        one = a.ndim == 2
+        a = np.ascontiguousarray(a.reshape(-1, nch, count))
+        nscan = a.shape[0]
+        field = np.ascontiguousarray(field, dtype=np.complex128)
+        nsteps = field.shape[0] if field.ndim == 3 else 0
+        assert field.shape == (nsteps, 6, nscan), (field.shape, nscan)
+        err = np.zeros(nscan)
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 6)) if obs_every > 0 else None
+        ns = len(si)
+        _chk(lib().bspatom_tdse_static(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
+                                       _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
+                                       _p(snaps), _p(err), obs_every, _p(obs), int(scheme), ns, _p(si) if ns else None,
+                                       _p(sf) if ns else None, _p(skind) if ns else None, _p(W) if ns else None), "bspatom_tdse_static")
+        if one:
+            a = a[0]
+        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+
+    def tdse_static_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, static, scheme=1, obs_every=0,
+                        obs_ptr=None, snap_every=0, snap_ptr=None):
+        """tdse_static on device memory: the arguments of tdse_lawson_dev, static = (spairs, skind, W_ptr) with the nstat * count * count
+        doubles of W at W_ptr, and rows of 6 doubles per (scan, channel) at obs_ptr.  Returns err (nscan,) when the result is there."""
+        ci, cf = self._tdse_pairs(pairs)
+        si, sf, skind, W_ptr = self._tdse_static(static)
+        ns = len(si)
+        err = np.zeros(nscan)
+        _chk(lib().bspatom_tdse_static_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
+                                           _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
+                                           float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
+                                           C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
+                                           C.c_void_p(obs_ptr) if obs_ptr else None, int(scheme), ns, _p(si) if ns else None,
+                                           _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None),
+             "bspatom_tdse_static_dev")
         return err
 
     def early_vector_state(self):

@@ -1,6 +1,7 @@
-// capi_tdse.hip -- bspatom_tdse_propagate / _dev, bspatom_tdse_observe / _dev and bspatom_tdse_lawson / _dev (include/bspatom.h): the
-// argument checks, the per-channel entry lists, the working buffers and the step loop of tdse.hip.  One code path: propagate is observe
-// without rows, and the Lawson scheme is a flag that adds the phase table.  The problem handle gives the device and the stream; nothing of a solve is read.
+// capi_tdse.hip -- bspatom_tdse_propagate / _dev, bspatom_tdse_observe / _dev, bspatom_tdse_lawson / _dev and bspatom_tdse_static / _dev
+// (include/bspatom.h): the argument checks, the per-channel entry lists, the working buffers and the step loop of tdse.hip.  One code
+// path: propagate is observe without rows, the Lawson scheme is a flag that adds the phase table, and the static call is either with
+// static entries behind the driven ones and rows of 6.  The problem handle gives the device and the stream; nothing of a solve is read.
 #include <cmath>
 #include "capi_internal.h"
 
@@ -23,23 +24,42 @@ bool args_ok(const bspatom_problem *p, int nch, int count, const double *E, int 
     return true;
 }
 
+// the static blocks of bspatom_tdse_static (host lists; W on the device once run_dev has it); null where a call has none by design
+struct Static { int n; const int32_t *si, *sf, *kind; const double *W; };
+
+bool static_args_ok(int nch, int scheme, int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W)
+{
+    if (scheme < 0 || scheme > 1 || nstat < 0) return false;
+    if (nstat > 0 && (!si || !sf || !skind || !W)) return false;
+    for (int j = 0; j < nstat; ++j)
+        if (si[j] < 0 || si[j] >= nch || sf[j] < 0 || sf[j] >= nch || skind[j] < 0 || skind[j] > 1) return false;
+    return true;
+}
+
 // everything of a call that lives on the device besides the caller's arrays
 struct Plan {
     TdseDims d;
     DevArray<int> cptr, ent;
     DevArray<double> aw, K, part, ph;
     DevArray<unsigned long long> err2;
-    size_t rows = 0, odbl = 0;                 // odbl: doubles of one row of observables, [nscan][nch][4]
+    size_t rows = 0, odbl = 0;                 // odbl: doubles of one row of observables, [nscan][nch][ow]
     bool observing = false;
-    int prepare(bspatom_problem *p, int nch, int count, int nscan, int npairs, const int32_t *ci, const int32_t *cf, bool observing_)
+    int ow = 4, nstat = 0;                     // ow = 6: a bspatom_tdse_static call; nstat: its static blocks
+    // stc: null (the rows of 4 of the other calls), or the static blocks of a bspatom_tdse_static call (rows of 6, stc->n may be 0)
+    int prepare(bspatom_problem *p, int nch, int count, int nscan, int npairs, const int32_t *ci, const int32_t *cf, bool observing_,
+                const Static *stc = nullptr)
     {
         d = {nch, count, nscan, tdse_columns(nscan)};
         rows = (size_t)nch * count;
-        odbl = (size_t)4 * nscan * nch;
+        ow = stc ? 6 : 4;
+        nstat = stc ? stc->n : 0;
+        odbl = (size_t)ow * nscan * nch;
         observing = observing_;
-        // channel c's entries in ascending p: (p, cf[p], 1) where ci[p] = c, (p, ci[p], 0) where cf[p] = c
-        std::vector<int> cp(nch + 1, 0), en((size_t)6 * npairs + 3, 0);
+        // channel c's entries in ascending p: (p, cf[p], 1) where ci[p] = c, (p, ci[p], 0) where cf[p] = c; behind them its static
+        // entries in ascending j: (j, si[j], 2 + skind[j]) where sf[j] = c
+        std::vector<int> cp(nch + 1, 0), en((size_t)6 * npairs + (size_t)3 * nstat + 3, 0);
         for (int q = 0; q < npairs; ++q) { ++cp[ci[q] + 1]; ++cp[cf[q] + 1]; }
+        for (int j = 0; j < nstat; ++j) ++cp[stc->sf[j] + 1];
         for (int c = 0; c < nch; ++c) cp[c + 1] += cp[c];
         std::vector<int> at(cp.begin(), cp.end() - 1);
         for (int q = 0; q < npairs; ++q) {
@@ -48,12 +68,16 @@ struct Plan {
             e = &en[(size_t)3 * at[cf[q]]++];
             e[0] = q; e[1] = ci[q]; e[2] = 0;
         }
+        for (int j = 0; j < nstat; ++j) {
+            int *e = &en[(size_t)3 * at[stc->sf[j]]++];
+            e[0] = j; e[1] = stc->si[j]; e[2] = 2 + stc->kind[j];
+        }
         int rc;
         if ((rc = cptr.put(cp.data(), cp.size())) || (rc = ent.put(en.data(), en.size())) || (rc = aw.alloc(rows * d.NC)) ||
             (rc = K.alloc(6 * rows * d.NC)) || (rc = err2.alloc(nscan)))
             return rc;
-        // the observing kernel's partials: one of 4 doubles per (channel, row tile of 64 states, scan slot)
-        if (observing && (rc = part.alloc((size_t)nch * ((count + 63) / 64) * (d.NC / 2) * 4))) return rc;
+        // the observing kernel's partials: one of 4 doubles (6 with static blocks) per (channel, row tile of 64 states, scan slot)
+        if (observing && (rc = part.alloc((size_t)nch * ((count + 63) / 64) * (d.NC / 2) * (nstat > 0 ? 6 : 4)))) return rc;
         return HIP_RC(hipMemsetAsync(err2.p, 0, (size_t)nscan * sizeof(unsigned long long), p->st));
     }
     // the Lawson scheme: the phase table from the energies on the device, before bufs()
@@ -62,7 +86,11 @@ struct Plan {
         const int rc = ph.alloc((size_t)10 * rows);
         return rc ? rc : launch_tdse_phases(d, d_E, dt, ph.p, p->st);
     }
-    TdseBufs bufs(const double *d_E, const double *d_D) const { return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p, observing ? part.p : nullptr, ph.p}; }
+    // d_W: the static blocks on the device (null without any: the kernels of the other calls run, whatever ow is)
+    TdseBufs bufs(const double *d_E, const double *d_D, const double *d_W = nullptr) const
+    {
+        return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p, observing ? part.p : nullptr, ph.p, nstat > 0 ? d_W : nullptr, ow};
+    }
     // steps n0 .. n1-1; d_field: the table from step n0 on; d_snap (or null): where snapshot number s0 (from 0) goes, the later ones behind it;
     // d_obs (or null): where row j0 goes (row j = the amplitudes before step j obs_every), the later ones behind it
     int run(bspatom_problem *p, const TdseBufs &w, int n0, int n1, double dt, const double *d_field, int snap_every, double *d_snap, int s0,
@@ -96,7 +124,7 @@ struct Plan {
 // obs_every = 0: no observables (obs null).  Otherwise rows for the steps 0, obs_every, .. < nsteps, then the row of the final amplitudes.
 int run_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci, const int32_t *cf,
             const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev, double *a_dev, int snap_every,
-            double *snap_dev, double *err, int obs_every, double *obs_dev, bool lawson)
+            double *snap_dev, double *err, int obs_every, double *obs_dev, bool lawson, const Static *stc = nullptr)
 {
     const bool observing = obs_every > 0;
     if (nsteps == 0 && !observing) {
@@ -105,10 +133,10 @@ int run_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npa
     }
     BSP_HIP(hipSetDevice(p->device));
     Plan pl;
-    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf, observing);
+    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf, observing, stc);
     if (!rc) rc = launch_tdse_pack(pl.d, a_dev, pl.aw.p, p->st);
     if (!rc && lawson && nsteps > 0) rc = pl.phases(p, E_dev, dt);
-    const TdseBufs w = pl.bufs(E_dev, D_dev);
+    const TdseBufs w = pl.bufs(E_dev, D_dev, stc ? stc->W : nullptr);
     if (!rc) rc = pl.run(p, w, 0, nsteps, dt, field_dev, snap_every, snap_dev, 0, obs_every, obs_dev, 0);
     if (!rc && observing) {
         const size_t last = nsteps > 0 ? (size_t)(nsteps - 1) / obs_every + 1 : 0;
@@ -121,7 +149,7 @@ int run_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npa
 
 int run_host(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf, const double *D,
              int nscan, int nsteps, double dt, const double *field, double *a, int snap_every, double *snap, double *err, int obs_every,
-             double *obs, bool lawson)
+             double *obs, bool lawson, const Static *stc = nullptr)
 {
     const bool observing = obs_every > 0;
     if (nsteps == 0 && !observing) {
@@ -130,7 +158,7 @@ int run_host(bspatom_problem *p, int nch, int count, const double *E, int npairs
     }
     BSP_HIP(hipSetDevice(p->device));
     const size_t rows = (size_t)nch * count, adbl = rows * nscan * 2, fdbl = (size_t)12 * nscan;     // doubles of a snapshot, of a step's field
-    const size_t odbl = (size_t)4 * nscan * nch;                                                      // of a row of observables
+    const size_t odbl = (size_t)(stc ? 6 : 4) * nscan * nch;                                          // of a row of observables
     // steps per group: the field of g steps, the (at most g / snap_every + 1) snapshots and the (at most (g - 1) / obs_every + 1)
     // observed steps among them within the bound, one step at least
     const bool snapping = snap && snap_every > 0;
@@ -148,17 +176,18 @@ int run_host(bspatom_problem *p, int nch, int count, const double *E, int npairs
     }
     if (g < 1) g = 1;
     Plan pl;
-    DevArray<double> dE, dD, da, dfield, dsnap, dobs;
-    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf, observing);
+    DevArray<double> dE, dD, dW, da, dfield, dsnap, dobs;
+    int rc = pl.prepare(p, nch, count, nscan, npairs, ci, cf, observing, stc);
     if (!rc) rc = dE.put(E, rows);
     if (!rc && npairs > 0) rc = dD.put(D, (size_t)npairs * count * count);
+    if (!rc && stc && stc->n > 0) rc = dW.put(stc->W, (size_t)stc->n * count * count);       // once per call, outside the bound like D
     if (!rc) rc = da.put(a, adbl);
     if (!rc && nsteps > 0) rc = dfield.alloc(g * fdbl);
     if (!rc && snapping) rc = dsnap.alloc(snaps_of(g) * adbl);
     if (!rc && observing) rc = dobs.alloc((obs_of(g) > 0 ? obs_of(g) : 1) * odbl);
     if (!rc) rc = launch_tdse_pack(pl.d, da.p, pl.aw.p, p->st);
     if (!rc && lawson && nsteps > 0) rc = pl.phases(p, dE.p, dt);
-    const TdseBufs w = pl.bufs(dE.p, dD.p);
+    const TdseBufs w = pl.bufs(dE.p, dD.p, dW.p);
     for (int n0 = 0; !rc && n0 < nsteps; n0 += (int)g) {
         const int n1 = n0 + (int)g < nsteps ? n0 + (int)g : nsteps;
         rc = HIP_RC(hipMemcpyAsync(dfield.p, field + (size_t)n0 * fdbl, (size_t)(n1 - n0) * fdbl * sizeof(double), hipMemcpyHostToDevice, p->st));
@@ -242,4 +271,29 @@ extern "C" int bspatom_tdse_lawson(bspatom_problem *p, int nch, int count, const
     if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap) || !obs_args_ok(obs_every, obs))
         return BSP_ERR_ARG;
     return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs, true);
+}
+
+extern "C" int bspatom_tdse_static_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                                       const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                                       double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev,
+                                       int scheme, int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W_dev)
+{
+    if (!args_ok(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev) ||
+        !obs_args_ok(obs_every, obs_dev) || !static_args_ok(nch, scheme, nstat, si, sf, skind, W_dev))
+        return BSP_ERR_ARG;
+    const Static stc = {nstat, si, sf, skind, W_dev};
+    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, obs_every, obs_dev,
+                   scheme == 1, &stc);
+}
+
+extern "C" int bspatom_tdse_static(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
+                                   const int32_t *cf, const double *D, int nscan, int nsteps, double dt, const double *field, double *a,
+                                   int snap_every, double *snap, double *err, int obs_every, double *obs, int scheme, int nstat,
+                                   const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W)
+{
+    if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap) || !obs_args_ok(obs_every, obs) ||
+        !static_args_ok(nch, scheme, nstat, si, sf, skind, W))
+        return BSP_ERR_ARG;
+    const Static stc = {nstat, si, sf, skind, W};
+    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs, scheme == 1, &stc);
 }

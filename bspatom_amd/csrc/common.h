@@ -306,6 +306,11 @@ struct TdseBufs {
     unsigned long long *err2;    // [nscan] bit patterns of max |sum_s (d_s - b_s) k_s|^2, zeroed by the caller
     double *part;                // observables: [nch][ceil(count / 64)][NC / 2][4] partials of the row tiles (null: nothing is observed)
     const double *ph;            // Lawson steps: [5][nch][count][2] cos, sin of E c_s dt, s = 1 .. 5 (launch_tdse_phases); null: the plain scheme
+    // bspatom_tdse_static: W = [nstat][count][count] static blocks, whose entries follow a channel's driven ones in ent, [3e] = j,
+    // [3e+1] = si[j], [3e+2] = 2 + skind[j], and part is 6 doubles wide (null: no static entry, the kernels of the other calls);
+    // ow = doubles per (scan, channel) of a row of observables, 4 or 6
+    const double *W = nullptr;
+    int ow = 4;
 };
 extern const double TDSE_A[6][5], TDSE_D[6], TDSE_B[6];
 int tdse_columns(int nscan);
@@ -318,6 +323,10 @@ int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field
 int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *d_field, double *d_row, hipStream_t st);
 // the phase table of bspatom_tdse_lawson from d_E, once per call
 int launch_tdse_phases(const TdseDims &d, const double *d_E, double dt, double *d_ph, hipStream_t st);
+// tdse_static.hip: what the launchers above launch when w.W is set (stage S, the observing stage 0) or w.ow is 6 (the reduction)
+int launch_tdse_static_stage(int S, const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st);
+int launch_tdse_static_observe(const TdseDims &d, const TdseBufs &w, const double *fld, bool lawson, hipStream_t st);
+int launch_tdse_static_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st);
 int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st);
 int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st);
 

@@ -535,6 +535,49 @@ def tdse_system(prob, channels, n0, count, kind_pi=1, mph=0):
     return E, pairs, D
 
 
+def cap_profile(r, r0, eta, power=2):
+    """The complex absorbing potential's W(r) = eta (r - r0)^power beyond r0, 0 inside (the Hamiltonian gains -i W(r))."""
+    import numpy as np
+    r = np.asarray(r, dtype=np.float64)
+    return float(eta) * np.where(r > r0, r - r0, 0.0) ** power
+
+
+def tdse_absorber(prob, channels, n0, count, g):
+    """The static argument (spairs, skind, W) of Problem.tdse_static for an absorber -i g(r) on the states n0 .. n0+count-1 (1-based)
+    of `channels`, the list of (l, m) given to tdse_system: one in-channel block of kind 1 per channel, W[c, i, f] = <f| g |i>, from
+    ONE operator_matrix call.  g: a callable of the array of points or an array on the quadrature grid (cap_profile)."""
+    import numpy as np
+    W = operator_matrix(prob, [(l, l) for l, _ in channels], [(g, False)], n0, count, n0, count)
+    nch = len(channels)
+    return [(c, c) for c in range(nch)], np.ones(nch, dtype=np.int32), W
+
+
+def tdse_static_rates(obs):
+    """d pop_c/dt from the static blocks, 2 Im s_c, (nobs, nscan, nch), of the rows obs (nobs, nscan, nch, 6) of Problem.tdse_static;
+    for a symmetric in-channel absorber that is -2 <W>_c."""
+    import numpy as np
+    obs = np.asarray(obs, dtype=np.float64)
+    if obs.ndim != 4 or obs.shape[-1] != 6:
+        raise ValueError("tdse_static_rates needs the rows of tdse_static, (nobs, nscan, nch, 6), got shape %s" % (obs.shape,))
+    return 2.0 * obs[..., 5]
+
+
+def tdse_yield(obs, dt, nsteps, obs_every):
+    """The population the static blocks removed from each channel during the run, (nscan, nch): the integral of -2 Im s_c over the
+    uniform time grid of the rows (trapezoid, spacing obs_every dt).  With an absorber, the ionisation yield per channel; yield.sum(-1)
+    + norm(T) = norm(0) up to the quadrature error.  The rows form a uniform grid only when obs_every divides nsteps."""
+    import numpy as np
+    if obs_every < 1 or nsteps < 0:
+        raise ValueError("tdse_yield needs nsteps >= 0 and obs_every >= 1")
+    if nsteps % obs_every:
+        raise ValueError("tdse_yield needs rows on a uniform grid: obs_every = %d does not divide nsteps = %d" % (obs_every, nsteps))
+    rate = -tdse_static_rates(obs)
+    if rate.shape[0] != nsteps // obs_every + 1:
+        raise ValueError("%d rows do not belong to nsteps = %d, obs_every = %d" % (rate.shape[0], nsteps, obs_every))
+    h = float(dt) * obs_every
+    return h * (rate.sum(axis=0) - 0.5 * (rate[0] + rate[-1]))
+
+
 def write_tdse_coeffs(path, a):
     """`CSs/TDSE_COEFFs.dat` as READ_TDCOEFF reads it (ReadInputs.f90:453-467): one list-directed record `n Re Im` per state, in the
     row order of MatElem_All.dat (channel position * count + n); a: complex (nch, count) or (nvec,); 17 significant digits, so

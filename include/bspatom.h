@@ -330,6 +330,51 @@ int bspatom_tdse_lawson_dev(bspatom_problem *p, int nch, int count, const double
                             const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
                             double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev);
 
+/* The same run with static blocks beside the driven couplings: terms of the Hamiltonian that the field does not multiply and that enter
+ * without a conjugate partner -- a complex absorbing potential -i W(r) (in-channel blocks <n| W |n'> of bspatom_operator_matrix,
+ * l_ini = l_fin), a static field, a perturbing potential, a second, constant drive.  The first 18 arguments are bspatom_tdse_observe's,
+ * unchanged in meaning; scheme: 0 = the plain tableau of bspatom_tdse_propagate, 1 = the Lawson steps of bspatom_tdse_lawson.
+ *   W[(j*count + i)*count + f], j < nstat: static block j, i a state of channel si[j], f of sf[j] (bspatom_operator_matrix's layout with
+ *   count_ini = count_fin = count); si[j] == sf[j] is allowed and is the main case.  Block j adds to the right-hand side of i da/dt of
+ *   channel sf[j] ONLY:   skind[j] = 0:  + W_j^T a_si[j]        skind[j] = 1:  - i W_j^T a_si[j],     (W^T a)[f] = sum_i W[i][f] a[i].
+ *   No conjugate partner is added: a Hermitian cross-channel term is two blocks, (si, sf, W) and (sf, si, W^T).  Symmetry and sign are
+ *   the caller's business and are not checked (a symmetric positive kind-1 block absorbs, its negative feeds).  Static blocks do not
+ *   see the field.  Several blocks on one channel add, in ascending j, after the channel's driven entries.
+ * With S(y) the sum of these terms:  plain scheme  k_s = -i (E y_s + driven terms + S(y_s));  Lawson  g_s gains S(y_s), y_s = R_s w_s,
+ * kappa_s = conj(R_s) (-i g_s) as before: the free phases stay exact, and dt ||W|| joins dt |f| ||D|| as the caller's stability business
+ * (for the plain scheme, beside dt max|E|).
+ * Rows: nobs as in bspatom_tdse_observe, obs[((j*nscan + q)*nch + c)*6 + k]:
+ *     k = 0 .. 3  as in bspatom_tdse_observe
+ *     k = 4, 5    Re, Im of s_c = sum_f conj(a_c[f]) S_c[f], S_c the static right-hand side of channel c evaluated on a(t_n)
+ *   sum_c Re s_c is the energy of the Hermitian static terms; d pop_c/dt from the static terms is 2 Im s_c, for a symmetric in-channel
+ *   absorber -2 <W>_c: the norm lost per channel, integrated over the rows, is the ionisation yield.  nsteps = 0 is a real call, as in
+ *   bspatom_tdse_observe: one row measuring a as given.
+ * How: a channel's entry list carries its static entries behind the driven ones; -i W^T y = W^T (-i y), and -i y is the Re/Im column
+ * exchange with a sign, done while the operand tile is staged, so both kinds run the same real product into ONE more accumulator,
+ * which the epilogue adds after the driven terms.  On an observed step stage 0 also chains conj(a) . (that accumulator): s_c, from
+ * what the kernel already holds, with no snapshot and no second read of W.  The launches per step are those of the scheme.
+ * Guarantees:
+ *   1. with nstat = 0, a, snap, err and k = 0 .. 3 of every row have the bits of bspatom_tdse_observe (scheme 0) or bspatom_tdse_lawson
+ *      (scheme 1) -- the same kernels run -- and k = 4, 5 are exactly 0;
+ *   2. with static blocks, k = 0 .. 3 of a row have the bits of a bspatom_tdse_observe call with nsteps = 0 on the same amplitudes;
+ *   3. results are run-to-run bit-identical: no floating-point atomics, no split of a sum along K;
+ *   4. the summation order of an element depends on count and on its channel's driven and static lists alone; a channel without a
+ *      static entry computes what it computes in the call without static blocks;
+ *   5. a scan does not depend on the other scans of the call;
+ *   6. a snapshot equals the result of the shorter run;
+ *   7. nothing depends on obs_every or on the staging bound (tdse_stage_mb).
+ * The host variant uploads W once per call; like D it is not counted in the staging bound.
+ * BSPATOM_ERR_ARG: everything bspatom_tdse_observe names; scheme outside {0, 1}; nstat < 0; nstat > 0 with a null si, sf, skind or W;
+ * a channel index outside 0..nch-1; skind outside {0, 1}.  The _dev variant: W_dev in device memory; si, sf, skind host pointers. */
+int bspatom_tdse_static(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf,
+                        const double *D, int nscan, int nsteps, double dt, const double *field, double *a, int snap_every,
+                        double *snap, double *err, int obs_every, double *obs, int scheme, int nstat, const int32_t *si,
+                        const int32_t *sf, const int32_t *skind, const double *W);
+int bspatom_tdse_static_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                            const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                            double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev, int scheme,
+                            int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W_dev);
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
@@ -345,7 +390,7 @@ int bspatom_last_timing(const bspatom_problem *p, double ms[6]);
  * times and launch counts per slot since the previous call into ms[] / launches[] (cap >= the slot count, which it returns)
  * and forgets them.  Slots: 0 rank-128 update (syr2k), 1 symm, 2 panel QR, 3 the small products of the panel chain,
  * 4 sb2sb_mfma_kernel, 5 sbr_rows_kernel<8> / <16> (sb16st_kernel with BSP_SB16_ROWS=0), 6 batched bisection, 7 Cholesky + standard form,
- * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel and tdse_observe_kernel, their Lawson variants and tdse_phase_kernel (tdse.hip);
+ * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel and tdse_observe_kernel, their Lawson and static variants and tdse_phase_kernel (tdse.hip, tdse_static.hip);
  * bspatom_kernel_slot_name(i) names them.  Launches on different streams overlap: the sums are sums of launch durations, not wall time. */
 int bspatom_kernel_times(double *ms, int32_t *launches, int cap);
 const char *bspatom_kernel_slot_name(int slot);
