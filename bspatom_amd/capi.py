@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -88,6 +88,8 @@ def lib():
         L.bspatom_tdse_lawson_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
         L.bspatom_tdse_static.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
         L.bspatom_tdse_static_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+        L.bspatom_tdse_fields.argtypes = L.bspatom_tdse_static.argtypes + [i32, vp]
+        L.bspatom_tdse_fields_dev.argtypes = L.bspatom_tdse_static_dev.argtypes + [i32, vp]
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -562,6 +564,69 @@ class Problem:
                                            C.c_void_p(obs_ptr) if obs_ptr else None, int(scheme), ns, _p(si) if ns else None,
                                            _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None),
              "bspatom_tdse_static_dev")
+        return err
+
+    @staticmethod
+    def _tdse_fidx(fidx, npairs):
+        """fidx as int32 (npairs,); None stays None (the library's NULL: all pairs on field 0, one field only)"""
+        if fidx is None:
+            return None
+        fidx = np.ascontiguousarray(np.asarray(fidx, dtype=np.int32).reshape(-1))
+        if len(fidx) != npairs:
+            raise ValueError("fidx: %d entries for %d pairs" % (len(fidx), npairs))
+        return fidx
+
+    def tdse_fields(self, E, pairs, D, fidx, a0, field, dt, static=None, scheme=1, obs_every=0, snap_every=0):
+        """tdse_static with several drive fields (bspatom_tdse_fields): fidx[p] names the field that multiplies pair p, field is complex
+        (nsteps, 6, nfield, nscan), [n, s, g, q] = f_{g,q} at the stage times (host.field_table_pol builds the two fields of a
+        field of any direction on the blocks of host.tdse_system_pol); nfield <= 3.  Returns (a, err[, obs][, snaps]) as tdse_static
+        does; obs: (nobs, nscan, nch, 4 + 2 nfield), [..., :2] population and sum E |a|^2, [..., 2:4] = Re, Im of z_{c,0}, [..., 4:6] of s_c,
+        [..., 4 + 2g: 6 + 2g] of z_{c,g}, z_{c,g} the sum over the pairs of field g that end in c (host.tdse_dipole_vector).  A field of
+        shape (0, 6, nfield, nscan) measures a0 as given."""
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        nch, count = E.shape
+        ci, cf = self._tdse_pairs(pairs)
+        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
+        fidx = self._tdse_fidx(fidx, len(ci))
+        si, sf, skind, W = self._tdse_static(static, count)
+        a = np.array(a0, dtype=np.complex128, order="C")
+        one = a.ndim == 2
+        a = np.ascontiguousarray(a.reshape(-1, nch, count))
+        nscan = a.shape[0]
+        field = np.ascontiguousarray(field, dtype=np.complex128)
+        if field.ndim != 4 or field.shape[1] != 6 or field.shape[3] != nscan:
+            raise ValueError("field must have shape (nsteps, 6, nfield, %d), got %s" % (nscan, field.shape))
+        nsteps, nfield = field.shape[0], field.shape[2]
+        err = np.zeros(nscan)
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 4 + 2 * max(nfield, 1))) if obs_every > 0 else None
+        ns = len(si)
+        _chk(lib().bspatom_tdse_fields(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
+                                       _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
+                                       _p(snaps), _p(err), obs_every, _p(obs), int(scheme), ns, _p(si) if ns else None,
+                                       _p(sf) if ns else None, _p(skind) if ns else None, _p(W) if ns else None, nfield,
+                                       _p(fidx) if fidx is not None and len(ci) else None), "bspatom_tdse_fields")
+        if one:
+            a = a[0]
+        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+
+    def tdse_fields_dev(self, nch, count, E_ptr, pairs, D_ptr, fidx, nfield, nscan, nsteps, dt, field_ptr, a_ptr, static=None, scheme=1,
+                        obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None):
+        """tdse_fields on device memory: the arguments of tdse_static_dev with fidx (a host list, or None with nfield = 1) and nfield; the
+        field table nsteps * 6 * nfield * nscan complex at field_ptr, rows of 4 + 2 nfield doubles per (scan, channel) at obs_ptr.
+        Returns err (nscan,) when the result is there."""
+        ci, cf = self._tdse_pairs(pairs)
+        fidx = self._tdse_fidx(fidx, len(ci))
+        si, sf, skind, W_ptr = self._tdse_static(static)
+        ns = len(si)
+        err = np.zeros(nscan)
+        _chk(lib().bspatom_tdse_fields_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
+                                           _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
+                                           float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
+                                           C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
+                                           C.c_void_p(obs_ptr) if obs_ptr else None, int(scheme), ns, _p(si) if ns else None,
+                                           _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None,
+                                           int(nfield), _p(fidx) if fidx is not None and len(ci) else None), "bspatom_tdse_fields_dev")
         return err
 
     def early_vector_state(self):

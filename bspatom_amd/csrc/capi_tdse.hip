@@ -1,7 +1,8 @@
-// capi_tdse.hip -- bspatom_tdse_propagate / _dev, bspatom_tdse_observe / _dev, bspatom_tdse_lawson / _dev and bspatom_tdse_static / _dev
-// (include/bspatom.h): the argument checks, the per-channel entry lists, the working buffers and the step loop of tdse.hip.  One code
-// path: propagate is observe without rows, the Lawson scheme is a flag that adds the phase table, and the static call is either with
-// static entries behind the driven ones and rows of 6.  The problem handle gives the device and the stream; nothing of a solve is read.
+// capi_tdse.hip -- bspatom_tdse_propagate / _dev, bspatom_tdse_observe / _dev, bspatom_tdse_lawson / _dev, bspatom_tdse_static / _dev and
+// bspatom_tdse_fields / _dev (include/bspatom.h): the argument checks, the per-channel entry lists, the working buffers and the step loop
+// of tdse.hip.  One code path: propagate is observe without rows, the Lawson scheme is a flag that adds the phase table, the static call
+// is either with static entries behind the driven ones and rows of 6, and the fields call is the static call whose driven entries name
+// their field (one field: the static call itself).  The problem handle gives the device and the stream; nothing of a solve is read.
 #include <cmath>
 #include "capi_internal.h"
 
@@ -25,7 +26,19 @@ bool args_ok(const bspatom_problem *p, int nch, int count, const double *E, int 
 }
 
 // the static blocks of bspatom_tdse_static (host lists; W on the device once run_dev has it); null where a call has none by design
-struct Static { int n; const int32_t *si, *sf, *kind; const double *W; };
+// nf, fidx: the drive fields of bspatom_tdse_fields and the field of every pair (null: all 0)
+struct Static { int n; const int32_t *si, *sf, *kind; const double *W; int nf = 1; const int32_t *fidx = nullptr; };
+
+// BSP_OK, or what bspatom_tdse_fields returns for its two own arguments
+int fields_args_rc(int nfield, const int32_t *fidx, int npairs)
+{
+    if (nfield < 1) return BSP_ERR_ARG;
+    if (nfield > BSPATOM_TDSE_MAX_FIELDS) return BSP_ERR_UNSUPPORTED;
+    if (!fidx) return nfield > 1 && npairs > 0 ? BSP_ERR_ARG : BSP_OK;
+    for (int q = 0; q < npairs; ++q)
+        if (fidx[q] < 0 || fidx[q] >= nfield) return BSP_ERR_ARG;
+    return BSP_OK;
+}
 
 bool static_args_ok(int nch, int scheme, int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W)
 {
@@ -44,19 +57,21 @@ struct Plan {
     DevArray<unsigned long long> err2;
     size_t rows = 0, odbl = 0;                 // odbl: doubles of one row of observables, [nscan][nch][ow]
     bool observing = false;
-    int ow = 4, nstat = 0;                     // ow = 6: a bspatom_tdse_static call; nstat: its static blocks
+    int ow = 4, nstat = 0, nf = 1;             // ow = 6: a bspatom_tdse_static call, 4 + 2 nf with nf > 1 fields; nstat: its static blocks
     // stc: null (the rows of 4 of the other calls), or the static blocks of a bspatom_tdse_static call (rows of 6, stc->n may be 0)
     int prepare(bspatom_problem *p, int nch, int count, int nscan, int npairs, const int32_t *ci, const int32_t *cf, bool observing_,
                 const Static *stc = nullptr)
     {
         d = {nch, count, nscan, tdse_columns(nscan)};
         rows = (size_t)nch * count;
-        ow = stc ? 6 : 4;
+        nf = stc ? stc->nf : 1;
+        ow = stc ? (nf > 1 ? 4 + 2 * nf : 6) : 4;
         nstat = stc ? stc->n : 0;
+        const int32_t *fidx = nf > 1 ? stc->fidx : nullptr;
         odbl = (size_t)ow * nscan * nch;
         observing = observing_;
         // channel c's entries in ascending p: (p, cf[p], 1) where ci[p] = c, (p, ci[p], 0) where cf[p] = c; behind them its static
-        // entries in ascending j: (j, si[j], 2 + skind[j]) where sf[j] = c
+        // entries in ascending j: (j, si[j], 2 + skind[j]) where sf[j] = c.  Several fields: a driven entry's third word gains 4 fidx[p]
         std::vector<int> cp(nch + 1, 0), en((size_t)6 * npairs + (size_t)3 * nstat + 3, 0);
         for (int q = 0; q < npairs; ++q) { ++cp[ci[q] + 1]; ++cp[cf[q] + 1]; }
         for (int j = 0; j < nstat; ++j) ++cp[stc->sf[j] + 1];
@@ -64,9 +79,10 @@ struct Plan {
         std::vector<int> at(cp.begin(), cp.end() - 1);
         for (int q = 0; q < npairs; ++q) {
             int *e = &en[(size_t)3 * at[ci[q]]++];
-            e[0] = q; e[1] = cf[q]; e[2] = 1;
+            const int g4 = fidx ? 4 * fidx[q] : 0;
+            e[0] = q; e[1] = cf[q]; e[2] = 1 + g4;
             e = &en[(size_t)3 * at[cf[q]]++];
-            e[0] = q; e[1] = ci[q]; e[2] = 0;
+            e[0] = q; e[1] = ci[q]; e[2] = g4;
         }
         for (int j = 0; j < nstat; ++j) {
             int *e = &en[(size_t)3 * at[stc->sf[j]]++];
@@ -76,8 +92,9 @@ struct Plan {
         if ((rc = cptr.put(cp.data(), cp.size())) || (rc = ent.put(en.data(), en.size())) || (rc = aw.alloc(rows * d.NC)) ||
             (rc = K.alloc(6 * rows * d.NC)) || (rc = err2.alloc(nscan)))
             return rc;
-        // the observing kernel's partials: one of 4 doubles (6 with static blocks) per (channel, row tile of 64 states, scan slot)
-        if (observing && (rc = part.alloc((size_t)nch * ((count + 63) / 64) * (d.NC / 2) * (nstat > 0 ? 6 : 4)))) return rc;
+        // the observing kernel's partials: one of 4 doubles (6 with static blocks, 4 + 2 nf with several fields) per (channel, row tile
+        // of 64 states, scan slot)
+        if (observing && (rc = part.alloc((size_t)nch * ((count + 63) / 64) * (d.NC / 2) * (nf > 1 ? ow : nstat > 0 ? 6 : 4)))) return rc;
         return HIP_RC(hipMemsetAsync(err2.p, 0, (size_t)nscan * sizeof(unsigned long long), p->st));
     }
     // the Lawson scheme: the phase table from the energies on the device, before bufs()
@@ -89,7 +106,7 @@ struct Plan {
     // d_W: the static blocks on the device (null without any: the kernels of the other calls run, whatever ow is)
     TdseBufs bufs(const double *d_E, const double *d_D, const double *d_W = nullptr) const
     {
-        return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p, observing ? part.p : nullptr, ph.p, nstat > 0 ? d_W : nullptr, ow};
+        return {cptr.p, ent.p, d_E, d_D, aw.p, K.p, err2.p, observing ? part.p : nullptr, ph.p, nstat > 0 ? d_W : nullptr, ow, nf};
     }
     // steps n0 .. n1-1; d_field: the table from step n0 on; d_snap (or null): where snapshot number s0 (from 0) goes, the later ones behind it;
     // d_obs (or null): where row j0 goes (row j = the amplitudes before step j obs_every), the later ones behind it
@@ -100,7 +117,7 @@ struct Plan {
             double *sn = nullptr, *ob = nullptr;
             if (d_snap && (n + 1) % snap_every == 0) sn = d_snap + ((size_t)((n + 1) / snap_every - 1 - s0)) * rows * d.nscan * 2;
             if (d_obs && n % obs_every == 0) ob = d_obs + (size_t)(n / obs_every - j0) * odbl;
-            const int rc = launch_tdse_step(d, w, d_field + (size_t)(n - n0) * 12 * d.nscan, dt, sn, ob, p->st);
+            const int rc = launch_tdse_step(d, w, d_field + (size_t)(n - n0) * 12 * d.nscan * nf, dt, sn, ob, p->st);
             if (rc) return rc;
         }
         return BSP_OK;
@@ -157,8 +174,9 @@ int run_host(bspatom_problem *p, int nch, int count, const double *E, int npairs
         return BSP_OK;
     }
     BSP_HIP(hipSetDevice(p->device));
-    const size_t rows = (size_t)nch * count, adbl = rows * nscan * 2, fdbl = (size_t)12 * nscan;     // doubles of a snapshot, of a step's field
-    const size_t odbl = (size_t)(stc ? 6 : 4) * nscan * nch;                                          // of a row of observables
+    const int nf = stc ? stc->nf : 1;
+    const size_t rows = (size_t)nch * count, adbl = rows * nscan * 2, fdbl = (size_t)12 * nscan * nf;        // doubles of a snapshot, of a step's field
+    const size_t odbl = (size_t)(stc ? (nf > 1 ? 4 + 2 * nf : 6) : 4) * nscan * nch;                         // of a row of observables
     // steps per group: the field of g steps, the (at most g / snap_every + 1) snapshots and the (at most (g - 1) / obs_every + 1)
     // observed steps among them within the bound, one step at least
     const bool snapping = snap && snap_every > 0;
@@ -295,5 +313,35 @@ extern "C" int bspatom_tdse_static(bspatom_problem *p, int nch, int count, const
         !static_args_ok(nch, scheme, nstat, si, sf, skind, W))
         return BSP_ERR_ARG;
     const Static stc = {nstat, si, sf, skind, W};
+    return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs, scheme == 1, &stc);
+}
+
+extern "C" int bspatom_tdse_fields_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                                       const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                                       double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev,
+                                       int scheme, int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W_dev,
+                                       int nfield, const int32_t *fidx)
+{
+    if (!args_ok(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev) ||
+        !obs_args_ok(obs_every, obs_dev) || !static_args_ok(nch, scheme, nstat, si, sf, skind, W_dev))
+        return BSP_ERR_ARG;
+    const int frc = fields_args_rc(nfield, fidx, npairs);
+    if (frc) return frc;
+    const Static stc = {nstat, si, sf, skind, W_dev, nfield, fidx};
+    return run_dev(p, nch, count, E_dev, npairs, ci, cf, D_dev, nscan, nsteps, dt, field_dev, a_dev, snap_every, snap_dev, err, obs_every, obs_dev,
+                   scheme == 1, &stc);
+}
+
+extern "C" int bspatom_tdse_fields(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci,
+                                   const int32_t *cf, const double *D, int nscan, int nsteps, double dt, const double *field, double *a,
+                                   int snap_every, double *snap, double *err, int obs_every, double *obs, int scheme, int nstat,
+                                   const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W, int nfield, const int32_t *fidx)
+{
+    if (!args_ok(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap) || !obs_args_ok(obs_every, obs) ||
+        !static_args_ok(nch, scheme, nstat, si, sf, skind, W))
+        return BSP_ERR_ARG;
+    const int frc = fields_args_rc(nfield, fidx, npairs);
+    if (frc) return frc;
+    const Static stc = {nstat, si, sf, skind, W, nfield, fidx};
     return run_host(p, nch, count, E, npairs, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err, obs_every, obs, scheme == 1, &stc);
 }

@@ -311,10 +311,13 @@ struct TdseBufs {
     // ow = doubles per (scan, channel) of a row of observables, 4 or 6
     const double *W = nullptr;
     int ow = 4;
+    // bspatom_tdse_fields with nf > 1 drive fields: a driven entry's [3e+2] is 4 g + {0, 1}, g its field; the field table of a stage
+    // is [nf][nscan][2]; part and the rows are ow = 4 + 2 nf doubles wide, and the kernels of tdse_fields.hip run, with or without W
+    int nf = 1;
 };
 extern const double TDSE_A[6][5], TDSE_D[6], TDSE_B[6];
 int tdse_columns(int nscan);
-// one step: six stage launches and the step kernel; d_field: the 6 * nscan complex values of this step; d_snap: null, or where the
+// one step: six stage launches and the step kernel; d_field: the 6 * w.nf * nscan complex values of this step; d_snap: null, or where the
 // new amplitudes go in the caller's layout [nscan][nch][count] complex; d_obs: null, or where the observables of the amplitudes
 // BEFORE the step go, [nscan][nch][4] (then stage 0 is the observing kernel, followed by the reduction: eight launches)
 int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, double *d_obs, hipStream_t st);
@@ -327,6 +330,10 @@ int launch_tdse_phases(const TdseDims &d, const double *d_E, double dt, double *
 int launch_tdse_static_stage(int S, const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st);
 int launch_tdse_static_observe(const TdseDims &d, const TdseBufs &w, const double *fld, bool lawson, hipStream_t st);
 int launch_tdse_static_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st);
+// tdse_fields.hip: what they launch instead when w.nf > 1
+int launch_tdse_fields_stage(int S, const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st);
+int launch_tdse_fields_observe(const TdseDims &d, const TdseBufs &w, const double *fld, bool lawson, hipStream_t st);
+int launch_tdse_fields_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st);
 int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st);
 int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st);
 

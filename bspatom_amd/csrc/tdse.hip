@@ -224,6 +224,7 @@ static int launch_stage_s(const TdseDims &d, const TdseBufs &w, const double *fl
     const int tm = (d.count + TBM - 1) / TBM;
     const size_t ks = (size_t)d.nch * d.count * d.NC;
     KScope ks_(KS_TDSE, st);
+    if (w.nf > 1) return launch_tdse_fields_stage(S, d, w, fld, dt, st);         // several drive fields (tdse_fields.hip)
     if (w.W) return launch_tdse_static_stage(S, d, w, fld, dt, st);              // static blocks, either scheme (tdse_static.hip)
     const int tn = d.NC == 16 ? 1 : (d.NC + 31) / 32;
     const long long grid = (long long)d.nch * tm * tn;
@@ -258,7 +259,10 @@ int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld,
         if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
         // a Lawson step's stage 0 leaves another k_0; a measurement alone (fld null) is the same kernel for both schemes
         const bool lawson = w.ph && fld;
-        if (w.W) {
+        if (w.nf > 1) {
+            const int rc = launch_tdse_fields_observe(d, w, fld, lawson, st);
+            if (rc) return rc;
+        } else if (w.W) {
             const int rc = launch_tdse_static_observe(d, w, fld, lawson, st);
             if (rc) return rc;
         } else {
@@ -269,6 +273,7 @@ int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld,
             BSP_HIP(hipGetLastError());
         }
     }
+    if (w.nf > 1) return launch_tdse_fields_reduce(d, w, d_row, st);            // rows of 4 + 2 nf (bspatom_tdse_fields)
     if (w.ow == 6) return launch_tdse_static_reduce(d, w, d_row, st);           // rows of 6 (bspatom_tdse_static)
     const long long blocks = ((long long)d.nscan * d.nch + 255) / 256;
     if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
@@ -279,7 +284,7 @@ int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld,
 
 int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, double *d_obs, hipStream_t st)
 {
-    const size_t fs = (size_t)2 * d.nscan;
+    const size_t fs = (size_t)2 * d.nscan * w.nf;
     int rc;
     if ((rc = d_obs ? launch_tdse_observe(d, w, d_field, d_obs, st) : launch_stage_s<0>(d, w, d_field, dt, st)) ||
         (rc = launch_stage_s<1>(d, w, d_field + fs, dt, st)) ||

@@ -11,6 +11,9 @@ constexpr int TBK = 16, TBM = 64, TLDA = TBM + 16;
 struct StageCoef { double w[5]; };          // A_s0 .. A_s,s-1
 template <bool STAT, int TN> struct StatAcc { double4_t v[1][TN]; };        // the accumulator of the static entries, absent without STAT
 template <int TN> struct StatAcc<false, TN> {};
+// the accumulator pairs of the fields 1 .. NX (bspatom_tdse_fields), absent with one field
+template <int NX, int TN> struct FieldAcc { double4_t t[NX][1][TN], n[NX][1][TN]; };
+template <int TN> struct FieldAcc<0, TN> {};
 
 // y_s of one element from a and the k_j of the step, in one fixed order (the staged operand and the epilogue's E .* y agree bit for bit)
 template <int S>
@@ -70,7 +73,21 @@ __device__ __forceinline__ void load_y(double (&v)[S + 1], const double *__restr
 // same real product into the one accumulator accS, which the field never touches: h += accS where the channel has a static entry
 // (a channel without one computes what the kernels without STAT compute).  OBS: two more chains t4, t5 on y and accS, reduced like
 // t2, t3, are s_c = conj(a_c) . S_c; the partials are 6 doubles wide.
-template <int S, int TN, bool OBS, bool LAWSON, bool STAT = false>
+//
+// NF > 1 (bspatom_tdse_fields, always with STAT): a driven entry carries its field in ent[3e+2] = 4 g + {0, 1} (a static entry stays 2 or
+// 3; with g = 0 the list is what the other kernels read), and every field g >= 1 has its own pair accX.t[g - 1], accX.n[g - 1] beside
+// accT, accN of field 0: an entry's products go into the pair of its field, so an accumulator sees its field's entries in ascending p
+// as if the others were not there.  fld holds this stage's values [g][nscan][2]; the epilogue chains the fields in ascending g,
+// h = ((E y + f_0 ..) + f_1 ..) + .., each field's four terms in the order above, accS behind them.  OBS: two more chains per field
+// g >= 1 on y and its accT, reduced like t2, t3, are z_{c,g}; the partials are 4 + 2 NF doubles wide: [0 .. 3] as ever (z of field
+// 0), [4, 5] = s_c, [4 + 2 g, 5 + 2 g] = z_{c,g}.
+template <int NF> __device__ __forceinline__ int ent_kind(int kd)
+{
+    if constexpr (NF > 1) return kd & 3;
+    else return kd;
+}
+
+template <int S, int TN, bool OBS, bool LAWSON, bool STAT = false, int NF = 1>
 __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
                                                 const int *__restrict__ ent, const double *__restrict__ E,
                                                 const double *__restrict__ D, const double *__restrict__ a,
@@ -79,7 +96,8 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
                                                 const double *__restrict__ Wst = nullptr)
 {
     static_assert(!OBS || S == 0, "only stage 0 runs on a(t_n)");
-    constexpr int PW = STAT ? 6 : 4;                                          // doubles of a partial
+    static_assert(NF == 1 || STAT, "several fields run with the static accumulator");
+    constexpr int PW = NF > 1 ? 4 + 2 * NF : STAT ? 6 : 4;                    // doubles of a partial
     constexpr bool ROT = LAWSON && S > 0;                                     // R_0 = 1; phs: this stage's phases [nch][count][2]
     constexpr int NB = 16 * TN, TLDB = NB + 16, BEL = TBK * NB / 256;        // B-tile elements per thread: 1 or 2
     __shared__ double As[TBK * TLDA];
@@ -94,17 +112,25 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
     const int ksteps = (count + TBK - 1) / TBK;
     const size_t blk = (size_t)count * count;
 
-    double4_t accT[1][TN], accN[1][TN];
+    double4_t accT[1][TN], accN[1][TN];                                       // field 0; accX.t[g - 1], accX.n[g - 1]: field g >= 1
     [[maybe_unused]] StatAcc<STAT, TN> accS;
+    [[maybe_unused]] FieldAcc<NF - 1, TN> accX;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         accT[0][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
         accN[0][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
         if constexpr (STAT) accS.v[0][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+        if constexpr (NF > 1) {
+#pragma unroll
+            for (int g = 0; g < NF - 1; ++g) {
+                accX.t[g][0][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+                accX.n[g][0][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+            }
+        }
     }
     // the static entries come last: the channel has one exactly if its last entry is one
     [[maybe_unused]] bool has_s = false;
-    if constexpr (STAT) has_s = e1 > e0 && ent[3 * (e1 - 1) + 2] >= 2;
+    if constexpr (STAT) has_s = e1 > e0 && ent_kind<NF>(ent[3 * (e1 - 1) + 2]) >= 2;
 
     double ra[4], rb[BEL][S + 1];
     [[maybe_unused]] double rc[ROT ? BEL : 1], rs[ROT ? BEL : 1];                            // cos, +- sin (+ on the Re lane) of the B-tile rows
@@ -112,10 +138,10 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
     auto load = [&](int it) {
         const int e = e0 + it / ksteps, k0 = (it % ksteps) * TBK;
         const int p = ent[3 * e], oc = ent[3 * e + 1], kd = ent[3 * e + 2];
-        const int nrm = STAT ? kd == 1 : kd;
+        const int nrm = STAT ? ent_kind<NF>(kd) == 1 : kd;
         const double *Dp = D + (size_t)p * blk;
         if constexpr (STAT) {
-            if (kd >= 2) Dp = Wst + (size_t)p * blk;
+            if (ent_kind<NF>(kd) >= 2) Dp = Wst + (size_t)p * blk;
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -144,7 +170,7 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
         return kd;
     };
     auto store = [&](int kd) {
-        const int nrm = STAT ? kd == 1 : kd;
+        const int nrm = STAT ? ent_kind<NF>(kd) == 1 : kd;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int idx = tid + r * 256;
@@ -180,7 +206,32 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
         __syncthreads();
         const int cur = nrm;
         if (it + 1 < nit) nrm = load(it + 1);
-        if (STAT && cur >= 2) {
+        if constexpr (NF > 1) {
+            // the accumulator of the entry's field, by uniform branches (an index would put the accumulators into scratch)
+            auto mm = [&](double4_t (&acc)[1][TN]) {
+#pragma unroll
+                for (int k4 = 0; k4 < TBK / 4; ++k4) {
+                    const int kr = k4 * 4 + (lane >> 4);
+                    mfma_step<1, TN>(&As[kr * TLDA + wave * 16], &Bs[kr * TLDB], lane, kr, acc);
+                }
+            };
+            const int kind = cur & 3, g = cur >> 2;
+            if (kind >= 2) {
+                mm(accS.v);
+            } else {
+                if (g == 0) {
+                    if (kind) mm(accN);
+                    else mm(accT);
+                }
+#pragma unroll
+                for (int gg = 1; gg < NF; ++gg) {
+                    if (g == gg) {
+                        if (kind) mm(accX.n[gg - 1]);
+                        else mm(accX.t[gg - 1]);
+                    }
+                }
+            }
+        } else if (STAT && cur >= 2) {
             if constexpr (STAT) {
 #pragma unroll
                 for (int k4 = 0; k4 < TBK / 4; ++k4) {
@@ -215,8 +266,24 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
         const bool cok = col < NC, fok = q < nscan;
         const double fre = stepping ? fld[fok ? 2 * q : 0] : 0.0, fim = stepping ? fld[fok ? 2 * q + 1 : 0] : 0.0;
         const double fr = fok ? fre : 0.0, fi = fok ? (odd ? fim : -fim) : 0.0;
+        // the fields g >= 1: fld[(g nscan + q) 2 + {0, 1}], selected like field 0's
+        [[maybe_unused]] double frg[NF], fig[NF];
+        if constexpr (NF > 1) {
+#pragma unroll
+            for (int g = 1; g < NF; ++g) {
+                const size_t at = fok ? ((size_t)g * nscan + q) * 2 : 0;
+                const double gre = stepping ? fld[at] : 0.0, gim = stepping ? fld[at + 1] : 0.0;
+                frg[g] = fok ? gre : 0.0;
+                fig[g] = fok ? (odd ? gim : -gim) : 0.0;
+            }
+        }
         double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
         [[maybe_unused]] double t4 = 0.0, t5 = 0.0;
+        [[maybe_unused]] double tz[NF][2];
+        if constexpr (NF > 1 && OBS) {
+#pragma unroll
+            for (int g = 1; g < NF; ++g) tz[g][0] = tz[g][1] = 0.0;
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int gm = m0 + wave * 16 + (lane >> 4) + 4 * r;
@@ -244,6 +311,21 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
             h = fma(fi, up, h);
             h = fma(fr, w, h);
             h = fma(-fi, wp, h);
+            if constexpr (NF > 1) {
+#pragma unroll
+                for (int g = 1; g < NF; ++g) {
+                    const double ug = accX.t[g - 1][0][j][r], wg = accX.n[g - 1][0][j][r];
+                    const double ugp = __shfl_xor(ug, 1), wgp = __shfl_xor(wg, 1);
+                    h = fma(frg[g], ug, h);
+                    h = fma(fig[g], ugp, h);
+                    h = fma(frg[g], wg, h);
+                    h = fma(-fig[g], wgp, h);
+                    if constexpr (OBS) {
+                        tz[g][0] = fma(y, ug, tz[g][0]);
+                        tz[g][1] = fma(y, ugp, tz[g][1]);
+                    }
+                }
+            }
             [[maybe_unused]] double sv = 0.0;
             if constexpr (STAT) {
                 sv = accS.v[0][j][r];
@@ -275,6 +357,13 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
             if constexpr (STAT) {
                 t[4] = t4;
                 t[5] = odd ? -t5 : t5;
+            }
+            if constexpr (NF > 1) {
+#pragma unroll
+                for (int g = 1; g < NF; ++g) {
+                    t[4 + 2 * g] = tz[g][0];
+                    t[5 + 2 * g] = odd ? -tz[g][1] : tz[g][1];
+                }
             }
 #pragma unroll
             for (int k = 0; k < PW; ++k) {

@@ -535,6 +535,80 @@ def tdse_system(prob, channels, n0, count, kind_pi=1, mph=0):
     return E, pairs, D
 
 
+def dipole_blocks_pol(channels):
+    """The length-gauge blocks of a field of any direction between `channels` (a list of (l, m)), for Problem.tdse_fields: (blocks,
+    fidx), blocks as dipole_blocks gives them.  First the nonzero q = 0 blocks of dipole_blocks(channels, 1, 0), on field 0; then the
+    q = +1 blocks on field 1, for EVERY ordered (bra, ket) pair of channels whose 3j symbol is nonzero (m_bra = m_ket + 1): r_{+1} is
+    not Hermitian, and the conjugate partner the call gives every pair supplies -r_{-1}.  The angular factor is dipole_blocks'."""
+    blocks = [b for b in dipole_blocks(channels, 1, 0) if b[5][0] != 0.0]          # dipole_blocks keeps the pairs whose 3j symbol vanishes
+    fidx = [0] * len(blocks)
+    for a_, (li, mi) in enumerate(channels):
+        for b_, (lj, mj) in enumerate(channels):
+            if abs(li - lj) != 1:
+                continue
+            l0, m0, lf, mf = lj, mj, li, mi
+            t3a = three_j(lf, 1, l0, -mf, 1, m0)
+            if t3a == 0.0:
+                continue
+            t3b = three_j(lf, 1, l0, 0, 0, 0)
+            c1 = (-1.0) ** (lf + l0 + mf) * math.sqrt(float((2 * lf + 1) * (2 * l0 + 1))) * t3a * t3b
+            blocks.append((a_, b_, l0, lf, 1.0, [c1, 0.0, 0.0]))
+            fidx.append(1)
+    return blocks, fidx
+
+
+def tdse_system_pol(prob, channels, n0, count):
+    """(E, pairs, D, fidx) of Problem.tdse_fields for the states n0 .. n0+count-1 (1-based) of `channels`, a list of (l, m) of the last
+    solve, in the length gauge under a field of any direction: tdse_system's E, the blocks of dipole_blocks_pol from ONE
+    dipole_matrix call, fidx[p] = 0 (r_0, driven by f_0 = F_z) or 1 (r_{+1}, driven by f_1 = -(F_x - i F_y) / sqrt 2): field_table_pol."""
+    import numpy as np
+    E_all, l_first = getattr(prob, "last_E", None), getattr(prob, "last_l0", 0)
+    if E_all is None:
+        raise ValueError("tdse_system_pol needs the eigenvalues of the problem's last solve()")
+    E = np.stack([np.asarray(E_all[l - l_first][n0 - 1: n0 - 1 + count], dtype=np.float64) for l, _ in channels])
+    if E.shape != (len(channels), count):
+        raise ValueError("states %d .. %d are not in the last solve" % (n0, n0 + count - 1))
+    blocks, fidx = dipole_blocks_pol(channels)
+    pairs = [(b_, a_) for a_, b_, *_ in blocks]
+    if not blocks:
+        return E, pairs, np.zeros((0, count, count)), fidx
+    D = prob.dipole_matrix([(l0, lf) for _, _, l0, lf, _, _ in blocks], n0, count, n0, count,
+                           np.array([coef for *_, coef in blocks], dtype=np.float64))
+    D = np.array([c0 for *_, c0, _ in blocks], dtype=np.float64)[:, None, None] * D
+    return E, pairs, D, fidx
+
+
+def field_table_pol(F, t0, dt, nsteps):
+    """The field argument of Problem.tdse_fields for the blocks of dipole_blocks_pol: complex (nsteps, 6, 2, nscan) with f_0 = F_z and
+    f_1 = -(F_x - i F_y) / sqrt 2 at the stage times, so that f_0 r_0 + f_1 r_{+1} + h.c. = F . r.  F: one entry per scan, a callable
+    of the array of times that returns (F_x, F_y, F_z), or an array (3, nsteps, 6) on rk_nodes(t0, dt, nsteps)."""
+    import numpy as np
+    t = rk_nodes(t0, dt, nsteps)
+    F = list(F)
+    out = np.zeros((nsteps, 6, 2, len(F)), dtype=np.complex128)
+    for q, f in enumerate(F):
+        v = f(t) if callable(f) else f
+        if len(v) != 3:
+            raise ValueError("scan %d: the field must give (Fx, Fy, Fz), got %d components" % (q, len(v)))
+        v = np.stack([np.broadcast_to(np.asarray(c, dtype=np.float64), t.shape) for c in v])
+        out[:, :, 0, q] = v[2]
+        out[:, :, 1, q] = -(v[0] - 1j * v[1]) / math.sqrt(2.0)
+    return out
+
+
+def tdse_dipole_vector(obs):
+    """(<x>, <y>, <z>), shape (nobs, nscan, 3), from the rows obs (nobs, nscan, nch, 8) of a Problem.tdse_fields run on the blocks of
+    dipole_blocks_pol: with z_g summed over the channels, <z> = 2 Re z_0, <x> = -sqrt 2 Re z_1, <y> = -sqrt 2 Im z_1 (z_1 = <r_{+1}>,
+    r_{+1} = -(x + i y) / sqrt 2)."""
+    import numpy as np
+    obs = np.asarray(obs)
+    if obs.ndim < 2 or obs.shape[-1] < 8:
+        raise ValueError("tdse_dipole_vector needs the rows of tdse_fields with two fields, (.., nch, 8), got shape %s" % (obs.shape,))
+    s = obs.sum(axis=-2)
+    r2 = np.sqrt(s.dtype.type(2))                           # in the rows' own precision
+    return np.stack([-r2 * s[..., 6], -r2 * s[..., 7], 2 * s[..., 2]], axis=-1)
+
+
 def cap_profile(r, r0, eta, power=2):
     """The complex absorbing potential's W(r) = eta (r - r0)^power beyond r0, 0 inside (the Hamiltonian gains -i W(r))."""
     import numpy as np

@@ -375,6 +375,53 @@ int bspatom_tdse_static_dev(bspatom_problem *p, int nch, int count, const double
                             double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev, int scheme,
                             int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W_dev);
 
+/* The same run with several drive fields, each driven block naming its own: a field with components along more than one axis (r_0 on one
+ * field, r_{+1} on a second: any polarisation and direction), a non-collinear two-colour pulse, a probe along another axis or in the
+ * other gauge, a multipole driven by A(t)^2.  The first 24 arguments are bspatom_tdse_static's, unchanged in meaning (scheme 0 plain,
+ * 1 Lawson; the static blocks as there).
+ *   nfield  the number of fields, 1 .. BSPATOM_TDSE_MAX_FIELDS (more: BSPATOM_ERR_UNSUPPORTED);
+ *   fidx[p] (host pointer, also for the _dev variant) the field of pair p, 0 .. nfield-1; NULL only with nfield = 1: all 0;
+ *   field[(((n*6 + s)*nfield + g)*nscan + q)*2 + {0,1}]: f_{g,q} at stage s of step n.  The host variant stages the table under
+ *   tdse_stage_mb as the other calls do; one step's worth is 12*nfield*nscan doubles.
+ *   i da_c/dt = E_c .* a_c + sum_{p: cf[p] = c} f_{fidx[p],q}(t) D_p^T a_ci[p] + sum_{p: ci[p] = c} conj(f_{fidx[p],q}(t)) D_p a_cf[p] + S_c(a)
+ * Two pairs between the same two channels with different fidx are legal ("a repeated pair adds").
+ * Rows: nobs as in bspatom_tdse_observe, RW = 4 + 2*nfield doubles wide, obs[((j*nscan + q)*nch + c)*RW + k]:
+ *     k = 0, 1                 population and sum E |a|^2, as in bspatom_tdse_observe
+ *     k = 2, 3                 Re, Im of z_{c,0}
+ *     k = 4, 5                 Re, Im of s_c, as in bspatom_tdse_static
+ *     k = 4 + 2g, 5 + 2g       Re, Im of z_{c,g}, g = 1 .. nfield-1
+ *   z_{c,g} = sum over the pairs p with cf[p] = c and fidx[p] = g of conj(a_cf) . D_p^T a_ci;  <H_int> = sum_g 2 Re(f_g z_g).  With
+ *   nfield = 1 this is bspatom_tdse_static's row of 6.  nsteps = 0 is a real call: the expectation values of up to
+ *   BSPATOM_TDSE_MAX_FIELDS block operators over any set of packets in one call.
+ * How: the field enters the stage only in its epilogue, so every field has its own pair of accumulators and an entry's products go into
+ * the pair of its field: the same reads of D and the same matrix instructions as with one field, no split along K, no atomics.  The limit
+ * of 3: every field costs two more accumulators of 8 registers and its epilogue values; with three fields no stage needs scratch, and
+ * the stages hold 168 .. 176 registers, at the edge of three waves per SIMD (two fields: 136 .. 152, three waves).
+ * Guarantees:
+ *   1. with nfield = 1, a, snap, err and obs have the bits of bspatom_tdse_static on the same inputs -- the same kernels run;
+ *   2. with more fields, k = 0, 1 of a row have the bits of a bspatom_tdse_observe call with nsteps = 0 on the same amplitudes; z_{c,g}
+ *      has the bits of such a call given only the pairs with fidx = g, in their order; s_c has the bits of a bspatom_tdse_static call
+ *      with nsteps = 0 and the same static blocks;
+ *   3. results are run-to-run bit-identical;
+ *   4. a scan does not depend on the other scans of the call;
+ *   5. a snapshot equals the result of the shorter run;
+ *   6. nothing depends on obs_every or on the staging bound (tdse_stage_mb);
+ *   7. the order of an element's sums depends on count and on its channel's lists alone: the entries are walked in ascending p, each
+ *      into the accumulator of its field; the epilogue adds the fields in ascending g, within a field in the order of the other calls;
+ *      the static accumulator comes after that.
+ * BSPATOM_ERR_ARG: everything bspatom_tdse_static names; nfield < 1; an fidx entry outside 0..nfield-1; fidx NULL with nfield > 1 and
+ * npairs > 0. */
+#define BSPATOM_TDSE_MAX_FIELDS 3
+int bspatom_tdse_fields(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf,
+                        const double *D, int nscan, int nsteps, double dt, const double *field, double *a, int snap_every,
+                        double *snap, double *err, int obs_every, double *obs, int scheme, int nstat, const int32_t *si,
+                        const int32_t *sf, const int32_t *skind, const double *W, int nfield, const int32_t *fidx);
+int bspatom_tdse_fields_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                            const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *field_dev,
+                            double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev, int scheme,
+                            int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W_dev, int nfield,
+                            const int32_t *fidx);
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
