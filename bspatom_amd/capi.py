@@ -748,15 +748,23 @@ def stage_bisect(d, e):
     return w
 
 
-def dsygv(A, B, jobz="V", uplo="U"):
-    """bsp_dsygv_ through its Fortran-77 ABI.  A, B: (n,n) arrays; returns w, Z (columns), factor of B, info."""
+def dsygv(A, B, jobz="V", uplo="U", lda=None, ldb=None, sentinel=-777.0):
+    """bsp_dsygv_ through its Fortran-77 ABI.  A, B: (n,n) arrays; returns w, Z (columns), factor of B, info.
+    lda / ldb (optional, >= n): leading dimensions of the arrays handed over; the rows beyond n hold `sentinel` on entry and the
+    arrays come back whole, (lda, n) and (ldb, n), so that a caller can see that those rows were left alone."""
     n = A.shape[0]
-    a = np.array(A, dtype=np.float64, order="F")
-    b = np.array(B, dtype=np.float64, order="F")
+    def padded(M, ld):
+        if ld is None:
+            return np.array(M, dtype=np.float64, order="F")
+        m = np.full((ld, n), sentinel, dtype=np.float64, order="F")
+        m[:n, :] = M
+        return m
+    a = padded(A, lda); b = padded(B, ldb)
     w = np.zeros(n); work = np.zeros(max(1, 4 * n))
-    it = C.c_int(1); nn = C.c_int(n); lda = C.c_int(n); lw = C.c_int(4 * n); info = C.c_int(0)
-    lib().bsp_dsygv_(C.byref(it), C.c_char_p(jobz.encode()), C.c_char_p(uplo.encode()), C.byref(nn), _p(a), C.byref(lda),
-                     _p(b), C.byref(lda), _p(w), _p(work), C.byref(lw), C.byref(info), C.c_size_t(1), C.c_size_t(1))
+    it = C.c_int(1); nn = C.c_int(n); la = C.c_int(n if lda is None else lda); lb = C.c_int(n if ldb is None else ldb)
+    lw = C.c_int(4 * n); info = C.c_int(0)
+    lib().bsp_dsygv_(C.byref(it), C.c_char_p(jobz.encode()), C.c_char_p(uplo.encode()), C.byref(nn), _p(a), C.byref(la),
+                     _p(b), C.byref(lb), _p(w), _p(work), C.byref(lw), C.byref(info), C.c_size_t(1), C.c_size_t(1))
     return w, a, b, info.value
 
 

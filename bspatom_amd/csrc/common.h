@@ -249,10 +249,12 @@ constexpr size_t OWN_CU_LDS = 144 * 1024;           // of 160 KB: 16 KB left
 int launch_early_vector(int n, int k, const double *d_SB, const double *d_HB, int m, double *d_E, double *d_work, double *d_vec,
                         int *d_info, hipStream_t st, bool own_cu);
 // eigvec.hip
-// vector iv: channel chan[iv] of HB (HB + chan*k*n), eigenvalue E[iv]; work: nvec*invit_work_doubles
+// vector iv: channel chan[iv] of HB (HB + chan*k*n), eigenvalue E[iv]; work: nvec*invit_work_doubles; d_start (or null): start[iv]
+// = 0 for the constant start vector, r > 0 for member r of a run of coinciding eigenvalues, whose r predecessors are the vectors in
+// front of it in d_vec; one launch computes the vectors with start[iv] == rank, rank r after rank r - 1 (eigvec.hip::invit_kernel)
 int launch_inverse_iteration(int n, int k, int nvec, const double *d_SB, const double *d_HB,
                              const int *d_chan, const double *d_E, double *d_work, double *d_vec,
-                             int *d_info, hipStream_t st);
+                             int *d_info, hipStream_t st, const int *d_start = nullptr, int rank = 0);
 size_t invit_work_doubles(int n, int k);
 // the same vectors for a channel range, persistent grid (invit_batch_kernel): item it = c * count + j is eigenvalue E[c*n + j] of
 // channel c (HB + c*k*n), vector at d_vec + it*n; d_work: slots * invit_batch_slot_doubles, slots from invit_batch_slots

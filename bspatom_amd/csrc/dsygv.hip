@@ -6,7 +6,8 @@
 // tests/test_gpu_solve.py::test_reference_binary_on_gpu_dsygv runs the reference's own program linked that way).
 // The pencil at that call site is banded (half-width k-1); the band is detected on the host, the pipeline of
 // capi.hip does the rest on the GPU.  JOBZ='V' eigenvectors come from batched inverse iteration on the banded pencil
-// (eigvec.hip), S-orthonormalised inside clusters of close eigenvalues (below).
+// (eigvec.hip), S-orthonormalised inside clusters of close eigenvalues (below).  A multiple eigenvalue gets an S-orthonormal basis of
+// its eigenspace, as from DSYGV (runs of coinciding eigenvalues: see the inverse iteration below).
 // info: 0 ok; -i = argument i illegal (LAPACK numbering; -5 also for a pencil that is not banded with half-width
 // <= 15, which the reference never produces); n+i = leading minor i of B not positive definite; n = the GPU path
 // failed (no device, out of memory, a kernel reported an error: message on stderr) -- LAPACK's "failed to converge"
@@ -89,6 +90,7 @@ template <class T> struct DBuf {
 // against the finished columns of the cluster (P = Q^T (S Z), Z -= Q P: two MFMA GEMMs per pass) and a Cholesky QR in the S inner
 // product inside the block (G = Z^T (S Z) by GEMM, its 64 x 64 factor on the host, Z <- Z R^-1), twice.  The vectors of a cluster
 // are nearly S-orthogonal to begin with (the spectrum of a radial problem is simple), so G = I + small and its factor is benign.
+// (The members of a multiple eigenvalue arrive S-orthogonal to each other too: bsp_dsygv_ computes them one after the other.)
 __global__ __launch_bounds__(256) void band_symm_block_kernel(int n, int k, const double *__restrict__ SB, const double *__restrict__ Z,
                                                              long ldz, double *__restrict__ Y, long ldy)
 {
@@ -268,10 +270,41 @@ extern "C" void bsp_dsygv_(const int *itype, const char *jobz, const char *uplo,
         if (dchan.alloc(chunk) != hipSuccess || dvw.alloc((size_t)chunk * invit_work_doubles(n, k)) != hipSuccess ||
             dvec.alloc((size_t)n * n) != hipSuccess) { fail("out of device memory (eigenvectors)"); return; }
         hipMemcpy(dchan.p, chan.data(), chunk * sizeof(int), hipMemcpyHostToDevice);
-        for (int done = 0; done < n && !rc; done += chunk) {
-            const int m = (n - done < chunk) ? n - done : chunk;
-            rc = launch_inverse_iteration(n, k, m, dSB.p, dHB.p, dchan.p, dE.p + done, dvw.p, dvec.p + (size_t)done * n, dinfo.p, 0);
+        // A multiple eigenvalue comes back as copies that agree to rounding: inverse iterations with (nearly) the same shift and the
+        // same start vector return the same vector m times, and no orthogonalisation makes a basis of the eigenspace out of that.
+        // Runs of eigenvalues closer than 64 eps |lambda|_max (chained) are such copies -- far below every gap of a spectrum that
+        // is simple in double precision at the accuracy of this solver, so the vectors of a simple spectrum keep their start and
+        // their bits.  Member r > 0 of a run is computed as LAPACK's DSTEIN computes a cluster: from a start vector of its own
+        // (eigvec.hip::invit_start), kept S-orthogonal to the r finished members before it in every step (invit_deflate) -- one
+        // launch per rank, so the members before it are there.  Its shift is the run's first eigenvalue moved down by
+        // 256 eps |lambda|_max: beside the backward error of the banded LU the shifted pencil is then a multiple of the identity on
+        // the eigenspace, and a solve does not turn the iterate back towards the members it was made orthogonal to.  The run lies
+        // inside one cluster of the rule below (64 eps << 1e-3), whose Gram-Schmidt and Cholesky QR finish the basis.
+        double wmax = 0.0;
+        for (int i = 0; i < n; ++i) wmax = std::fmax(wmax, std::fabs(w[i]));
+        const double ulp = 2.220446049250313e-16 * wmax, dtol = 64.0 * ulp;
+        std::vector<int> start(n, 0);
+        std::vector<double> shift(w, w + n);
+        int rmax = 0;
+        for (int i = 1; i < n; ++i)
+            if (w[i] - w[i - 1] <= dtol) {
+                start[i] = start[i - 1] + 1;
+                shift[i] = w[i - start[i]] - 256.0 * ulp;
+                if (start[i] > rmax) rmax = start[i];
+            }
+        DBuf<int> dstart;
+        DBuf<double> dshift;
+        if (rmax > 0) {
+            if (dstart.alloc(n) != hipSuccess || dshift.alloc(n) != hipSuccess) { fail("out of device memory (eigenvectors)"); return; }
+            hipMemcpy(dstart.p, start.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice);
+            hipMemcpy(dshift.p, shift.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice);
         }
+        for (int rank = 0; rank <= rmax && !rc; ++rank)
+            for (int done = 0; done < n && !rc; done += chunk) {
+                const int m = (n - done < chunk) ? n - done : chunk;
+                rc = launch_inverse_iteration(n, k, m, dSB.p, dHB.p, dchan.p, (rmax > 0 ? dshift.p : dE.p) + done, dvw.p,
+                                              dvec.p + (size_t)done * n, dinfo.p, 0, rmax > 0 ? dstart.p + done : nullptr, rank);
+            }
         if (rc || hipDeviceSynchronize() != hipSuccess) { fail("the inverse iteration failed"); return; }
         hipMemcpy(&cinfo, dinfo.p, sizeof(int), hipMemcpyDeviceToHost);
         if (cinfo) { fail("an inverse iteration broke down"); *info = cinfo <= n ? cinfo : n; return; }
@@ -281,9 +314,7 @@ extern "C" void bsp_dsygv_(const int *itype, const char *jobz, const char *uplo,
         // 1e-5 left 7e-11 between neighbours just outside a cluster, and 1e-3 leaves 2e-13.  On the reference's pencils that
         // makes the whole spectrum one cluster (4 n^3 flop of blocked Gram-Schmidt on the MFMA GEMM: ~15 ms at n = 4096).
         // The vectors move to a padded array (ld npad, the extent the GEMM kernels want) for that.
-        double lmax = 0.0;
-        for (int i = 0; i < n; ++i) lmax = std::fmax(lmax, std::fabs(w[i]));
-        const double ctol = 1e-3 * lmax;
+        const double lmax = wmax, ctol = 1e-3 * lmax;
         int mmax = 0;
         for (int c0 = 0; c0 < n;) {
             int c1 = c0 + 1;

@@ -72,22 +72,63 @@ __device__ __forceinline__ void y_sync()
     else lds_sync();
 }
 
+// Start vector of the inverse iteration.  seed 0: the constant vector, the start of every vector of a simple spectrum.  seed r > 0:
+// member r of a run of eigenvalues that coincide to rounding (dsygv.hip): equal shifts and equal starts give equal vectors, so the
+// members after the first start from entries in [-1, 1) that depend on (r, j) alone -- the same bits in every call -- and are kept
+// S-orthogonal to the members before them (invit_deflate).
+__device__ __forceinline__ double invit_start(int seed, int j)
+{
+    if (seed == 0) return 1.0;
+    unsigned h = (unsigned)seed * 0x9E3779B9u ^ ((unsigned)j + 1u) * 0x85EBCA6Bu;
+    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+    return (double)(int)h * (1.0 / 2147483648.0);
+}
+
+// y <- y - sum_q z_q (z_q^T S y) over the cnt vectors in front of vec (z_q = vec - q n: the finished members of the run, S-orthonormal).
+// Lane-local: a lane reads and writes only the entries y[j], j = lane mod 64, so no synchronisation is needed between the terms.
+__device__ __forceinline__ void invit_deflate(int n, int b, const double *__restrict__ SB, double *y, const double *vec, int cnt, int lane)
+{
+    for (int q = 1; q <= cnt; ++q) {
+        const double *z = vec - (size_t)q * n;
+        double s = 0.0;
+        for (int j = lane; j < n; j += 64) {
+            double t = 0.0;
+            for (int d = -b; d <= b; ++d) {
+                const int c = j + d;
+                if (c >= 0 && c < n) {
+                    const int ad = d < 0 ? -d : d, lo = d < 0 ? c : j;
+                    t += SB[(size_t)ad * n + lo] * z[c];
+                }
+            }
+            s += t * y[j];
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        for (int j = lane; j < n; j += 64) y[j] -= s * z[j];
+    }
+}
+
 // BT >= b = k - 1: rows of the register window (instances 8 and 15).  One wavefront (lane = its lane); y: n doubles of LDS (YG false)
 // or of global memory (YG true: every pass boundary waits for the wave's global stores, y_sync); work: n (3 b + 3) doubles;
 // *info <- iv + 1 if the iterate vanished.  The arithmetic does not depend on YG.
 template <int BT, bool YG = false>
 __device__ __forceinline__ void invit_body(int n, int k, const double *__restrict__ SB, const double *__restrict__ HB, const double E,
-                                           double *work, double *vec, int *info, int iv, double *y, const int lane)
+                                           double *work, double *vec, int *info, int iv, double *y, const int lane, const int seed = 0)
 {
     const int b = k - 1;
     double *U = work, *Lm = work + (size_t)n * (2 * b + 1), *piv = Lm + (size_t)n * b, *tmp = piv + n;
 
     // scale for the zero-pivot perturbation: ~ eps * max|M_jj|
-    double dmax = 0.0;
-    for (int j = lane; j < n; j += 64) dmax = fmax(dmax, fabs(HB[j] - E * SB[j]));
+    // (floor: where the whole diagonal of H - E S cancels -- n = 1, or H a multiple of S on the diagonal -- the scale is eps times
+    // the terms that cancelled, so that 1 / pivot stays finite; everywhere else it is far below dmax and changes nothing)
+    double dmax = 0.0, dflo = 0.0;
+    for (int j = lane; j < n; j += 64) {
+        dmax = fmax(dmax, fabs(HB[j] - E * SB[j]));
+        dflo = fmax(dflo, fabs(HB[j]) + fabs(E * SB[j]));
+    }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) dmax = fmax(dmax, __shfl_xor(dmax, off));
-    const double pertol = 2.220446049250313e-16 * fmax(dmax, 1e-300);
+    for (int off = 32; off >= 1; off >>= 1) { dmax = fmax(dmax, __shfl_xor(dmax, off)); dflo = fmax(dflo, __shfl_xor(dflo, off)); }
+    const double pertol = 2.220446049250313e-16 * fmax(fmax(dmax, 2.220446049250313e-16 * dflo), 1e-280);
 
     // ---- banded LU with partial pivoting (LINPACK dgbfa's row window), the window in REGISTERS (round 4): lane c (0 .. 2 b) holds
     // column j + c of the rows j .. j + b, a[t] = M(j + t, j + c).  The pivot search runs down lane 0's registers, the pivot row
@@ -156,7 +197,8 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
     }
 
     // ---- inverse iteration: 3 solves ----
-    for (int j = lane; j < n; j += 64) y[j] = 1.0;
+    for (int j = lane; j < n; j += 64) y[j] = invit_start(seed, j);
+    if (seed > 0) invit_deflate(n, b, SB, y, vec, seed, lane);     // member `seed` of a run: start S-orthogonal to the members before it
     __syncthreads();                                   // also: U, L, piv are in memory (vmcnt(0))
     if constexpr (YG) y_sync<YG>();                    // (y_sync: y = 1 is in memory before the forward pass reads it)
     for (int iter = 0; iter < 3; ++iter) {
@@ -260,6 +302,8 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
             }
             y_sync<YG>();
         }
+        // member of a run of coinciding eigenvalues: stay S-orthogonal to the members before it (as LAPACK's DSTEIN does in a cluster)
+        if (seed > 0) invit_deflate(n, b, SB, y, vec, seed, lane);
         // normalise by max-abs, then rhs = S x for the next iteration
         double mx = 0.0;
         for (int j = lane; j < n; j += 64) mx = fmax(mx, fabs(y[j]));
@@ -322,18 +366,23 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
     for (int j = lane; j < n; j += 64) vec[j] = y[j] * nrm;
 }
 
-template <int BT>
+template <int BT, bool RUN = false>
 __global__ __launch_bounds__(64) void invit_kernel(int n, int k, const double *__restrict__ SB, const double *__restrict__ HBall,
                                                   const int *__restrict__ chan, const double *__restrict__ Eall,
-                                                  double *workall, double *vecall, int *info)
+                                                  double *workall, double *vecall, int *info, const int *__restrict__ start, int rank)
 {
     extern __shared__ double y[];                       // n doubles
+    // start (or null: every vector from the constant start): start[iv] = r for member r of a run of coinciding eigenvalues; a launch
+    // computes the members of ONE rank, rank r after the ranks before it: member r is kept S-orthogonal to the vectors iv - r .. iv - 1
+    // (RUN: the instance for rank > 0; the rank-0 instance has the constant start compiled in and the registers of the plain kernel)
+    if (start && start[blockIdx.x] != rank) return;
+    const int seed = RUN ? rank : 0;
     // one wavefront on a chain of dependent steps, usually beside the batched bisection whose waves are pure VALU work:
     // issue priority over them
     __builtin_amdgcn_s_setprio(3);
     const int iv = blockIdx.x, b = k - 1;
     invit_body<BT>(n, k, SB, HBall + (size_t)chan[iv] * k * n, Eall[iv], workall + (size_t)iv * ((size_t)n * (3 * b + 3)),
-                   vecall + (size_t)iv * n, info, iv, y, threadIdx.x);
+                   vecall + (size_t)iv * n, info, iv, y, threadIdx.x, seed);
 }
 
 // Throughput form (bspatom_eigvecs_batch): a PERSISTENT grid of single-wave workgroups, one per resident work slot (the
@@ -388,7 +437,7 @@ __global__ __launch_bounds__(BS_T) void early_vector_kernel(int n, int k, const 
 size_t invit_work_doubles(int n, int k) { return (size_t)n * (3 * (k - 1) + 3); }
 
 int launch_inverse_iteration(int n, int k, int nvec, const double *d_SB, const double *d_HB, const int *d_chan,
-                             const double *d_E, double *d_work, double *d_vec, int *d_info, hipStream_t st)
+                             const double *d_E, double *d_work, double *d_vec, int *d_info, hipStream_t st, const int *d_start, int rank)
 {
     if (k - 1 > EB_MAX || k < 2) return BSP_ERR_ARG;
     const size_t lds = (size_t)n * sizeof(double);
@@ -399,10 +448,18 @@ int launch_inverse_iteration(int n, int k, int nvec, const double *d_SB, const d
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
         BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(invit_kernel<EB_MAX>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(invit_kernel<8, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(invit_kernel<EB_MAX, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
         attr_set = true;
     }
-    if (k - 1 <= 8) hipLaunchKernelGGL(invit_kernel<8>, dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info);
-    else hipLaunchKernelGGL(invit_kernel<EB_MAX>, dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info);
+    if (rank > 0) {
+        if (!d_start) return BSP_ERR_ARG;
+        if (k - 1 <= 8) hipLaunchKernelGGL((invit_kernel<8, true>), dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info, d_start, rank);
+        else hipLaunchKernelGGL((invit_kernel<EB_MAX, true>), dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info, d_start, rank);
+    } else if (k - 1 <= 8) hipLaunchKernelGGL(invit_kernel<8>, dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info, d_start, rank);
+    else hipLaunchKernelGGL(invit_kernel<EB_MAX>, dim3(nvec), dim3(64), lds, st, n, k, d_SB, d_HB, d_chan, d_E, d_work, d_vec, d_info, d_start, rank);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
