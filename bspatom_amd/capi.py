@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_tdse_adaptive", "bspatom_tdse_adaptive_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -90,6 +90,8 @@ def lib():
         L.bspatom_tdse_static_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
         L.bspatom_tdse_fields.argtypes = L.bspatom_tdse_static.argtypes + [i32, vp]
         L.bspatom_tdse_fields_dev.argtypes = L.bspatom_tdse_static_dev.argtypes + [i32, vp]
+        L.bspatom_tdse_adaptive.argtypes = L.bspatom_tdse_static.argtypes + [i32, dbl, i32, i32, vp, i32, vp, vp, vp]
+        L.bspatom_tdse_adaptive_dev.argtypes = L.bspatom_tdse_static_dev.argtypes + [i32, dbl, i32, i32, vp, i32, vp, vp, vp]
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -565,6 +567,71 @@ class Problem:
                                            _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None),
              "bspatom_tdse_static_dev")
         return err
+
+    def tdse_adaptive(self, E, pairs, D, a0, fn, dt, static, tol, max_level, nsub=1, level0=0, scheme=1, obs_every=0, snap_every=0,
+                      log_cap=0):
+        """tdse_static with step-size control on the device (bspatom_tdse_adaptive): dt and the nsteps of fn describe the COARSE grid;
+        inside every coarse step the controller halves the step, down to dt / 2**max_level, until the embedded estimate of every scan is
+        within tol, and doubles it again where the estimate is below tol / 64.  fn: complex (nsteps * nsub + 1, 2, nscan), [i, 0, q] =
+        f_q and [i, 1, q] = df_q/dt at t0 + i dt / nsub (host.field_nodes); the library integrates the equation with the cubic Hermite
+        interpolant of these nodes.  Returns (a, err[, obs][, snaps], stats, log): obs and snaps on the coarse grid as tdse_static
+        gives them, stats int64 (6,) = accepted, rejected, forced, deepest level, level at the end (level0 of a continued run),
+        attempts; log = (log_i (nlog, 4) int32 rows (n, m, j, flag), log_e (nlog, nscan), log_f (nlog, 6, nscan) complex) of the first
+        log_cap attempts (host.adapt_steps).  The step sequence depends on all scans of the call; a forced step (flag 2) may exceed tol."""
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        nch, count = E.shape
+        ci, cf = self._tdse_pairs(pairs)
+        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
+        si, sf, skind, W = self._tdse_static(static, count)
+        a = np.array(a0, dtype=np.complex128, order="C")
+        one = a.ndim == 2
+        a = np.ascontiguousarray(a.reshape(-1, nch, count))
+        nscan = a.shape[0]
+        fn = np.ascontiguousarray(fn, dtype=np.complex128)
+        nsub = int(nsub)
+        if fn.ndim != 3 or fn.shape[1:] != (2, nscan) or nsub < 1 or (fn.shape[0] - 1) % nsub:
+            raise ValueError("fn must be (nsteps * nsub + 1, 2, nscan) with nscan = %d, nsub = %d, got %s" % (nscan, nsub, fn.shape))
+        nsteps = (fn.shape[0] - 1) // nsub
+        err = np.zeros(nscan)
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 6)) if obs_every > 0 else None
+        stats = np.zeros(6, dtype=np.int64)
+        log_i = np.zeros((log_cap, 4), dtype=np.int32) if log_cap > 0 else None
+        log_e = np.zeros((log_cap, nscan)) if log_cap > 0 else None
+        log_f = np.zeros((log_cap, 6, nscan), dtype=np.complex128) if log_cap > 0 else None
+        ns = len(si)
+        _chk(lib().bspatom_tdse_adaptive(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
+                                         _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(fn), _p(a), snap_every, _p(snaps),
+                                         _p(err), obs_every, _p(obs), int(scheme), ns, _p(si) if ns else None, _p(sf) if ns else None,
+                                         _p(skind) if ns else None, _p(W) if ns else None, nsub, float(tol), int(max_level), int(level0),
+                                         _p(stats), int(log_cap), _p(log_i), _p(log_e), _p(log_f)), "bspatom_tdse_adaptive")
+        if one:
+            a = a[0]
+        nlog = int(min(stats[5], log_cap))
+        log = (log_i[:nlog], log_e[:nlog], log_f[:nlog]) if log_cap > 0 else (np.zeros((0, 4), dtype=np.int32), np.zeros((0, nscan)),
+                                                                             np.zeros((0, 6, nscan), dtype=np.complex128))
+        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,)) + (stats, log)
+
+    def tdse_adaptive_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, fn_ptr, a_ptr, static, tol, max_level, nsub=1, level0=0,
+                          scheme=1, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None, log_cap=0, log_ptrs=None):
+        """tdse_adaptive on device memory: the arguments of tdse_static_dev with the node table ((nsteps * nsub + 1) * 2 * nscan complex)
+        at fn_ptr; log_ptrs = (log_i, log_e, log_f) device pointers for log_cap entries (4 int32, nscan doubles, 6 * nscan complex
+        each).  Returns (err (nscan,), stats (6,) int64) when the result is there."""
+        ci, cf = self._tdse_pairs(pairs)
+        si, sf, skind, W_ptr = self._tdse_static(static)
+        ns = len(si)
+        err = np.zeros(nscan)
+        stats = np.zeros(6, dtype=np.int64)
+        lp = [C.c_void_p(x) if x else None for x in (log_ptrs or (None, None, None))]
+        _chk(lib().bspatom_tdse_adaptive_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
+                                             _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
+                                             float(dt), C.c_void_p(fn_ptr) if fn_ptr else None, C.c_void_p(a_ptr), snap_every,
+                                             C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
+                                             C.c_void_p(obs_ptr) if obs_ptr else None, int(scheme), ns, _p(si) if ns else None,
+                                             _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None,
+                                             int(nsub), float(tol), int(max_level), int(level0), _p(stats), int(log_cap), lp[0], lp[1], lp[2]),
+             "bspatom_tdse_adaptive_dev")
+        return err, stats
 
     @staticmethod
     def _tdse_fidx(fidx, npairs):

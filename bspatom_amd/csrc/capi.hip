@@ -76,6 +76,7 @@ const OptName OPT_TABLE[] = {
     {"dipole_stage_mb", "BSP_DIPOLE_STAGE_MB", &Options::dipole_stage_mb},
     {"wf_stage_mb", "BSP_WF_STAGE_MB", &Options::wf_stage_mb},
     {"tdse_stage_mb", "BSP_TDSE_STAGE_MB", &Options::tdse_stage_mb},
+    {"tdse_adapt_group", "BSP_TDSE_ADAPT_GROUP", &Options::tdse_adapt_group},
 };
 }  // namespace
 

@@ -107,6 +107,8 @@ struct Options {
                                  // one group's eigenvector block) in MB (0 = 256 MiB); small values force several groups (the test's hook)
     int tdse_stage_mb = 0;       // BSP_TDSE_STAGE_MB: > 0 = device staging of bspatom_tdse_propagate's host variant (the field table and the snapshots of one
                                  // group of steps) in MB (0 = 256 MiB); small values force several groups (the test's hook)
+    int tdse_adapt_group = 0;    // BSP_TDSE_ADAPT_GROUP: > 0 = attempts that bspatom_tdse_adaptive enqueues between two looks at its control block (0 = 16); the
+                                 // result does not depend on it (the test's hook)
     int ktime = 0;               // 1: HIP events around every launch of the kernels in KSlot (bspatom_kernel_times; bench.py's
                                  // per-kernel roofline entries are measured with it in one extra, untimed step)
 };
@@ -338,6 +340,39 @@ int launch_tdse_fields_observe(const TdseDims &d, const TdseBufs &w, const doubl
 int launch_tdse_fields_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st);
 int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st);
 int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st);
+
+// tdse_adapt.hip: bspatom_tdse_adaptive.  The control block in device memory: this header, then at TDSE_CTL_HDR bytes the six field
+// values per scan of the coming attempt, fld[(s nscan + q) 2 + {0, 1}], then errmax[nscan], the largest estimate of an accepted step.
+// Only tdse_adapt_control_kernel writes it on the device; the host writes it between groups of launches, after the stream has drained.
+struct TdseAdaptCtl {
+    int n, m, j;                  // the coming attempt: coarse step, level, position
+    int flag;                     // the decision of the last attempt: 0 rejected, 1 accepted, 2 forced; -1 before the first
+    int done;                     // n == nend: every launch behind it returns at its first instruction
+    int nend;                     // the end of the group of coarse steps that is staged
+    int row, snap;                // where the row of the coming attempt goes / the snapshot of the accepted one, within the group; -1: none
+    int row0, snap0, node0;       // the group's first row, snapshot and field node
+    int pad_;
+    long long acc_t;              // the number of the last accepted attempt (tdse_adapt_commit_kernel compares its own with it), -1
+    long long stats[6];           // accepted, rejected, forced, deepest level, (level at the end: m), attempts
+};
+constexpr size_t TDSE_CTL_HDR = 128;
+static_assert(sizeof(TdseAdaptCtl) <= TDSE_CTL_HDR, "the arrays of the control block start behind its header");
+inline size_t tdse_ctl_bytes(int nscan) { return TDSE_CTL_HDR + (size_t)13 * nscan * sizeof(double); }
+__host__ __device__ inline const double *tdse_ctl_fld(const TdseAdaptCtl *c) { return (const double *)((const char *)c + TDSE_CTL_HDR); }
+// what the controller is given besides the block; the log arrays may be null (log_cap = 0)
+struct TdseAdaptArgs {
+    int nsub, max_level, snap_every, obs_every, log_cap;
+    double dt, tol;
+    const double *fn;             // the nodes of the staged group, from node0 on
+    int *log_i;
+    double *log_e, *log_f;
+};
+// the field of the attempt (n, m, j) of a fresh block or a new group: the controller's last part alone
+int launch_tdse_adapt_init(const TdseDims &d, const TdseBufs &w, TdseAdaptCtl *ctl, const TdseAdaptArgs &g, hipStream_t st);
+// one attempt, number t: six stages (stage 0 observing, with the reduction to the row ctl->row of d_obs, when d_obs is given), the step into
+// the candidate buffer cand, the controller, the commit (a, and the snapshot ctl->snap of d_snap).  w.ph: one table per level, phlev doubles each
+int launch_tdse_adapt_attempt(const TdseDims &d, const TdseBufs &w, TdseAdaptCtl *ctl, const TdseAdaptArgs &g, long long t, double *cand,
+                              size_t phlev, double *d_snap, double *d_obs, hipStream_t st);
 
 // capi.hip: enqueue Cholesky -> standard form -> sy2sb -> sb2st -> bisection on `st` for nl channels
 // whose upper bands are already in d_SB / d_HB.  ev (optional): 5 events recorded at the stage

@@ -109,75 +109,7 @@ __global__ __launch_bounds__(256) void tdse_obs_reduce_kernel(int nch, int tm, i
     for (int k = 0; k < 4; ++k) row[(size_t)t * 4 + k] = s[k];
 }
 
-// ---- the step: a += dt sum_s d_s k_s, the error estimate, the snapshot ------------------------------------------------------
-// One thread per (state row, scan): 32 rows x 8 scans per workgroup, the 16 real columns of 8 scans contiguous.  err2[q] (bit
-// pattern of a non-negative double) takes the maximum of |sum_s (d_s - b_s) k_s|^2 with an integer atomic maximum: order-independent.
-// snap (or null): the new amplitudes in the caller's layout [nscan][nch * count] complex.
-// LAWSON: the update and the estimate from the k_s as they are, then a_{n+1} = R_4 .* (the sum), ph4 = the phases of s = 4 [rows][2];
-// what is stored and what the snapshot takes is the rotated value.
-struct StepCoef { double d[6], e[6]; };
-
-template <bool LAWSON>
-__device__ __forceinline__ void tdse_step_body(long long rows, int NC, int nscan, double *__restrict__ a, const double *__restrict__ K,
-                                               size_t kstride, const StepCoef &sc, double dt, unsigned long long *__restrict__ err2,
-                                               double *__restrict__ snap, const double *__restrict__ ph4)
-{
-    __shared__ double smax[4][8];
-    const int tid = threadIdx.x, ql = tid & 7, lane = tid & 63, wave = tid >> 6;
-    const int q = blockIdx.y * 8 + ql;
-    const long long row = (long long)blockIdx.x * 32 + (tid >> 3);
-    const bool ok = row < rows && 2 * q < NC;
-    double m2 = 0.0;
-    if (ok) {
-        const size_t idx = (size_t)row * NC + 2 * q;
-        double s[2], e[2];
-#pragma unroll
-        for (int ri = 0; ri < 2; ++ri) {
-            const double k0 = K[idx + ri];
-            s[ri] = sc.d[0] * k0;
-            e[ri] = sc.e[0] * k0;
-#pragma unroll
-            for (int j = 2; j < 6; ++j) {               // the second stage has weight 0 in both formulas
-                const double kj = K[(size_t)j * kstride + idx + ri];
-                s[ri] = fma(sc.d[j], kj, s[ri]);
-                e[ri] = fma(sc.e[j], kj, e[ri]);
-            }
-            s[ri] = fma(dt, s[ri], a[idx + ri]);
-            if constexpr (!LAWSON) a[idx + ri] = s[ri];
-        }
-        if constexpr (LAWSON) {
-            // (cos - i sin)(s_re + i s_im)
-            const double pc = ph4[(size_t)row * 2], psn = ph4[(size_t)row * 2 + 1];
-            const double re = fma(psn, s[1], pc * s[0]), im = fma(-psn, s[0], pc * s[1]);
-            s[0] = re;
-            s[1] = im;
-            a[idx] = re;
-            a[idx + 1] = im;
-        }
-        m2 = fma(e[0], e[0], e[1] * e[1]);
-        if (snap && q < nscan) {
-            double *o = snap + ((size_t)q * rows + row) * 2;
-            o[0] = s[0];
-            o[1] = s[1];
-        }
-    }
-    // maximum over the 8 lanes of a wave with the same scan, then over the 4 waves.  A NaN never wins a comparison here.
-#pragma unroll
-    for (int sh = 8; sh < 64; sh <<= 1) {
-        const double o = __shfl_xor(m2, sh);
-        m2 = o > m2 ? o : m2;
-    }
-    if (lane < 8) smax[wave][lane] = m2;
-    __syncthreads();
-    if (tid < 8) {
-        double m = smax[0][tid];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) m = smax[w][tid] > m ? smax[w][tid] : m;
-        const int qq = blockIdx.y * 8 + tid;
-        if (qq < nscan && m > 0.0) atomicMax(&err2[qq], (unsigned long long)__double_as_longlong(m));
-    }
-}
-
+// ---- the step: tdse_step_body (tdse_stage.h) ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tdse_step_kernel(long long rows, int NC, int nscan, double *__restrict__ a,
                                                        const double *__restrict__ K, size_t kstride, StepCoef sc, double dt,
                                                        unsigned long long *__restrict__ err2, double *__restrict__ snap)

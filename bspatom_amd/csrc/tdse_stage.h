@@ -1,5 +1,5 @@
-// tdse_stage.h -- the stage of the TDSE step (tdse.hip, tdse_static.hip): one body for every scheme, instantiated by the kernels of
-// both files.  Device code only.
+// tdse_stage.h -- the stage and the step of the TDSE (tdse.hip, tdse_static.hip, tdse_fields.hip, tdse_adapt.hip): one body each for
+// every scheme, instantiated by the kernels of these files.  Device code only.
 #pragma once
 #include "common.h"
 #include "mfma_tile.h"
@@ -87,16 +87,29 @@ template <int NF> __device__ __forceinline__ int ent_kind(int kd)
     else return kd;
 }
 
-template <int S, int TN, bool OBS, bool LAWSON, bool STAT = false, int NF = 1>
+//
+// ADAPT (bspatom_tdse_adaptive, tdse_adapt.hip; always with STAT, NF = 1): the step size, the field and the phase table of the attempt
+// come from the control block ctl: dt = ldexp(dt, -ctl->m) after one uniform load, fld = the block's six values per scan, phs moves
+// phlev doubles per level, and a launch enqueued behind the end of the run returns at once.  Everything after that is the code above.
+template <int S, int TN, bool OBS, bool LAWSON, bool STAT = false, int NF = 1, bool ADAPT = false>
 __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, int tm, int tn, const int *__restrict__ cptr,
                                                 const int *__restrict__ ent, const double *__restrict__ E,
                                                 const double *__restrict__ D, const double *__restrict__ a,
                                                 double *__restrict__ K, size_t kstride, const double *__restrict__ fld,
                                                 StageCoef cf, double dt, double *__restrict__ part, const double *__restrict__ phs,
-                                                const double *__restrict__ Wst = nullptr)
+                                                const double *__restrict__ Wst = nullptr, const TdseAdaptCtl *__restrict__ ctl = nullptr,
+                                                size_t phlev = 0)
 {
     static_assert(!OBS || S == 0, "only stage 0 runs on a(t_n)");
     static_assert(NF == 1 || STAT, "several fields run with the static accumulator");
+    static_assert(!ADAPT || (STAT && NF == 1), "the adaptive call runs the static stage with one field");
+    if constexpr (ADAPT) {
+        if (ctl->done) return;
+        const int lev = ctl->m;
+        dt = ldexp(dt, -lev);
+        fld = tdse_ctl_fld(ctl) + (size_t)S * 2 * nscan;
+        if constexpr (LAWSON && S > 0) phs += (size_t)lev * phlev;
+    }
     constexpr int PW = NF > 1 ? 4 + 2 * NF : STAT ? 6 : 4;                    // doubles of a partial
     constexpr bool ROT = LAWSON && S > 0;                                     // R_0 = 1; phs: this stage's phases [nch][count][2]
     constexpr int NB = 16 * TN, TLDB = NB + 16, BEL = TBK * NB / 256;        // B-tile elements per thread: 1 or 2
@@ -397,6 +410,94 @@ __device__ __forceinline__ void tdse_stage_body(int count, int NC, int nscan, in
             const int q = ((n0 + j * 16) >> 1) + s8;
             if (q < nscan) part[(((size_t)c * tm + im) * (NC >> 1) + q) * 4 + k] = s;
         }
+    }
+}
+
+// ---- the step: a += dt sum_s d_s k_s, the error estimate, the snapshot ------------------------------------------------------
+// One thread per (state row, scan): 32 rows x 8 scans per workgroup, the 16 real columns of 8 scans contiguous.  err2[q] (bit
+// pattern of a non-negative double) takes the maximum of |sum_s (d_s - b_s) k_s|^2 with an integer atomic maximum: order-independent.
+// snap (or null): the new amplitudes in the caller's layout [nscan][nch * count] complex.
+// LAWSON: the update and the estimate from the k_s as they are, then a_{n+1} = R_4 .* (the sum), ph4 = the phases of s = 4 [rows][2];
+// what is stored and what the snapshot takes is the rotated value.
+// ADAPT (bspatom_tdse_adaptive): dt = ldexp(dt, -ctl->m), ph4 moves phlev doubles per level, the new amplitudes go to the candidate
+// buffer cand instead of a (tdse_adapt_commit_kernel copies them and writes the snapshot once the step is accepted), and a launch
+// behind the end of the run returns at once.  The arithmetic is the one above.
+struct StepCoef { double d[6], e[6]; };
+
+template <bool LAWSON, bool ADAPT = false>
+__device__ __forceinline__ void tdse_step_body(long long rows, int NC, int nscan, double *__restrict__ a, const double *__restrict__ K,
+                                               size_t kstride, const StepCoef &sc, double dt, unsigned long long *__restrict__ err2,
+                                               double *__restrict__ snap, const double *__restrict__ ph4,
+                                               const TdseAdaptCtl *__restrict__ ctl = nullptr, size_t phlev = 0,
+                                               double *__restrict__ cand = nullptr)
+{
+    if constexpr (ADAPT) {
+        if (ctl->done) return;
+        const int lev = ctl->m;
+        dt = ldexp(dt, -lev);
+        if constexpr (LAWSON) ph4 += (size_t)lev * phlev;
+    }
+    __shared__ double smax[4][8];
+    const int tid = threadIdx.x, ql = tid & 7, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.y * 8 + ql;
+    const long long row = (long long)blockIdx.x * 32 + (tid >> 3);
+    const bool ok = row < rows && 2 * q < NC;
+    double m2 = 0.0;
+    if (ok) {
+        const size_t idx = (size_t)row * NC + 2 * q;
+        double s[2], e[2];
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri) {
+            const double k0 = K[idx + ri];
+            s[ri] = sc.d[0] * k0;
+            e[ri] = sc.e[0] * k0;
+#pragma unroll
+            for (int j = 2; j < 6; ++j) {               // the second stage has weight 0 in both formulas
+                const double kj = K[(size_t)j * kstride + idx + ri];
+                s[ri] = fma(sc.d[j], kj, s[ri]);
+                e[ri] = fma(sc.e[j], kj, e[ri]);
+            }
+            s[ri] = fma(dt, s[ri], a[idx + ri]);
+            if constexpr (!LAWSON) {
+                if constexpr (ADAPT) cand[idx + ri] = s[ri];
+                else a[idx + ri] = s[ri];
+            }
+        }
+        if constexpr (LAWSON) {
+            // (cos - i sin)(s_re + i s_im)
+            const double pc = ph4[(size_t)row * 2], psn = ph4[(size_t)row * 2 + 1];
+            const double re = fma(psn, s[1], pc * s[0]), im = fma(-psn, s[0], pc * s[1]);
+            s[0] = re;
+            s[1] = im;
+            if constexpr (ADAPT) {
+                cand[idx] = re;
+                cand[idx + 1] = im;
+            } else {
+                a[idx] = re;
+                a[idx + 1] = im;
+            }
+        }
+        m2 = fma(e[0], e[0], e[1] * e[1]);
+        if (!ADAPT && snap && q < nscan) {
+            double *o = snap + ((size_t)q * rows + row) * 2;
+            o[0] = s[0];
+            o[1] = s[1];
+        }
+    }
+    // maximum over the 8 lanes of a wave with the same scan, then over the 4 waves.  A NaN never wins a comparison here.
+#pragma unroll
+    for (int sh = 8; sh < 64; sh <<= 1) {
+        const double o = __shfl_xor(m2, sh);
+        m2 = o > m2 ? o : m2;
+    }
+    if (lane < 8) smax[wave][lane] = m2;
+    __syncthreads();
+    if (tid < 8) {
+        double m = smax[0][tid];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) m = smax[w][tid] > m ? smax[w][tid] : m;
+        const int qq = blockIdx.y * 8 + tid;
+        if (qq < nscan && m > 0.0) atomicMax(&err2[qq], (unsigned long long)__double_as_longlong(m));
     }
 }
 

@@ -496,6 +496,42 @@ def field_table(fns, t0, dt, nsteps):
     return out
 
 
+def field_nodes(fns, dfns, t0, dt, nsteps, nsub):
+    """The fn argument of Problem.tdse_adaptive: complex (nsteps * nsub + 1, 2, nscan), [i, 0, q] = f_q and [i, 1, q] = df_q/dt at the
+    nodes t0 + i dt / nsub.  fns: one callable of the array of times per scan; dfns: their time derivatives, or None: then the
+    derivative is the centred difference (f(t + d) - f(t - d)) / (2 d) with d = hf / 8, hf = dt / nsub the node spacing (its error is
+    O(hf^2) times the third derivative, O(hf^3) in the interpolated field; give dfns where that matters)."""
+    import numpy as np
+    if nsteps < 0 or nsub < 1:
+        raise ValueError("field_nodes needs nsteps >= 0 and nsub >= 1")
+    hf = float(dt) / nsub
+    t = float(t0) + np.arange(nsteps * nsub + 1, dtype=np.float64) * hf
+    fns = list(fns)
+    dfns = None if dfns is None else list(dfns)
+    if dfns is not None and len(dfns) != len(fns):
+        raise ValueError("field_nodes: %d fields but %d derivatives" % (len(fns), len(dfns)))
+    out = np.zeros((len(t), 2, len(fns)), dtype=np.complex128)
+    d = hf / 8.0
+    for q, f in enumerate(fns):
+        out[:, 0, q] = np.asarray(f(t), dtype=np.complex128)
+        if dfns is None:
+            out[:, 1, q] = (np.asarray(f(t + d), dtype=np.complex128) - np.asarray(f(t - d), dtype=np.complex128)) / (2.0 * d)
+        else:
+            out[:, 1, q] = np.asarray(dfns[q](t), dtype=np.complex128)
+    return out
+
+
+def adapt_steps(log_i, t0, dt):
+    """The accepted steps of the log of Problem.tdse_adaptive: (t, h), the start time t0 + dt (n + j / 2^m) and the size dt / 2^m of
+    every attempt with flag 1 or 2 in log_i (nlog, 4) rows (n, m, j, flag), in order."""
+    import numpy as np
+    li = np.asarray(log_i, dtype=np.int64).reshape(-1, 4)
+    li = li[li[:, 3] > 0]
+    n, m, j = li[:, 0], li[:, 1].astype(np.int32), li[:, 2]
+    t = float(t0) + float(dt) * (n.astype(np.float64) + np.ldexp(j.astype(np.float64), -m))
+    return t, np.ldexp(np.full(len(li), float(dt)), -m)
+
+
 def obs_steps(nsteps, obs_every):
     """The step numbers n_j of the rows of Problem.tdse_observe: 0, obs_every, 2 obs_every, .. < nsteps, then nsteps; row j
     describes a(t0 + n_j dt).  nsteps = 0: the one row [0]."""

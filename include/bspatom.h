@@ -242,7 +242,7 @@ int bspatom_wavefunctions_dev(bspatom_problem *p, int l0, int nl, int n0, int co
  * Integrator: nsteps fixed steps dt of the six-stage embedded pair of MOD_RK_PARAMS: y_s = a + dt sum_{j<s} A_sj k_j,
  * k_s = -i H(t_n + c_s dt) y_s, c = (0, 2/9, 1/3, 3/4, 1, 5/6); a_{n+1} = a_n + dt sum_s d_s k_s with the 5th-order weights
  * d = (47/450, 0, 12/25, 32/225, 1/30, 6/25); err[q] = max over steps, channels, states of dt |sum_s (d_s - b_s) k_s|,
- * b = (1/9, 0, 9/20, 16/45, 1/12, 0).  No step-size control (a result is a function of its inputs alone); stability, dt max|E|, is the
+ * b = (1/9, 0, 9/20, 16/45, 1/12, 0).  No step-size control here (bspatom_tdse_adaptive below resizes the step from err); stability, dt max|E|, is the
  * caller's business (bspatom_tdse_lawson below removes that bound); amplitudes are not checked for finiteness.
  * The library never evaluates a pulse: field[((n*6 + s)*nscan + q)*2 + {0,1}] = Re, Im of f_q(t0 + (n + c_s) dt).
  *   a    [((q*nch + c)*count + n)*2 + {0,1}] (complex128 of shape (nscan, nch, count)); in: a(t0), out: a(t0 + nsteps dt)
@@ -422,6 +422,78 @@ int bspatom_tdse_fields_dev(bspatom_problem *p, int nch, int count, const double
                             int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W_dev, int nfield,
                             const int32_t *fidx);
 
+/* The run of bspatom_tdse_static (one field, driven pairs, static blocks, scheme 0 plain or 1 Lawson) with step-size control on the device
+ * from the embedded estimate.  The first 24 arguments are bspatom_tdse_static's with two changes of meaning: dt and nsteps describe the
+ * COARSE grid t0 + n dt, and the field arrives as a node table fn that the library interpolates (the stage times are not known in advance).
+ * The step grid.  The controller's state is (n, m, j): coarse step 0 <= n < nsteps, level 0 <= m <= max_level, position 0 <= j < 2^m;
+ * the step is h = ldexp(dt, -m) and starts at t0 + dt (n + j / 2^m).  It starts at (0, level0, 0).  After an attempt, e = max_q err_q,
+ * err_q = h max |sum_s (d_s - b_s) k_s| of that attempt (the estimate of the other calls with h in the place of dt):
+ *     e <= tol                          accepted
+ *     not, and m == max_level           accepted as FORCED and counted (also an e that does not compare, a NaN)
+ *     otherwise                         rejected: (n, m + 1, 2 j), a untouched
+ *   after an accepted step: j += 1; if e <= tol * 0.015625 and m > 0 and j is even: m -= 1, j >>= 1 (the local error scales as h^5, a
+ *   doubled step multiplies it by 32; the factor 2 left over keeps a coarsened step from being rejected at once); if j == 2^m:
+ *   n += 1, j = 0.  The level is carried across coarse steps.  tol = +inf never rejects.  max_level <= BSPATOM_TDSE_MAX_LEVEL.
+ *   Stage times: x_s = ldexp((double)j + c_s, -m), t_s = t0 + dt * ((double)n + x_s), c_s the double nearest the fraction; IEEE operations.
+ *   Attempts per coarse step: at most 2^max_level accepted; a rejection either deepens the level or follows a coarsening, of which there
+ *   is at most one per accepted step: no more than 2^(max_level + 1) + max_level attempts.  A run that exceeds this is an internal error:
+ *   BSPATOM_ERR_HIP with a message on stderr.
+ * The field.  nsub >= 1 intervals per coarse step, node i at t0 + i dt / nsub, i = 0 .. nsteps * nsub:
+ *     fn[((i*2 + k)*nscan + q)*2 + {0,1}], k = 0: f_q, k = 1: d f_q / dt.
+ *   At x_s: i_loc = min((int)floor(x_s * nsub), nsub - 1), u = x_s * nsub - i_loc, hf = dt / nsub, with i = n nsub + i_loc
+ *     omu = 1 - u; omu2 = omu * omu; u2 = u * u;
+ *     h00 = (1 + 2 u) * omu2;  h10 = u * omu2;  h01 = u2 * (3 - 2 u);  h11 = u2 * (u - 1);
+ *     f = ((h00 * f_i + (h10 * hf) * f'_i) + h01 * f_{i+1}) + (h11 * hf) * f'_{i+1}
+ *   in IEEE multiplies and adds in exactly this order, no FMA, Re and Im independently.  THE EQUATION THAT IS INTEGRATED IS THE ONE WITH
+ *   THIS PIECEWISE-CUBIC FIELD: it is C1 and depends on fn alone; how well it follows the caller's pulse is the caller's choice of nsub.
+ * What comes back:
+ *   a, snap, err as in bspatom_tdse_static; a snapshot after every snap_every-th COARSE step; err[q] the maximum over accepted steps.
+ *   obs: rows of 6 for the coarse steps 0, obs_every, .. < nsteps and the final state (nobs as in bspatom_tdse_observe): a uniform time
+ *   grid whatever the controller does.
+ *   stats[6]: accepted, rejected, forced steps, the deepest level of an attempt, the level at the end (fed back as level0 it continues a
+ *   run), attempts; all counted whether logged or not.
+ *   the log of the first log_cap attempts (t = 0, 1, ..): log_i[4 t] = (n, m, j, flag), flag 0 rejected, 1 accepted, 2 forced;
+ *   log_e[t*nscan + q] the estimate per scan; log_f[((t*6 + s)*nscan + q)*2 + {0,1}] the field values the attempt used.
+ * How: a control block in device memory holds (n, m, j), the last decision, a done flag, the six field values per scan of the coming
+ * attempt and the counters.  An attempt is a fixed sequence of launches: the six stages of the static call (tdse_stage.h with its ADAPT
+ * flag: h from the block by one load and ldexp, the field from the block; stage 0 observing, with the reduction to the row the block
+ * names, on every attempt when rows are asked for), the step into a CANDIDATE buffer, tdse_adapt_control_kernel (one workgroup: judges,
+ * advances (n, m, j), writes the log entry, interpolates the field of the coming attempt, sets done at the end) and
+ * tdse_adapt_commit_kernel, which copies an accepted candidate into a and writes its snapshot: 9 launches, 10 with rows.  No kernel waits
+ * for another.  The host enqueues attempts in groups of 16 (bspatom_set_option("tdse_adapt_group", g) sets another size), copies the
+ * block back, synchronises and goes on until done; launches enqueued
+ * behind the end return at their first instruction.  Lawson: one phase table per level 0 .. max_level, each from tdse_phase_kernel with
+ * dt = h, before the first attempt.  The host variant stages fn, the snapshots and the rows under tdse_stage_mb by groups of coarse steps.
+ * Guarantees:
+ *   1. chain identity: the accepted steps of the log, replayed in order as bspatom_tdse_static calls with nsteps = 1, dt = h of the step
+ *      and the (1, 6, nscan) table from log_f, reproduce a, every snapshot, the per-step err (= log_e) and k = 0 .. 5 of every row bit
+ *      for bit: the stage arithmetic is the static call's, the controller only chooses h;
+ *   2. fixed-step identity: with tol = +inf and level0 = 0, a, snap, err and the rows equal one bspatom_tdse_static call with nsteps, dt
+ *      and log_f as its table, bit for bit;
+ *   3. every decision in the log follows from the logged estimate by the rule above, exactly;
+ *   4. results are run-to-run bit-identical; nothing depends on obs_every, snap_every, log_cap, the enqueue group size or the staging bound;
+ *   5. a run continued from a snapshot with level0 = stats[4] of the shorter run equals the long run, bit for bit;
+ *   6. THE STEP SEQUENCE DEPENDS ON ALL SCANS OF THE CALL, because the worst one decides; given the sequence, a scan's amplitudes depend
+ *      on that scan alone (guarantee 1 with a single scan in each replay call).
+ * What it does not give: a forced step can exceed tol (stats[2] counts them: raise max_level or shorten dt); tol bounds the local
+ * estimate of the 4th-order formula per step, not the global error.
+ * BSPATOM_ERR_ARG: everything bspatom_tdse_static names (fn in the place of field); tol not positive or NaN; max_level < 0; level0
+ * outside 0..max_level; nsub < 1; fn NULL with nsteps > 0; stats NULL; log_cap < 0; log_cap > 0 with a null log array.
+ * BSPATOM_ERR_UNSUPPORTED: max_level > BSPATOM_TDSE_MAX_LEVEL.  The _dev variant: fn_dev and the three log arrays in device memory as
+ * well; stats and err host pointers. */
+#define BSPATOM_TDSE_MAX_LEVEL 16
+int bspatom_tdse_adaptive(bspatom_problem *p, int nch, int count, const double *E, int npairs, const int32_t *ci, const int32_t *cf,
+                          const double *D, int nscan, int nsteps, double dt, const double *fn, double *a, int snap_every, double *snap,
+                          double *err, int obs_every, double *obs, int scheme, int nstat, const int32_t *si, const int32_t *sf,
+                          const int32_t *skind, const double *W, int nsub, double tol, int max_level, int level0, int64_t *stats,
+                          int log_cap, int32_t *log_i, double *log_e, double *log_f);
+int bspatom_tdse_adaptive_dev(bspatom_problem *p, int nch, int count, const double *E_dev, int npairs, const int32_t *ci,
+                              const int32_t *cf, const double *D_dev, int nscan, int nsteps, double dt, const double *fn_dev,
+                              double *a_dev, int snap_every, double *snap_dev, double *err, int obs_every, double *obs_dev, int scheme,
+                              int nstat, const int32_t *si, const int32_t *sf, const int32_t *skind, const double *W_dev, int nsub,
+                              double tol, int max_level, int level0, int64_t *stats, int log_cap, int32_t *log_i_dev, double *log_e_dev,
+                              double *log_f_dev);
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
@@ -437,7 +509,7 @@ int bspatom_last_timing(const bspatom_problem *p, double ms[6]);
  * times and launch counts per slot since the previous call into ms[] / launches[] (cap >= the slot count, which it returns)
  * and forgets them.  Slots: 0 rank-128 update (syr2k), 1 symm, 2 panel QR, 3 the small products of the panel chain,
  * 4 sb2sb_mfma_kernel, 5 sbr_rows_kernel<8> / <16> (sb16st_kernel with BSP_SB16_ROWS=0), 6 batched bisection, 7 Cholesky + standard form,
- * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel and tdse_observe_kernel, their Lawson and static variants and tdse_phase_kernel (tdse.hip, tdse_static.hip);
+ * 8 the band route's reduction (crawford.hip), 9 operator_band_kernel (opmat.hip), 10 tdse_stage_kernel and tdse_observe_kernel, their Lawson and static variants and tdse_phase_kernel (tdse.hip, tdse_static.hip), and every kernel of bspatom_tdse_adaptive (tdse_adapt.hip: its stages, step, reduction, tdse_adapt_control_kernel, tdse_adapt_commit_kernel);
  * bspatom_kernel_slot_name(i) names them.  Launches on different streams overlap: the sums are sums of launch durations, not wall time. */
 int bspatom_kernel_times(double *ms, int32_t *launches, int cap);
 const char *bspatom_kernel_slot_name(int slot);
