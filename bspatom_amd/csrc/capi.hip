@@ -60,6 +60,7 @@ const OptName OPT_TABLE[] = {
     {"route", "BSP_ROUTE", &Options::route},
     {"cw_onediv", "BSP_CW_ONEDIV", &Options::cw_onediv},
     {"cw_items4", "BSP_CW_ITEMS4", &Options::cw_items4},
+    {"cw_bcast", "BSP_CW_BCAST", &Options::cw_bcast},
     {"cw_nw", "BSP_CW_NW", &Options::cw_nw},
     {"cw_ldspad", "BSP_CW_LDSPAD", &Options::cw_ldspad},
     {"cw_ipw", "BSP_CW_IPW", &Options::cw_ipw},

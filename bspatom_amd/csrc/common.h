@@ -101,7 +101,9 @@ struct Options {
     int cw_ipw = 0;              // BSP_CW_IPW: items per wave of crawford_item4_kernel (0 = 4; 1, 2: experiment 9; bit-identical results)
     int cw_ldspad = 0;           // BSP_CW_LDSPAD: KB of unused dynamic LDS per workgroup of crawford_item4_kernel (timing experiment: occupancy)
     int cw_onediv = 0;           // BSP_CW_ONEDIV: reflectors of the band route's RQ loop in the one-division form (A/B switch)
-    int dipole_stage_mb = 0;     // BSP_DIPOLE_STAGE_MB: > 0 = device scratch of one group of pairs of bspatom_dipole_matrix in MB (0 = 2 GiB); small
+    int cw_bcast = 1;            // BSP_CW_BCAST: crawford_item4_kernel's reflector row 1 = as a DPP operand of the FMAs (row_newbcast; half the
+                                 // registers and LDS, four waves per SIMD), 0 = through LDS (the cross-check); bit-identical results
+    int dipole_stage_mb = 0;    // BSP_DIPOLE_STAGE_MB: > 0 = device scratch of one group of pairs of bspatom_dipole_matrix in MB (0 = 2 GiB); small
                                  // values force several groups (the results do not depend on the grouping: the test's hook)
     int wf_stage_mb = 0;         // BSP_WF_STAGE_MB: > 0 = device staging of bspatom_tabulate / bspatom_wavefunctions (U and dU of one group of vectors,
                                  // one group's eigenvector block) in MB (0 = 256 MiB); small values force several groups (the test's hook)

@@ -257,6 +257,8 @@ __global__ __launch_bounds__(256) void crawford_item_kernel(int N, int t, int jl
 // into the accumulator layout of the matrix cores (2 KB per item) and the congruences run exactly as above, one item at a time.
 // The arithmetic of an item is the first kernel's in another summation order (sums over 16 columns run 0 .. 15 inside a lane
 // instead of as a butterfly): spectra agree to rounding, not bit for bit; BSP_CW_ITEMS4=0 keeps the first kernel as the cross-check.
+// The default (BSP_CW_BCAST=1, rq4_step_dpp below) hands row I round as a DPP operand of the FMAs instead of through LDS: the same
+// bits at half the registers and half the LDS -- four waves per SIMD instead of two; BSP_CW_BCAST=0 keeps the LDS form.
 constexpr int QLD = 18;                                                  // LDS row stride of a stored Q (doubles): 144 B, 16-byte aligned
 
 template <int I, bool ONEDIV>
@@ -329,9 +331,137 @@ __device__ __forceinline__ void rq4_step(double (&x)[16], double (&q)[16], doubl
     }
 }
 
+// ---- the same step with the broadcast as an OPERAND (BSP_CW_BCAST=1).  DPP's row_newbcast:I hands lane I of a DPP row to the
+// row's 16 lanes and is the one DPP control that 64-bit instructions take: v_fmac_f64_dpp D, A, B computes D += bcast(A) * B, so
+// row I of X never leaves its lane's registers -- no LDS round trip on the chain of the eight steps, no broadcast copy u[16] in
+// every lane.  The compiler does not form these instructions (it splits a double into two 32-bit DPP moves): inline assembly,
+// and therefore the wait states are ours.  HAZARD RULE: a DPP instruction reads its DPP source no sooner than 2 wait states
+// after a VALU instruction wrote it (5 after a VALU write of EXEC).  The producers are compiler code in front of a statement, so
+// every statement opens with `s_nop 1`; inside a statement no instruction writes a register that a later one reads by DPP (the
+// DPP sources are u, sig and alpha, the destinations the sums and x / q).  tests/test_host_cw_codeobj.py walks the assembly.
+// Not volatile: outputs only, the scheduler stays free to interleave the steps.
+#define CW_PAD "s_nop 1\n\t"                                                  // the 2 wait states in front of a statement
+#define CW_DPPC " row_newbcast:%[I] row_mask:0xf bank_mask:0xf\n\t"
+#define CW_FD(a, k) "v_fmac_f64_dpp %[a" #a "], %[u" #k "], %[x" #k "]" CW_DPPC          // a += bcast(u_k) * x_k
+#define CW_FA(k) "v_fmac_f64_dpp %[x" #k "], %[u" #k "], %[tw]" CW_DPPC                  // x_k += bcast(u_k) * tw
+#define CW_FD1 CW_FD(0, 0)
+#define CW_FD2 CW_FD1 CW_FD(1, 1)
+#define CW_FD3 CW_FD2 CW_FD(2, 2)
+#define CW_FD4 CW_FD3 CW_FD(3, 3)
+#define CW_FD5 CW_FD4 CW_FD(0, 4)
+#define CW_FD6 CW_FD5 CW_FD(1, 5)
+#define CW_FD7 CW_FD6 CW_FD(2, 6)
+#define CW_FD8 CW_FD7 CW_FD(3, 7)
+#define CW_FA1 CW_FA(0)
+#define CW_FA2 CW_FA1 CW_FA(1)
+#define CW_FA3 CW_FA2 CW_FA(2)
+#define CW_FA4 CW_FA3 CW_FA(3)
+#define CW_FA5 CW_FA4 CW_FA(4)
+#define CW_FA6 CW_FA5 CW_FA(5)
+#define CW_FA7 CW_FA6 CW_FA(6)
+#define CW_FA8 CW_FA7 CW_FA(7)
+#define CW_UI(k) [u##k] "v"(u[O + k])
+#define CW_XI(k) [x##k] "v"(x[O + k])
+#define CW_XO(k) [x##k] "+v"(x[O + k])
+#define CW_L1(M) M(0)
+#define CW_L2(M) CW_L1(M), M(1)
+#define CW_L3(M) CW_L2(M), M(2)
+#define CW_L4(M) CW_L3(M), M(3)
+#define CW_L5(M) CW_L4(M), M(4)
+#define CW_L6(M) CW_L5(M), M(5)
+#define CW_L7(M) CW_L6(M), M(6)
+#define CW_L8(M) CW_L7(M), M(7)
+#define CW_DOT_CASE(n)                                                                                                               \
+    if constexpr (CNT == n)                                                                                                          \
+        asm(CW_PAD CW_FD##n : [a0] "+v"(ws[0]), [a1] "+v"(ws[1]), [a2] "+v"(ws[2]), [a3] "+v"(ws[3])                           \
+            : CW_L##n(CW_UI), CW_L##n(CW_XI), [I] "i"(I));
+#define CW_AXPY_CASE(n)                                                                                                              \
+    if constexpr (CNT == n) asm(CW_PAD CW_FA##n : CW_L##n(CW_XO) : CW_L##n(CW_UI), [tw] "v"(tw), [I] "i"(I));
+// the same with one plain FMA behind the broadcast ones: x[O + n] += nt * w
+#define CW_AXPYL_CASE(n)                                                                                                             \
+    if constexpr (CNT == n)                                                                                                          \
+        asm(CW_PAD CW_FA##n "v_fmac_f64 %[xl], %[nt], %[w]\n\t" : CW_L##n(CW_XO), [xl] "+v"(x[O + n])                                  \
+            : CW_L##n(CW_UI), [tw] "v"(tw), [nt] "v"(nt), [w] "v"(w), [I] "i"(I));
+
+// ws[c & 3] += bcast_I(u[O + c]) * x[O + c], c = 0 .. CNT - 1 in this order (O is a multiple of 4: the sums of rq4_step, term for term)
+template <int I, int O, int CNT>
+__device__ __forceinline__ void cw_bdot(double (&ws)[4], const double (&u)[16], const double (&x)[16])
+{
+    static_assert(CNT >= 1 && CNT <= 8 && (O & 3) == 0, "a statement of at most eight FMAs");
+    CW_DOT_CASE(1) CW_DOT_CASE(2) CW_DOT_CASE(3) CW_DOT_CASE(4) CW_DOT_CASE(5) CW_DOT_CASE(6) CW_DOT_CASE(7) CW_DOT_CASE(8)
+}
+// x[O + c] += bcast_I(u[O + c]) * tw, c = 0 .. CNT - 1
+template <int I, int O, int CNT>
+__device__ __forceinline__ void cw_baxpy(double (&x)[16], const double (&u)[16], const double tw)
+{
+    static_assert(CNT >= 1 && CNT <= 8, "a statement of at most eight FMAs");
+    CW_AXPY_CASE(1) CW_AXPY_CASE(2) CW_AXPY_CASE(3) CW_AXPY_CASE(4) CW_AXPY_CASE(5) CW_AXPY_CASE(6) CW_AXPY_CASE(7) CW_AXPY_CASE(8)
+}
+
+// x[O + c] += bcast_I(u[O + c]) * tw, c = 0 .. CNT - 1, and x[O + CNT] += nt * w, one rounding (no broadcast: the reflector's unit component)
+template <int I, int O, int CNT>
+__device__ __forceinline__ void cw_baxpy_last(double (&x)[16], const double (&u)[16], const double tw, const double nt, const double w)
+{
+    static_assert(CNT >= 1 && CNT <= 7, "a statement of at most eight FMAs");
+    CW_AXPYL_CASE(1) CW_AXPYL_CASE(2) CW_AXPYL_CASE(3) CW_AXPYL_CASE(4) CW_AXPYL_CASE(5) CW_AXPYL_CASE(6) CW_AXPYL_CASE(7)
+}
+
+// rq4_step, arithmetic and order unchanged (the same bits): every lane does to its own row what rq4_step does to the broadcast
+// copy of row I -- the partial sums of squares, the scaling by sc -- and only lane I's values are ever read, through DPP.
+template <int I, bool ONEDIV>
+__device__ __forceinline__ void rq4_step_dpp(double (&x)[16], double (&q)[16], const int r)
+{
+    constexpr int LEN = CB + I;
+    double sg[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < LEN; ++c) sg[c & 3] = fma(x[c], x[c], sg[c & 3]);
+    const double sigl = (sg[0] + sg[1]) + (sg[2] + sg[3]), alphal = x[LEN];
+    double sig, alpha;                                                   // lane I's, in the whole row
+    asm(CW_PAD
+        "v_mov_b64_dpp %[s], %[sl]" CW_DPPC "v_mov_b64_dpp %[a], %[al]" CW_DPPC
+        : [s] "=&v"(sig), [a] "=&v"(alpha) : [sl] "v"(sigl), [al] "v"(alphal), [I] "i"(I));
+    const double a2s = fma(alpha, alpha, sig);
+    const bool ok = (a2s > 1e-280) && (sig != 0.0);                    // nothing (numerically) left of the pivot: H = I
+    const double nrm = sqrt(ok ? a2s : 1.0);
+    const double bt = (alpha >= 0.0) ? -nrm : nrm;
+    const double amb = alpha - bt;
+    const double okf = ok ? 1.0 : 0.0, ambs = ok ? amb : 1.0, bts = ok ? bt : 1.0;   // masked divisions: see rq4_step
+    const double sc = ONEDIV ? 1.0 : (1.0 / ambs) * okf;
+    const double t = (ONEDIV ? -1.0 / (bts * ambs) : (bts - alpha) / bts) * okf;
+    double u[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) u[c] = (c < LEN) ? (ONEDIV ? x[c] : x[c] * sc) : (ONEDIV ? amb : 1.0);   // beyond LEN: not read
+    {   // rows up to and INCLUDING I, as in rq4_step
+        double ws[4] = {0.0, 0.0, 0.0, 0.0};
+        cw_bdot<I, 0, 8>(ws, u, x);
+        cw_bdot<I, 8, I + 1>(ws, u, x);
+        const double w = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+        const double tw = (r <= I) ? -t * w : 0.0;
+        cw_baxpy<I, 0, 8>(x, u, tw);
+        cw_baxpy<I, 8, I + 1>(x, u, tw);
+    }
+    {
+        double ws[4] = {0.0, 0.0, 0.0, 0.0};
+        cw_bdot<I, 0, 8>(ws, u, q);
+        cw_bdot<I, 8, I + 1>(ws, u, q);
+        const double w = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+        const double tw = -t * w;
+        cw_baxpy<I, 0, 8>(q, u, tw);
+        if constexpr (ONEDIV) {
+            cw_baxpy<I, 8, I + 1>(q, u, tw);
+        } else {
+            // u[LEN] = 1: rq4_step's fma(tw, 1.0, q[LEN]) is tw + q[LEN] to the compiler, which contracts the product inside tw
+            // into it -- ONE rounding, not two.  Written out here, so that the bits do not hang on that choice.
+            if constexpr (I > 0) cw_baxpy_last<I, 8, I>(q, u, tw, -t, w);
+            else q[LEN] = fma(-t, w, q[LEN]);
+        }
+    }
+}
+
 // The work of one wave on its (up to) four items of wavefront t of channel `chan`: items idx0 .. idx0 + ipw - 1 of the wavefront's
 // list (nch chase items j = jlo .., then the elimination jel if any).  Qsw / Bcw: the wave's LDS (4 x 16 x QLD and 4 x 16 doubles).
-template <bool ONEDIV>
+// BCAST: the reflector row by DPP (rq4_step_dpp), no Bcw, and Qsw IS Wsw: phase B's operands are in registers before Q is stored.
+template <bool ONEDIV, bool BCAST>
 __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo, int nch, int jel, const int ipw, const int nlh,
                                         const int qstride, const int nlead, const int chan, const int idx0, const int lane,
                                         double *Qsw, double *Bcw, double *Wsw, const double *__restrict__ Qel, double *Dall, double *Eall,
@@ -367,6 +497,25 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
         }
     }
 
+    // phase B's operands as they lie in Wsw (the lane's places in the layout of the matrix cores; they do not depend on the item)
+    double wv[4][4], sdv[4][2];
+    auto read_ws = [&]() {
+        const int g = lane >> 4, c8 = lane & 7;
+        const bool left = (lane & 15) < CB;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const double *W0 = Wsw + s * 4 * CBB, *W1 = W0 + CBB, *WE = W0 + 2 * CBB, *WM = W0 + 3 * CBB;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int R = 4 * r + g;
+                const int hi = R > c8 ? R : c8, lo = R > c8 ? c8 : R;
+                wv[s][r] = *(left ? W0 + hi * CB + lo : WE + c8 * CB + R);
+                wv[s][r + 2] = *(left ? WE + R * CB + c8 : W1 + hi * CB + lo);
+                sdv[s][r] = WM[(4 * r + g) * CB + c8];
+            }
+        }
+    };
+
     // ---- phase A: the RQ loops of the wave's chase items, an item per DPP row ----
     if (idx0 < nch) {
         const int it = lane >> 4, r = lane & 15;
@@ -385,30 +534,50 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
         }
 #pragma unroll
         for (int c = 0; c < 16; ++c) q[c] = (c == r) ? 1.0 : 0.0;
-        double *bc = Bcw + it * 16;
         if (diag) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tsa = __builtin_amdgcn_s_memtime(); }   // X has arrived
-        rq4_step<7, ONEDIV>(x, q, bc, r);
-        rq4_step<6, ONEDIV>(x, q, bc, r);
-        rq4_step<5, ONEDIV>(x, q, bc, r);
-        rq4_step<4, ONEDIV>(x, q, bc, r);
-        rq4_step<3, ONEDIV>(x, q, bc, r);
-        rq4_step<2, ONEDIV>(x, q, bc, r);
-        rq4_step<1, ONEDIV>(x, q, bc, r);
-        rq4_step<0, ONEDIV>(x, q, bc, r);
+        if constexpr (BCAST) {
+            rq4_step_dpp<7, ONEDIV>(x, q, r);
+            rq4_step_dpp<6, ONEDIV>(x, q, r);
+            rq4_step_dpp<5, ONEDIV>(x, q, r);
+            rq4_step_dpp<4, ONEDIV>(x, q, r);
+            rq4_step_dpp<3, ONEDIV>(x, q, r);
+            rq4_step_dpp<2, ONEDIV>(x, q, r);
+            rq4_step_dpp<1, ONEDIV>(x, q, r);
+            rq4_step_dpp<0, ONEDIV>(x, q, r);
+        } else {
+            double *bc = Bcw + it * 16;
+            rq4_step<7, ONEDIV>(x, q, bc, r);
+            rq4_step<6, ONEDIV>(x, q, bc, r);
+            rq4_step<5, ONEDIV>(x, q, bc, r);
+            rq4_step<4, ONEDIV>(x, q, bc, r);
+            rq4_step<3, ONEDIV>(x, q, bc, r);
+            rq4_step<2, ONEDIV>(x, q, bc, r);
+            rq4_step<1, ONEDIV>(x, q, bc, r);
+            rq4_step<0, ONEDIV>(x, q, bc, r);
+        }
         if (diag) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tsb = __builtin_amdgcn_s_memtime(); }   // the eight reflectors
         if (live) {                                                      // E_{p+1} <- R
             double *ep = E + (size_t)(p + 1) * CBB + r * CB;
 #pragma unroll
             for (int c = 0; c < CB; c += 2) *reinterpret_cast<double2 *>(ep + c) = make_double2(x[CB + c], x[CB + c + 1]);
         }
+        if constexpr (BCAST) {                                           // Q goes where phase B's operands lie: those to registers first
+            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");             // the DMA (the four stores of R are younger, see below)
+            read_ws();
+            asm volatile("" ::: "memory");
+        }
         double *qs = Qsw + it * (16 * QLD) + r * QLD;
 #pragma unroll
         for (int c = 0; c < 16; c += 2) *reinterpret_cast<double2 *>(qs + c) = make_double2(q[c], q[c + 1]);
+    } else if constexpr (BCAST) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        read_ws();
     }
     // this wave's own LDS stores (no other wave reads them) and the DMA of phase B's operands, requested a phase ago: the counter is
     // in order over loads and stores, and the only operations younger than the DMA are the four 16-byte stores of R that a wave with
     // a chase item has just issued (lanes 0 .. 7 of its first item are always live)
-    if (idx0 < nch) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    if constexpr (BCAST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the DMA was waited for before Q took its place)
+    else if (idx0 < nch) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     // Everything phase B computes from the kernel's arguments (item numbers, block addresses of four items) would otherwise be
     // hoisted in front of phase A and sit in registers across it (96 dwords spilled at three waves per SIMD): the two values it
@@ -425,7 +594,8 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     const int g = lane >> 4, c = lane & 15, c8 = c & 7;
     const bool left = c < CB;
     int kind[4], jj[4], pp[4];                                           // kind: 0 none, 1 chase, 2 elimination
-    double wv[4][4], sdv[4][2], qe[4], xt[2] = {0.0, 0.0};
+    double qe[4], xt[2] = {0.0, 0.0};
+    if constexpr (!BCAST) read_ws();
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         const int idx = idx0b + s;
@@ -433,17 +603,8 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
         jj[s] = kind[s] == 1 ? jlo + idx : (kind[s] == 2 ? jel : jlo + idx0b);
         pp[s] = kind[s] == 2 ? jel - 1 : jj[s] - 2 - (t - 2 * jj[s]);
         if (kind[s] == 0) { jj[s] = jj[0]; pp[s] = pp[0]; }
-        const int p = pp[s];
-        const double *W0 = Wsw + s * 4 * CBB, *W1 = W0 + CBB, *WE = W0 + 2 * CBB, *WM = W0 + 3 * CBB;
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int R = 4 * r + g;
-            const int hi = R > c8 ? R : c8, lo = R > c8 ? c8 : R;
-            wv[s][r] = *(left ? W0 + hi * CB + lo : WE + c8 * CB + R);
-            wv[s][r + 2] = *(left ? WE + R * CB + c8 : W1 + hi * CB + lo);
-            const double v = WM[(4 * r + g) * CB + c8];
-            sdv[s][r] = (p >= 1 && left) ? v : 0.0;
-        }
+        for (int r = 0; r < 2; ++r) sdv[s][r] = (pp[s] >= 1 && left) ? sdv[s][r] : 0.0;
     }
     // the elimination of this wavefront, if this wave holds it (at most one, the last item): its Q and E_j
     int se = -1;
@@ -532,8 +693,8 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     }
 }
 
-template <bool ONEDIV, int NW>
-__global__ __launch_bounds__(64 * NW, 8 / NW) void crawford_item4_kernel(int N, int t, int jlo, int nch, int jel, int ipw, int nlh, int qstride,
+template <bool ONEDIV, int NW, bool BCAST>
+__global__ __launch_bounds__(64 * NW, (BCAST ? 16 : 8) / NW) void crawford_item4_kernel(int N, int t, int jlo, int nch, int jel, int ipw, int nlh, int qstride,
                                                             int nlead, const double *__restrict__ Qel, double *Dall, double *Eall, double *Gall,
                                                             unsigned long long *diag)
 {
@@ -542,15 +703,20 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void crawford_item4_kernel(int N, 
     __builtin_amdgcn_s_setprio(3);
     // BSP_CW_DIAG: s_memtime stamps of a wave's phases, summed over the waves of every launch (diag[0..6] ticks, diag[7] waves)
     if (diag && (((blockIdx.x & 7) | (blockIdx.y & 7)) != 0)) diag = nullptr;   // one wave in 64 reports (the sums are atomics)
-    __shared__ __attribute__((aligned(16))) double Qs[NW][4][16 * QLD];  // per wave and item slot: Q, row-major, stride QLD
-    __shared__ __attribute__((aligned(16))) double Bc[NW][4][16];        // per wave and item slot: the row that goes round
-    __shared__ __attribute__((aligned(16))) double Ws[NW][4][4 * CBB];   // per wave and item slot: D_p, D_{p+1}, E_p, E_{p-1} (phase B's operands)
+    // per wave and item slot: Q, row-major, stride QLD; the row that goes round; D_p, D_{p+1}, E_p, E_{p-1} (phase B's operands).
+    // BCAST: no row goes round, and Q takes the place of phase B's operands once they are in registers: 9 KB per wave, not 17.5
+    __shared__ __attribute__((aligned(16))) double Qs[NW][4][16 * QLD];
+    __shared__ __attribute__((aligned(16))) double Bc[BCAST ? 1 : NW][BCAST ? 1 : 4][BCAST ? 2 : 16];
+    __shared__ __attribute__((aligned(16))) double Wsep[BCAST ? 1 : NW][BCAST ? 1 : 4][BCAST ? 2 : 4 * CBB];
+    static_assert(16 * QLD >= 4 * CBB, "a slot of Q holds a slot of phase B's operands");
+    double *Wsw = BCAST ? &Qs[0][0][0] : &Wsep[0][0][0];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // ipw = items per wave: 4; 2 or 1 only as an experiment (BSP_CW_IPW).  An item's arithmetic does not depend on the slot it
     // sits in: the choice changes no bit (tests/test_gpu_solve.py::test_band_route_properties).
-    cw_quad<ONEDIV>(N, t, jlo, nch, jel, ipw, nlh, qstride, nlead, (int)blockIdx.y, (blockIdx.x * NW + wave) * ipw, lane, &Qs[wave][0][0],
-                    &Bc[wave][0][0], &Ws[wave][0][0], Qel, Dall, Eall, Gall, diag);
+    cw_quad<ONEDIV, BCAST>(N, t, jlo, nch, jel, ipw, nlh, qstride, nlead, (int)blockIdx.y, (blockIdx.x * NW + wave) * ipw, lane,
+                           &Qs[wave][0][0], BCAST ? nullptr : &Bc[wave][0][0], Wsw + wave * (BCAST ? 4 * 16 * QLD : 4 * 4 * CBB), Qel, Dall,
+                           Eall, Gall, diag);
 }
 
 // index-reversed overlap band: SBf[d][i] = S_f(i, i + d) = S(n-1-i-d, n-1-i)
@@ -985,9 +1151,19 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
             const int ipw = (opts().cw_ipw == 1 || opts().cw_ipw == 2) ? opts().cw_ipw : 4;
             const int waves = (items + ipw - 1) / ipw;
             const dim3 grid((waves + nw - 1) / nw, cy), block(64 * nw);
-            if (opts().cw_onediv) hipLaunchKernelGGL((crawford_item4_kernel<true, 1>), dim3(waves, cy), dim3(64), 0, ws, Ns, t, jlo, nch, jel, ipw, nl, qstride, nlead, w.Qel, gD, gE, gG, dg);
-            else if (nw == 4) hipLaunchKernelGGL((crawford_item4_kernel<false, 4>), grid, block, 0, ws, Ns, t, jlo, nch, jel, ipw, nl, qstride, nlead, w.Qel, gD, gE, gG, dg);
-            else hipLaunchKernelGGL((crawford_item4_kernel<false, 1>), grid, block, (size_t)opts().cw_ldspad * 1024, ws, Ns, t, jlo, nch, jel, ipw, nl, qstride, nlead, w.Qel, gD, gE, gG, dg);
+            const size_t pad = (size_t)opts().cw_ldspad * 1024;
+#define CW_LAUNCH4(OD, NWV, BC, G, B, LDS)                                                                                           \
+    hipLaunchKernelGGL((crawford_item4_kernel<OD, NWV, BC>), G, B, LDS, ws, Ns, t, jlo, nch, jel, ipw, nl, qstride, nlead, w.Qel, gD, gE, gG, dg)
+            if (opts().cw_bcast) {
+                if (opts().cw_onediv) CW_LAUNCH4(true, 1, true, dim3(waves, cy), dim3(64), 0);
+                else if (nw == 4) CW_LAUNCH4(false, 4, true, grid, block, 0);
+                else CW_LAUNCH4(false, 1, true, grid, block, pad);
+            } else {
+                if (opts().cw_onediv) CW_LAUNCH4(true, 1, false, dim3(waves, cy), dim3(64), 0);
+                else if (nw == 4) CW_LAUNCH4(false, 4, false, grid, block, 0);
+                else CW_LAUNCH4(false, 1, false, grid, block, pad);
+            }
+#undef CW_LAUNCH4
         } else {
             const dim3 grid((items + 3) / 4, cy);
             if (opts().cw_onediv) hipLaunchKernelGGL(crawford_item_kernel<true>, grid, dim3(256), 0, ws, Ns, t, jlo, nch, jel, nl, qstride, nlead, w.Qel, gD, gE, gG);
