@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_tdse_adaptive", "bspatom_tdse_adaptive_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_resolvent", "bspatom_resolvent_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_tdse_adaptive", "bspatom_tdse_adaptive_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -74,6 +74,8 @@ def lib():
         L.bspatom_operator_bands_dev.argtypes = [vp, i32, vp, vp, vp]
         L.bspatom_operator_matrix.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.bspatom_operator_matrix_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+        L.bspatom_resolvent.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.bspatom_resolvent_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.bspatom_write_wf.argtypes = [vp, vp, i32, vp, vp]
         L.bspatom_quadrature.argtypes = [vp, C.POINTER(i32), vp, vp]
         L.bspatom_tabulate.argtypes = [vp, i32, vp, i32, vp, vp, vp]
@@ -316,6 +318,49 @@ class Problem:
         _chk(lib().bspatom_operator_matrix_dev(self._h, nop, C.c_void_p(g_ptr), _p(self._deriv(deriv, nop)), len(li), _p(li), _p(lf),
                                                n0_ini, count_ini, n0_fin, count_fin, _p(a), C.c_void_p(dev_ptr)),
              "bspatom_operator_matrix_dev")
+
+    @staticmethod
+    def _resolvent_matrices(l, z, w, nabs):
+        """(nmat, l as int32, z as complex128, w as int32 or None) with scalars broadcast to the longest of the three"""
+        l, z = np.atleast_1d(np.asarray(l, dtype=np.int32)), np.atleast_1d(np.asarray(z, dtype=np.complex128))
+        w = None if w is None else np.atleast_1d(np.asarray(w, dtype=np.int32))
+        nmat = max(l.size, z.size, 1 if w is None else w.size)
+        bc = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(a, (nmat,)) if a.size == 1 else a)
+        l, z, w = bc(l), bc(z), bc(w)
+        assert l.shape == z.shape == (nmat,) and (w is None or w.shape == (nmat,)), (l.shape, z.shape)
+        return nmat, l, z, w
+
+    def resolvent(self, l, z, B, W=None, w=None, P=None, want_x=True):
+        """Solves (H_l[m] - i W_w[m] - z[m] S) x = B[r] for every matrix m and right-hand side r in one call (bspatom_resolvent), and
+        the projections R[m, r, q] = sum_i P[q, i] x[m, r, i] (bilinear, no conjugate).  l, z, w: scalars or arrays of one length
+        (scalars broadcast); the channels are those of the last solve() or assemble().  B: (nrhs, nfun) or (nfun,), P: (nproj, nfun),
+        (nfun,) or None, complex or real.  W: full bands (nabs, 2k-1, nfun) or (2k-1, nfun) as operator_bands returns them, or None;
+        w[m] = -1 switches the absorber off for matrix m, w=None takes W[0] everywhere.  Returns (X, R, info): X (nmat, nrhs, nfun)
+        complex128 or None (want_x False), R (nmat, nrhs, nproj) complex128 or None (P None), info (nmat,) replaced pivots (0)."""
+        n = self.nfun
+        B = np.ascontiguousarray(np.asarray(B, dtype=np.complex128).reshape(-1, n))
+        P = None if P is None else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, n))
+        W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
+        nabs = 0 if W is None else W.shape[0]
+        nmat, l, z, w = self._resolvent_matrices(l, z, w, nabs)
+        nrhs, nproj = B.shape[0], 0 if P is None else P.shape[0]
+        X = np.zeros((nmat, nrhs, n), dtype=np.complex128) if want_x else None
+        R = np.zeros((nmat, nrhs, nproj), dtype=np.complex128) if P is not None else None
+        info = np.zeros(nmat, dtype=np.int32)
+        _chk(lib().bspatom_resolvent(self._h, nmat, _p(l), _p(z), nabs, _p(W), _p(w), nrhs, _p(B), nproj, _p(P), _p(X), _p(R),
+                                     _p(info)), "bspatom_resolvent")
+        return X, R, info
+
+    def resolvent_dev(self, l, z, nrhs, B_ptr, nabs=0, W_ptr=None, w=None, nproj=0, P_ptr=None, X_ptr=None, R_ptr=None):
+        """resolvent with B (nrhs * nfun complex), W (nabs * (2k-1) * nfun doubles), P (nproj * nfun complex), X (nmat * nrhs * nfun
+        complex) and R (nmat * nrhs * nproj complex) in device memory of this problem's device, e.g. torch tensors' data_ptr(); X and
+        R are written in place (either pointer may be None).  l, z, w are host values as in resolvent.  Returns info."""
+        nmat, l, z, w = self._resolvent_matrices(l, z, w, nabs)
+        info = np.zeros(nmat, dtype=np.int32)
+        vp = lambda a: None if a is None else C.c_void_p(a)
+        _chk(lib().bspatom_resolvent_dev(self._h, nmat, _p(l), _p(z), nabs, vp(W_ptr), _p(w), nrhs, vp(B_ptr), nproj, vp(P_ptr),
+                                         vp(X_ptr), vp(R_ptr), _p(info)), "bspatom_resolvent_dev")
+        return info
 
     def write_wf(self, c, npts=10000):
         c = np.ascontiguousarray(c, dtype=np.float64)

@@ -75,6 +75,8 @@ const OptName OPT_TABLE[] = {
     {"sbr_lag", "BSP_SBR_LAG", &Options::sbr_lag},
     {"fused_probe", "BSP_FUSED_PROBE", &Options::fused_probe},
     {"dipole_stage_mb", "BSP_DIPOLE_STAGE_MB", &Options::dipole_stage_mb},
+    {"resolvent_stage_mb", "BSP_RESOLVENT_STAGE_MB", &Options::resolvent_stage_mb},
+    {"resolvent_slots", "BSP_RESOLVENT_SLOTS", &Options::resolvent_slots},
     {"wf_stage_mb", "BSP_WF_STAGE_MB", &Options::wf_stage_mb},
     {"tdse_stage_mb", "BSP_TDSE_STAGE_MB", &Options::tdse_stage_mb},
     {"tdse_adapt_group", "BSP_TDSE_ADAPT_GROUP", &Options::tdse_adapt_group},
@@ -332,6 +334,7 @@ static int ensure_capacity(bspatom_problem *p, int nl)
     if (nl <= p->cap_nl) return BSP_OK;
     free_solve_buffers(p);
     p->last_nl = 0; p->pre_l = -1;                          // the spectra and bands of the last solve are gone
+    p->band_nl = 0;
     const HostSetup &h = p->hs;
     const size_t n = h.nfun, k = h.k, np = p->npad, b = nl;
     BSP_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_SB), k * n * sizeof(double)));
@@ -389,9 +392,11 @@ extern "C" int bspatom_assemble(bspatom_problem *p, int l0, int nl, double *SB, 
     int rc;
     if ((rc = ensure_capacity(p, nl))) return rc;
     p->last_nl = 0; p->pre_l = -1;                          // d_HB is overwritten: eigvec / eigvecs need a new solve
+    p->band_nl = 0;
     if ((rc = enqueue_assemble(p, l0, nl))) return rc;
     BSP_HIP(hipStreamSynchronize(p->st));
     if ((rc = check_status(p))) return rc;
+    p->band_l0 = l0; p->band_nl = nl;                       // the bands themselves are whole: bspatom_resolvent may use them
     const size_t kn = (size_t)p->hs.k * p->hs.nfun;
     if (SB) BSP_HIP(hipMemcpy(SB, p->d_SB, kn * sizeof(double), hipMemcpyDeviceToHost));
     if (HB) BSP_HIP(hipMemcpy(HB, p->d_HB, kn * nl * sizeof(double), hipMemcpyDeviceToHost));
@@ -476,7 +481,7 @@ static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, dou
     if ((rc = ensure_capacity(p, nl))) return rc;
     const int route = pipeline_route(n, h.k);
     if ((rc = ensure_route_buffers(p, nl, route))) return rc;
-    p->last_nl = 0;                                          // valid again only when this solve has completed
+    p->last_nl = 0; p->band_nl = 0;                          // valid again only when this solve has completed
     BSP_HIP(hipMemsetAsync(p->d_info, 0, sizeof(int), p->st));
     BSP_HIP(hipEventRecord(p->ev[0], p->st));
     // Band route: S is there once the first channel is assembled, and what the reduction does with S alone (the reversed band, its
@@ -621,6 +626,7 @@ static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, dou
         for (int l = 0; l < nl; ++l) info[l] = cinfo ? n + cinfo : 0;       // DSYGV: n+i, B not PD
     if (E_host) BSP_HIP(hipMemcpy(E_host, p->d_E, (size_t)nl * n * sizeof(double), hipMemcpyDeviceToHost));
     p->last_l0 = l0; p->last_nl = nl;
+    p->band_l0 = l0; p->band_nl = nl;
     return BSP_OK;
 }
 

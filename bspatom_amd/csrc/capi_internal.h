@@ -39,6 +39,7 @@ struct bspatom_problem {
     int pre_l = -1, pre_n0 = -1, pre_ch = 0;
     // last solve
     int last_l0 = 0, last_nl = 0;
+    int band_l0 = 0, band_nl = 0;             // channels whose bands d_HB holds (the last bspatom_solve or bspatom_assemble): bspatom_resolvent's
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double ms[6] = {0, 0, 0, 0, 0, 0};
 };

@@ -1,0 +1,82 @@
+// capi_resolvent.hip -- bspatom_resolvent / bspatom_resolvent_dev (include/bspatom.h): solves with the banded pencil at complex
+// energies, (H_l - i W - z S) x = b, by resolvent.hip's one-wave LU.  The bands are those the problem holds on the device (the
+// last bspatom_solve or bspatom_assemble); all work goes on the problem's stream and the scratch of a call is freed when it returns.
+#include <algorithm>
+#include "capi_internal.h"
+
+using namespace bsp;
+
+static constexpr size_t RESOLVENT_STAGE_BYTES = (size_t)2048 << 20;
+
+static int resolvent_impl(bspatom_problem *p, int nmat, const int32_t *l, const double *z, int nabs, const double *WB, const int32_t *w,
+                          int nrhs, const double *B, int nproj, const double *P, double *X, double *R, int32_t *info, bool dev)
+{
+    if (!p || !l || !z || !B || !info || (!X && !R)) return BSP_ERR_ARG;
+    if (nmat < 1 || nrhs < 1 || nabs < 0 || nproj < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
+    if (R && (!P || nproj < 1)) return BSP_ERR_ARG;
+    if (!WB) nabs = 0;
+    for (int m = 0; m < nmat; ++m) {
+        if (p->band_nl < 1 || l[m] < p->band_l0 || l[m] >= p->band_l0 + p->band_nl) return BSP_ERR_ARG;
+        if (w && (w[m] < -1 || w[m] >= nabs)) return BSP_ERR_ARG;
+    }
+    const HostSetup &h = p->hs;
+    const int n = h.nfun, k = h.k;
+    const size_t wband = (size_t)(2 * k - 1) * n, stage = opts().resolvent_stage_mb > 0 ? (size_t)opts().resolvent_stage_mb << 20 : RESOLVENT_STAGE_BYTES;
+    BSP_HIP(hipSetDevice(p->device));
+    int rc;
+    // the work slots: what is resident, within the scratch bound, one at least
+    int slots = 0;
+    if ((rc = resolvent_slots(k, nmat, &slots))) return rc;
+    if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, nmat);
+    const size_t slot_bytes = resolvent_slot_doubles(n, k) * sizeof(double);
+    slots = (int)std::max<size_t>(1, std::min<size_t>(slots, stage / slot_bytes));
+    // the host variant's groups: the X of one group within the bound, one matrix at least
+    const size_t x_mat = (size_t)2 * nrhs * n;                       // doubles of one matrix's X
+    int group = nmat;
+    if (!dev && X) group = (int)std::max<size_t>(1, std::min<size_t>(nmat, stage / (x_mat * sizeof(double))));
+    std::vector<int> chan(nmat), wsel(nmat, nabs > 0 && !w ? 0 : -1);
+    for (int m = 0; m < nmat; ++m) { chan[m] = l[m] - p->band_l0; if (w) wsel[m] = w[m]; }
+    DevArray<double> work, dz, dWB, dB, dP, dX, dR;
+    DevArray<int> dchan, dw, dinfo;
+    if ((rc = work.alloc((size_t)slots * resolvent_slot_doubles(n, k))) || (rc = dz.put(z, (size_t)2 * nmat)) ||
+        (rc = dchan.put(chan.data(), nmat)) || (rc = dw.put(wsel.data(), nmat)) || (rc = dinfo.alloc(nmat))) return rc;
+    const size_t r_all = (size_t)2 * nmat * nrhs * nproj;
+    if (!dev) {
+        if ((nabs > 0 && (rc = dWB.put(WB, (size_t)nabs * wband))) || (rc = dB.put(B, (size_t)2 * nrhs * n)) ||
+            (R && (rc = dP.put(P, (size_t)2 * nproj * n))) || (X && (rc = dX.alloc((size_t)group * x_mat))) || (R && (rc = dR.alloc(r_all))))
+            return rc;
+    }
+    ResolventArgs a;
+    a.n = n; a.k = k; a.nrhs = nrhs; a.nproj = R ? nproj : 0;
+    a.SB = p->d_SB; a.HB = p->d_HB;
+    a.WB = nabs > 0 ? (dev ? WB : dWB.p) : nullptr;
+    a.B = dev ? B : dB.p;
+    a.P = R ? (dev ? P : dP.p) : nullptr;
+    a.work = work.p;
+    rc = BSP_OK;
+    for (int m0 = 0; !rc && m0 < nmat; m0 += group) {
+        const int g = std::min(group, nmat - m0);
+        a.nmat = g;
+        a.chan = dchan.p + m0; a.z = dz.p + (size_t)2 * m0; a.w = dw.p + m0; a.info = dinfo.p + m0;
+        a.X = X ? (dev ? X + (size_t)m0 * x_mat : dX.p) : nullptr;
+        a.R = R ? (dev ? R : dR.p) + (size_t)2 * m0 * nrhs * nproj : nullptr;
+        rc = launch_resolvent(a, std::min(slots, g), p->st);
+        if (!rc && !dev && X) rc = HIP_RC(hipMemcpyAsync(X + (size_t)m0 * x_mat, dX.p, (size_t)g * x_mat * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc && !dev && R) rc = HIP_RC(hipMemcpyAsync(R, dR.p, r_all * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    if (!rc) rc = HIP_RC(hipMemcpyAsync(info, dinfo.p, (size_t)nmat * sizeof(int), hipMemcpyDeviceToHost, p->st));
+    return drain(p, rc);
+}
+
+extern "C" int bspatom_resolvent(bspatom_problem *p, int nmat, const int32_t *l, const double *z, int nabs, const double *WB,
+                                 const int32_t *w, int nrhs, const double *B, int nproj, const double *P, double *X, double *R,
+                                 int32_t *info)
+{
+    return resolvent_impl(p, nmat, l, z, nabs, WB, w, nrhs, B, nproj, P, X, R, info, false);
+}
+extern "C" int bspatom_resolvent_dev(bspatom_problem *p, int nmat, const int32_t *l, const double *z, int nabs, const double *WB_dev,
+                                     const int32_t *w, int nrhs, const double *B_dev, int nproj, const double *P_dev, double *X_dev,
+                                     double *R_dev, int32_t *info)
+{
+    return resolvent_impl(p, nmat, l, z, nabs, WB_dev, w, nrhs, B_dev, nproj, P_dev, X_dev, R_dev, info, true);
+}

@@ -111,6 +111,10 @@ struct Options {
                                  // group of steps) in MB (0 = 256 MiB); small values force several groups (the test's hook)
     int tdse_adapt_group = 0;    // BSP_TDSE_ADAPT_GROUP: > 0 = attempts that bspatom_tdse_adaptive enqueues between two looks at its control block (0 = 16); the
                                  // result does not depend on it (the test's hook)
+    int resolvent_stage_mb = 0;  // BSP_RESOLVENT_STAGE_MB: > 0 = bound in MB on the slot scratch of bspatom_resolvent and on the X of one group of matrices
+                                 // of its host variant (0 = 2048); one slot and one matrix at least; results do not depend on it (the test's hook)
+    int resolvent_slots = 0;     // BSP_RESOLVENT_SLOTS: > 0 = work slots (resident waves) of resolvent_kernel, 0 = the occupancy query x CUs;
+                                 // results do not depend on it (the test's hook)
     int ktime = 0;               // 1: HIP events around every launch of the kernels in KSlot (bspatom_kernel_times; bench.py's
                                  // per-kernel roofline entries are measured with it in one extra, untimed step)
 };
@@ -288,6 +292,24 @@ int launch_operator_bands(int nfun, int k, int ka, int nkp, int nop, int nr, con
 // ascending, rows over diagonals ascending, no FMA
 int launch_band_combine_apply(int n, int k, int nop, int count, int nitems, const double *d_GB, const double *d_acoef,
                               const long long *d_xoff, const double *d_base, double *d_W, hipStream_t st);
+// resolvent.hip: (H_l - i W_w - z S) x = b for nmat matrices (bspatom_resolvent).  Matrix m: channel chan[m] of HB (HB + chan*k*n),
+// z = (z[2m], z[2m+1]), absorber band WB + w[m]*(2k-1)*n (w null or w[m] < 0: none).  B: nrhs, P: nproj vectors of n complex;
+// X[m][r][n], R[m][r][nproj] complex (either may be null); info[m]: pivots replaced.  Every pointer is device memory.
+// work: slots * resolvent_slot_doubles (16-byte aligned), slots at most resolvent_slots.
+struct ResolventArgs {
+    int n, k, nmat, nrhs, nproj;
+    const double *SB, *HB;
+    const int *chan;
+    const double *z, *WB;
+    const int *w;
+    const double *B, *P;
+    double *X, *R;
+    int *info;
+    double *work;
+};
+size_t resolvent_slot_doubles(int n, int k);
+int resolvent_slots(int k, int nmat, int *slots);
+int launch_resolvent(const ResolventArgs &a, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

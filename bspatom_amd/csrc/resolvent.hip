@@ -1,0 +1,352 @@
+// resolvent.hip -- solves with the banded pencil at a complex energy: (H_l - i W - z S) x = b, and projections p^T x.
+//
+// The stationary layers answer at the box eigenvalues only; everything of second order (dynamic polarizabilities, two-photon
+// amplitudes, a Green's function between two packets) is otherwise a sum over every state of a channel.  The B-spline way is the
+// perturbed function itself: one banded LU per energy, O(n k^2), the whole basis taking part, and with an absorber W the energy may
+// lie anywhere in the continuum.  This is eigvec.hip::invit_body's factorisation -- one wavefront per matrix, the row window in
+// registers, multipliers and pivot row by readlane, the window moved by a one-lane DPP shift, the entering row fetched a block
+// ahead, no LDS and no barrier in the n dependent steps -- for the COMPLEX matrix
+//     Re M(i,j) = H_l(i,j) - Re z S(i,j),     Im M(i,j) = -Im z S(i,j) - W(i,j),     |i - j| <= b = k - 1,
+// with the caller's right-hand sides in place of the inverse iteration's own.
+//
+// Arithmetic, fixed: pivot by |Re| + |Im| (LAPACK's cabs1), ties to the smallest row; a complex product is the plain four-product
+// form (ac - bd, ad + bc); one reciprocal per pivot (scaled by cabs1, so that it neither overflows nor underflows), kept in U's
+// diagonal slot and multiplied with in the factorisation and in the back substitution.  With Im z = 0, no absorber and real
+// right-hand sides every imaginary part is a sum of products with a zero factor: +-0.0 throughout (G3 of include/bspatom.h).
+// A matrix is one item, its right-hand sides are solved one after the other: nothing of an x depends on the other matrices, on the
+// number of right-hand sides or projections, or on the slot that took the item (G2).
+#include "common.h"
+
+namespace bsp {
+namespace {
+constexpr int RS_BMAX = 15;                // half-bandwidth limit (k <= 16)
+constexpr int RS_PF = 8;                   // steps per prefetch block
+
+template <int CTRL>
+__device__ __forceinline__ double rs_dpp(double x)
+{
+    union { double d; int i[2]; } u, r;
+    u.d = x;
+    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
+    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
+    return r.d;
+}
+__device__ __forceinline__ double rs_readlane(double x, int l)
+{
+    union { double d; int i[2]; } u, r;
+    u.d = x;
+    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
+    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
+    return r.d;
+}
+// sum over lanes 0 .. 31 (the callers' terms are zero beyond lane 2 b <= 30), the same in every lane: a fixed tree
+__device__ __forceinline__ double rs_sum32(double x)
+{
+    x += rs_dpp<0x111>(x); x += rs_dpp<0x112>(x); x += rs_dpp<0x114>(x); x += rs_dpp<0x118>(x);   // row_shr 1, 2, 4, 8 (zeros shift in)
+    return rs_readlane(x, 15) + rs_readlane(x, 31);
+}
+__device__ __forceinline__ double rs_sum64(double x)
+{
+    x += rs_dpp<0x111>(x); x += rs_dpp<0x112>(x); x += rs_dpp<0x114>(x); x += rs_dpp<0x118>(x);
+    return (rs_readlane(x, 15) + rs_readlane(x, 31)) + (rs_readlane(x, 47) + rs_readlane(x, 63));
+}
+// doubles of one slot's scratch, even (a slot starts on a 16-byte boundary)
+__host__ __device__ inline size_t rs_slot_doubles(int n, int k)
+{
+    const size_t b = (size_t)k - 1, piv = ((size_t)n + 1) / 2;
+    return 2 * ((size_t)n * (2 * b + 1) + (size_t)n * b + (size_t)n) + piv + (piv & 1);
+}
+// a wave's own global stores are complete before the pass that reads them through other lanes (eigvec.hip: y_sync<true>)
+__device__ __forceinline__ void rs_sync() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// M(r, c); SB, HB upper bands [k][n] used symmetrically (eigvec.hip::pencil_entry), WB the absorber's FULL band [2k-1][n] with
+// WB[d + b][i] = W(i, i + d), both triangles as given, or null
+__device__ __forceinline__ void rs_entry(const double *__restrict__ SB, const double *__restrict__ HB, const double *__restrict__ WB,
+                                         int n, int b, double zr, double zi, int r, int c, double &re, double &im)
+{
+    const int d = (r > c) ? (r - c) : (c - r);
+    re = 0.0; im = 0.0;
+    if (d > b || r < 0 || c < 0 || r >= n || c >= n) return;
+    const int lo = (r > c) ? c : r;
+    const double s = SB[(size_t)d * n + lo];
+    re = HB[(size_t)d * n + lo] - zr * s;
+    im = -(zi * s);
+    if (WB) im -= WB[(size_t)(c - r + b) * n + r];
+}
+
+// The factorisation P M = L U of one matrix by one wavefront.  U: [n][2b+1] complex, row j = (1 / pivot, U(j, j+1 .. j+2b));
+// Lm: [n][b] complex multipliers; piv: [n] pivot rows.  Returns the number of pivots that were replaced by pertol.
+template <int BT>
+__device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict__ SB, const double *__restrict__ HB,
+                                         const double *__restrict__ WB, const double zr, const double zi, double2 *U, double2 *Lm,
+                                         int *piv, const int lane)
+{
+    constexpr int PF = RS_PF;
+    // scale of the zero-pivot perturbation, invit_body's with |M_jj| measured by cabs1
+    double dmax = 0.0, dflo = 0.0;
+    for (int j = lane; j < n; j += 64) {
+        const double s = SB[j], h = HB[j], wv = WB ? WB[(size_t)b * n + j] : 0.0;
+        dmax = fmax(dmax, fabs(h - zr * s) + fabs(-(zi * s) - wv));
+        dflo = fmax(dflo, (fabs(h) + fabs(zr * s)) + (fabs(zi * s) + fabs(wv)));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { dmax = fmax(dmax, __shfl_xor(dmax, off)); dflo = fmax(dflo, __shfl_xor(dflo, off)); }
+    const double pertol = 2.220446049250313e-16 * fmax(fmax(dmax, 2.220446049250313e-16 * dflo), 1e-280);
+
+    // lane c (0 .. 2 b) holds column j + c of the rows j .. j + b: a[t] = M(j + t, j + c)
+    double ar[BT + 1], ai[BT + 1];
+#pragma unroll
+    for (int t = 0; t <= BT; ++t) {
+        ar[t] = 0.0; ai[t] = 0.0;
+        if (t <= b && lane <= 2 * b) rs_entry(SB, HB, WB, n, b, zr, zi, t, lane, ar[t], ai[t]);
+    }
+    // the row that enters at step j (row j + b + 1), one entry per lane and step, requested a block of PF steps ahead
+    double per[PF], pei[PF], pnr[PF], pni[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        pnr[u] = 0.0; pni[u] = 0.0;
+        if (lane <= 2 * b) rs_entry(SB, HB, WB, n, b, zr, zi, u + b + 1, u + 1 + lane, pnr[u], pni[u]);
+    }
+    int nper = 0;
+    for (int j = 0; j < n; ++j) {
+        if ((j & (PF - 1)) == 0) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                per[u] = pnr[u]; pei[u] = pni[u];
+                pnr[u] = 0.0; pni[u] = 0.0;
+                if (lane <= 2 * b) rs_entry(SB, HB, WB, n, b, zr, zi, j + PF + u + b + 1, j + PF + u + 1 + lane, pnr[u], pni[u]);
+            }
+        }
+        const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;       // rows below the pivot row
+        // pivot search down lane 0's registers (column j); ties go to the smallest row
+        double mxv = fabs(ar[0]) + fabs(ai[0]);
+        int dpl = 0;
+#pragma unroll
+        for (int t = 1; t <= BT; ++t) {
+            const double v = (t <= nrow) ? fabs(ar[t]) + fabs(ai[t]) : -1.0;
+            if (v > mxv) { mxv = v; dpl = t; }
+        }
+        const int dp = __builtin_amdgcn_readfirstlane(dpl);
+        if (dp != 0) {                                               // uniform: rows j and j + dp change places, in every column
+#pragma unroll
+            for (int t = 1; t <= BT; ++t)
+                if (t == dp) {
+                    const double t1 = ar[0], t2 = ai[0];
+                    ar[0] = ar[t]; ai[0] = ai[t]; ar[t] = t1; ai[t] = t2;
+                }
+        }
+        double pr = rs_readlane(ar[0], 0), pi = rs_readlane(ai[0], 0);
+        if (fabs(pr) + fabs(pi) < pertol) { pr = (pr < 0.0) ? -pertol : pertol; pi = 0.0; ++nper; }
+        // 1 / pivot, once per column
+        const double sc = 1.0 / (fabs(pr) + fabs(pi));
+        const double qr = pr * sc, qi = pi * sc;
+        const double rd = 1.0 / (qr * qr + qi * qi);
+        const double rr = (qr * rd) * sc, ri = -((qi * rd) * sc);
+        double lmr = 0.0, lmi = 0.0;                                 // this lane's multiplier (row j + lane), for the store
+#pragma unroll
+        for (int t = 1; t <= BT; ++t) {
+            const double xr = rs_readlane(ar[t], 0), xi = rs_readlane(ai[t], 0);
+            const double ltr = (t <= nrow) ? xr * rr - xi * ri : 0.0;
+            const double lti = (t <= nrow) ? xr * ri + xi * rr : 0.0;
+            lmr = (lane == t) ? ltr : lmr;
+            lmi = (lane == t) ? lti : lmi;
+            const double ur = ltr * ar[0] - lti * ai[0], ui = ltr * ai[0] + lti * ar[0];
+            ar[t] = (lane >= 1) ? ar[t] - ur : 0.0;                  // columns j + 1 .. j + 2 b; column j is eliminated
+            ai[t] = (lane >= 1) ? ai[t] - ui : 0.0;
+        }
+        if (lane == 0) piv[j] = j + dp;
+        if (lane <= 2 * b) U[(size_t)j * (2 * b + 1) + lane] = (lane == 0) ? make_double2(rr, ri) : make_double2(ar[0], ai[0]);
+        if (lane >= 1 && lane <= b) Lm[(size_t)j * b + lane - 1] = make_double2(lmr, lmi);
+        // slide the window: row j leaves, row j + b + 1 enters; column j leaves, column j + 2 b + 1 enters (zero above the entering row)
+        double pinr = per[0], pini = pei[0];
+#pragma unroll
+        for (int u = 1; u < PF; ++u) {
+            pinr = ((j & (PF - 1)) == u) ? per[u] : pinr;
+            pini = ((j & (PF - 1)) == u) ? pei[u] : pini;
+        }
+#pragma unroll
+        for (int t = 0; t < BT; ++t) { ar[t] = rs_dpp<0x130>(ar[t + 1]); ai[t] = rs_dpp<0x130>(ai[t + 1]); }   // wave_shl:1
+        ar[BT] = 0.0; ai[BT] = 0.0;
+#pragma unroll
+        for (int t = 0; t <= BT; ++t)
+            if (t == b) { ar[t] = pinr; ai[t] = pini; }              // uniform
+    }
+    return nper;
+}
+
+// y <- U^-1 L^-1 P y in place (y: n complex in global memory, the slot's): invit_body's two passes, the b + 1 (forward) and 2 b
+// (backward) entries a step can touch in a register window, what enters it requested a block ahead.  The caller has made y visible
+// (rs_sync); on return the solution is visible to every lane.
+__device__ __forceinline__ void rs_solve(int n, int b, const double2 *U, const double2 *Lm, const int *piv, double2 *y, const int lane)
+{
+    constexpr int PF = RS_PF;
+    // forward: y <- L^-1 P y; lane i holds y[j + i]
+    {
+        double wr = 0.0, wi = 0.0;
+        if (lane <= b && lane < n) { const double2 v = y[lane]; wr = v.x; wi = v.y; }
+        double2 lvn[PF]; int pvn[PF];
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            lvn[u] = (u < n && lane >= 1 && lane <= b) ? Lm[(size_t)u * b + lane - 1] : make_double2(0.0, 0.0);
+            pvn[u] = (u < n) ? piv[u] : 0;
+        }
+        // the entering entries: one per lane (lane u: step u's), a block ahead; above every index this pass has written
+        double2 yln = (lane < PF && lane + b + 1 < n) ? y[lane + b + 1] : make_double2(0.0, 0.0);
+        for (int j0 = 0; j0 < n; j0 += PF) {
+            double2 lv[PF]; int pvv[PF];
+            const double2 yl = yln;
+            yln = (lane < PF && j0 + PF + lane + b + 1 < n) ? y[j0 + PF + lane + b + 1] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int jn = j0 + u + PF;
+                lv[u] = lvn[u]; pvv[u] = pvn[u];
+                lvn[u] = (jn < n && lane >= 1 && lane <= b) ? Lm[(size_t)jn * b + lane - 1] : make_double2(0.0, 0.0);
+                pvn[u] = (jn < n) ? piv[jn] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int j = j0 + u;
+                if (j < n) {
+                    const int p = __builtin_amdgcn_readfirstlane(pvv[u]);
+                    if (p != j) {                                    // uniform: rows j and p change places (p - j <= b: inside the window)
+                        const double t0r = rs_readlane(wr, 0), t0i = rs_readlane(wi, 0);
+                        const double tqr = rs_readlane(wr, p - j), tqi = rs_readlane(wi, p - j);
+                        wr = lane == 0 ? tqr : (lane == p - j ? t0r : wr);
+                        wi = lane == 0 ? tqi : (lane == p - j ? t0i : wi);
+                    }
+                    const double yr = rs_readlane(wr, 0), yi = rs_readlane(wi, 0);
+                    const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;
+                    if (lane >= 1 && lane <= nrow) {
+                        wr -= lv[u].x * yr - lv[u].y * yi;
+                        wi -= lv[u].x * yi + lv[u].y * yr;
+                    }
+                    if (lane == 0) y[j] = make_double2(yr, yi);
+                    wr = rs_dpp<0x130>(wr); wi = rs_dpp<0x130>(wi);  // wave_shl:1 -- lane i takes lane i + 1
+                    const double er = rs_readlane(yl.x, u), ei = rs_readlane(yl.y, u);
+                    if (lane == b) { wr = er; wi = ei; }
+                }
+            }
+        }
+        rs_sync();
+    }
+    // backward: x_j = (y_j - sum_{c=1..2b} U[j][c] x_{j+c}) / pivot_j; lane c holds x[j + c] (zero beyond the matrix)
+    {
+        const int w = 2 * b + 1;
+        double wr = 0.0, wi = 0.0;
+        double2 uvn[PF], udn[PF];
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int j = n - 1 - u;
+            uvn[u] = (j >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)j * w + lane] : make_double2(0.0, 0.0);
+            udn[u] = (j >= 0) ? U[(size_t)j * w] : make_double2(0.0, 0.0);
+        }
+        double2 ybn = (lane < PF && n - 1 - lane >= 0) ? y[n - 1 - lane] : make_double2(0.0, 0.0);
+        for (int j0 = n - 1; j0 >= 0; j0 -= PF) {
+            double2 uv[PF], ru[PF];
+            const double2 yb = ybn;
+            ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int jn = j0 - u - PF;
+                uv[u] = uvn[u]; ru[u] = udn[u];
+                uvn[u] = (jn >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)jn * w + lane] : make_double2(0.0, 0.0);
+                udn[u] = (jn >= 0) ? U[(size_t)jn * w] : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int j = j0 - u;
+                if (j >= 0) {
+                    double sr = 0.0, si = 0.0;
+                    if (lane >= 1 && lane <= 2 * b && j + lane < n) {
+                        sr = uv[u].x * wr - uv[u].y * wi;
+                        si = uv[u].x * wi + uv[u].y * wr;
+                    }
+                    sr = rs_sum32(sr); si = rs_sum32(si);
+                    const double dr = rs_readlane(yb.x, u) - sr, di = rs_readlane(yb.y, u) - si;
+                    const double xr = dr * ru[u].x - di * ru[u].y, xi = dr * ru[u].y + di * ru[u].x;
+                    if (lane == 0) y[j] = make_double2(xr, xi);
+                    wr = rs_dpp<0x138>(wr); wi = rs_dpp<0x138>(wi);  // wave_shr:1 -- lane i takes lane i - 1
+                    if (lane == 1) { wr = xr; wi = xi; }
+                }
+            }
+        }
+        rs_sync();
+    }
+}
+}  // namespace
+
+// A PERSISTENT grid of single-wave workgroups, one per work slot, takes the matrices by a static stride (invit_batch_kernel's
+// scheduling: bounded work per item, nobody waits for anybody -- a wrong residency estimate costs speed, never progress).
+// Slot scratch: U [n][2b+1], L [n][b], y [n] complex, then piv [n] ints (resolvent_slot_doubles).
+template <int BT>
+__global__ __launch_bounds__(64) void resolvent_kernel(const ResolventArgs a)
+{
+    const int b = a.k - 1;
+    double *work = a.work + (size_t)blockIdx.x * rs_slot_doubles(a.n, a.k);
+    for (int it = blockIdx.x; it < a.nmat; it += gridDim.x) {
+        // the operands made new values in every item, so that nothing hoisted out of the bodies stays live across the items
+        // (eigvec.hip::invit_batch_kernel; the asm emits no instruction)
+        int n = a.n, lane = threadIdx.x;
+        const double *sb = a.SB, *hb = a.HB, *wb = a.WB;
+        double *wk = work;
+        asm volatile("" : "+s"(n), "+s"(sb), "+s"(hb), "+s"(wb), "+s"(wk), "+v"(lane));
+        double2 *U = reinterpret_cast<double2 *>(wk), *Lm = U + (size_t)n * (2 * b + 1), *y = Lm + (size_t)n * b;
+        int *piv = reinterpret_cast<int *>(y + n);
+        const int wsel = a.w ? a.w[it] : -1;
+        const double *wband = (wb && wsel >= 0) ? wb + (size_t)wsel * (2 * b + 1) * n : nullptr;
+        const int nper = rs_factor<BT>(n, b, sb, hb + (size_t)a.chan[it] * a.k * n, wband, a.z[2 * it], a.z[2 * it + 1], U, Lm, piv, lane);
+        if (lane == 0) a.info[it] = nper;
+        for (int r = 0; r < a.nrhs; ++r) {
+            // (the caller's arrays are read and written as doubles: the ABI promises no more than their alignment)
+            const double *B = a.B + (size_t)2 * r * n;
+            for (int j = lane; j < n; j += 64) y[j] = make_double2(B[2 * j], B[2 * j + 1]);
+            rs_sync();                                               // y, and with the first right-hand side U, L, piv, are in memory
+            rs_solve(n, b, U, Lm, piv, y, lane);
+            const size_t mr = (size_t)it * a.nrhs + r;
+            if (a.X) {
+                double *X = a.X + 2 * mr * n;
+                for (int j = lane; j < n; j += 64) { const double2 v = y[j]; X[2 * j] = v.x; X[2 * j + 1] = v.y; }
+            }
+            if (a.R)
+                for (int q = 0; q < a.nproj; ++q) {
+                    // bilinear, no conjugate: lane-strided partial sums, then the wave's fixed tree
+                    const double *P = a.P + (size_t)2 * q * n;
+                    double sr = 0.0, si = 0.0;
+                    for (int j = lane; j < n; j += 64) {
+                        const double2 pv = make_double2(P[2 * j], P[2 * j + 1]), xv = y[j];
+                        sr += pv.x * xv.x - pv.y * xv.y;
+                        si += pv.x * xv.y + pv.y * xv.x;
+                    }
+                    sr = rs_sum64(sr); si = rs_sum64(si);
+                    if (lane == 0) { a.R[2 * (mr * a.nproj + q)] = sr; a.R[2 * (mr * a.nproj + q) + 1] = si; }
+                }
+            rs_sync();                                               // every load of y is back before the next right-hand side overwrites it
+        }
+    }
+}
+
+size_t resolvent_slot_doubles(int n, int k) { return rs_slot_doubles(n, k); }
+
+int resolvent_slots(int k, int nmat, int *slots)
+{
+    if (k - 1 > RS_BMAX || k < 2 || nmat < 1) return BSP_ERR_ARG;
+    int dev = 0, cus = 0, per_cu = 0;
+    BSP_HIP(hipGetDevice(&dev));
+    BSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (k - 1 <= 8) BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_kernel<8>, 64, 0));
+    else BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_kernel<RS_BMAX>, 64, 0));
+    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+    *slots = (int)(r < nmat ? r : nmat);
+    return BSP_OK;
+}
+
+int launch_resolvent(const ResolventArgs &a, int slots, hipStream_t st)
+{
+    if (a.k - 1 > RS_BMAX || a.k < 2 || a.n < 1 || a.nmat < 1 || a.nrhs < 1 || slots < 1) return BSP_ERR_ARG;
+    if (a.k - 1 <= 8) hipLaunchKernelGGL(resolvent_kernel<8>, dim3(slots), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(resolvent_kernel<RS_BMAX>, dim3(slots), dim3(64), 0, st, a);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+}  // namespace bsp

@@ -790,6 +790,77 @@ def operator_matrix(prob, pairs, ops, n0_ini, count_ini, n0_fin, count_fin, a=No
     return prob.operator_matrix(pairs, G, deriv, n0_ini, count_ini, n0_fin, count_fin, a)
 
 
+# ---- response at any complex energy: solves with the banded pencil (Problem.resolvent) -------------------------------------
+C_RESPONSE = 137.035999          # the speed of light in atomic units, photoabsorption's
+
+
+def band_apply(A, X):
+    """Y[j] = A x_j for the rows x_j of X (m, n); A (2k-1, n) a full band, A[d + k - 1][i] = A(i, i + d) (the layout of
+    Problem.dipole_bands / operator_bands).  X real or complex."""
+    import numpy as np
+    A, X = np.asarray(A), np.asarray(X)
+    k, n = (A.shape[0] + 1) // 2, A.shape[1]
+    Y = np.zeros_like(X)
+    for d in range(-(k - 1), k):
+        lo, hi = max(0, -d), min(n, n - d)                     # rows i with 0 <= i + d < n
+        Y[:, lo:hi] += A[d + k - 1, lo:hi] * X[:, lo + d:hi + d]
+    return Y
+
+
+def _absorber_band(prob, absorber):
+    """the full band (2k-1, nfun) of W(r) for an absorber given as a callable of the points or an array on the quadrature grid
+    (cap_profile), or None"""
+    import numpy as np
+    if absorber is None:
+        return None
+    r = prob.quadrature()[0]
+    g = np.asarray(absorber(r) if callable(absorber) else absorber, dtype=np.float64)
+    if g.shape != r.shape:
+        raise ValueError("absorber must give one value per quadrature point (%d), got shape %s" % (r.size, g.shape))
+    return prob.operator_bands(g, [0])[0]
+
+
+def response(prob, l_ini, n_ini, l_fin, a, z, absorber=None, a_left=None):
+    """R(z) = (A' c_i)^T (H_{l_fin} - i W - z S)^-1 A c_i for every z of an array (or one z): the second-order response of state
+    n_ini (1-based) of channel l_ini through the intermediate channel l_fin, at ANY complex energy -- the sum over every state of
+    l_fin without forming one of them (Problem.resolvent: one banded LU per energy).  A = a[0] R_r + a[1] R_{1/r} + a[2] R_{d/dr}
+    from dipole_bands, A' likewise from a_left (None: A' = A); c_i from eigvecs; W the band of `absorber` (a callable of the
+    points or an array on prob.quadrature()'s grid, e.g. cap_profile; None: no absorber, z must then keep off the box
+    eigenvalues).  Both channels must be in the last solve.  Returns complex128 of z's shape."""
+    import numpy as np
+    RB = prob.dipole_bands()
+    ci = prob.eigvecs(l_ini, n_ini, 1)
+    comb = lambda co: sum(float(co[o]) * RB[o] for o in range(3))
+    b = band_apply(comb(a), ci)
+    p = b if a_left is None else band_apply(comb(a_left), ci)
+    zz = np.asarray(z, dtype=np.complex128)
+    W = _absorber_band(prob, absorber)
+    _, R, info = prob.resolvent(l_fin, zz.reshape(-1), b, W=W, P=p, want_x=False)
+    if np.any(info != 0):
+        raise ArithmeticError("response: z on an eigenvalue of channel %d (%d pivots replaced)" % (l_fin, int(info.max())))
+    return R[:, 0, 0].reshape(zz.shape)
+
+
+def polarizability(prob, n_ini, omega, absorber=None):
+    """The dynamic dipole polarizability of the s state n_ini (1-based; channels 0 and 1 in the last solve, made by prob.solve):
+    alpha(omega) = [R(E_i + omega) + R(E_i - omega)] / 3 with A = r and l_fin = 1; (2/3) R(E_i) at omega = 0.  Real omega without an
+    absorber (below the first excitation: real alpha), or any omega with one.  Returns complex128 of omega's shape."""
+    import numpy as np
+    om = np.asarray(omega, dtype=np.float64)
+    Ei = float(prob.last_E[0 - prob.last_l0, n_ini - 1])
+    z = np.stack([Ei + om, Ei - om]).astype(np.complex128)
+    R = response(prob, 0, n_ini, 1, (1.0, 0.0, 0.0), z, absorber=absorber)
+    return (R[0] + R[1]) / 3.0
+
+
+def photoabsorption(prob, n_ini, omega, absorber):
+    """sigma(omega) = 4 pi omega Im alpha(omega) / c in atomic units (c = 137.035999): with an absorber a smooth function of omega
+    across the continuum, no box normalisation, no interpolation over the box states."""
+    import numpy as np
+    om = np.asarray(omega, dtype=np.float64)
+    return 4.0 * np.pi * om * polarizability(prob, n_ini, om, absorber).imag / C_RESPONSE
+
+
 # ---- KIND_PI = 0 on several GPUs: one process per GPU, channels sharded, spectra gathered (SURVEY 8e) ---------------
 def write_structure_outputs(nfun, lmax, E, l_ini, wf, outdir):
     """Enl.dat, wf_n0.dat and the stdout text of a KIND_PI = 0 run from the spectra E[l][i] and the tabulated initial

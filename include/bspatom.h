@@ -186,6 +186,38 @@ int bspatom_operator_matrix_dev(bspatom_problem *p, int nop, const double *g_dev
                                 const int32_t *l_ini, const int32_t *l_fin, int n0_ini, int count_ini, int n0_fin, int count_fin,
                                 const double *a, double *D_dev);
 
+/* ---- resolvent solves on the banded pencil (csrc/resolvent.hip) ------------------------------------------------------------ */
+/* The response at ANY complex energy, where the layers above answer at the box eigenvalues only: for m < nmat the banded system
+ *   M_m x = b,   M_m = H_{l[m]} - i W_{w[m]} - z_m S,   z_m = z[2m] + i z[2m+1],
+ * is solved for each of nrhs right-hand sides shared by all matrices, and projected on nproj left vectors:
+ *   X[((size_t)m*nrhs + r)*nfun + i] = x_{m,r}(i),      R[((size_t)m*nrhs + r)*nproj + q] = sum_i P_q(i) x_{m,r}(i)
+ * (bilinear: NO complex conjugate).  Complex means interleaved (Re, Im) doubles: z has 2*nmat doubles, B nrhs*nfun complex, P
+ * nproj*nfun complex, X nmat*nrhs*nfun complex, R nmat*nrhs*nproj complex.  H_l and S are the bands the problem holds on the device,
+ * so l[m] must be a channel of the last bspatom_solve or bspatom_assemble, whichever came last.  W: nabs caller-given FULL bands in
+ * bspatom_operator_bands' layout, WB[(a*(2k-1) + (d+k-1))*nfun + i] = W_a(i, i+d), both triangles used as given (e.g. the band of
+ * host.cap_profile: a complex absorbing potential); w[m] = -1: no absorber for matrix m; w == NULL: absorber 0 for every matrix
+ * if WB is given, none otherwise.  With an absorber z may lie anywhere in the continuum and p^T x is a smooth function of z: the sum
+ * over every state of a channel (dynamic polarizabilities, two-photon amplitudes, Green's functions) in O(nfun k^2) per energy.
+ * One wavefront factors one matrix: banded LU with partial pivoting by |Re| + |Im| (ties to the smallest row), complex products in
+ * the plain four-product form, one reciprocal per pivot; info[m] = number of pivots below eps * max_j |M_jj| that were replaced by
+ * that bound on the real axis: 0 unless a real z sits on an eigenvalue with no absorber (the x is then huge, not wrong).
+ * At least one of X and R must be non-NULL; P may be NULL when R is.  Guarantees:
+ *   (G1) results are bit-identical from run to run;
+ *   (G2) x_{m,r} and R[m][r][q] depend on (l[m], z_m, W_{w[m]}, B_r, P_q) alone -- not on the other matrices, on nmat, nrhs or nproj, on
+ *        the number of work slots, on the grouping below, or on the host versus _dev variant;
+ *   (G3) with Im z = 0, no absorber and real B every imaginary part of X is +-0.0 exactly.
+ * The host variant processes the matrices in groups, in the order given, the X of one group staged through a device buffer of at
+ * most 2 GiB (one matrix at least); the kernel's scratch, nfun*(6k-1) doubles per resident wave, stays within the same bound (one
+ * wave at least); bspatom_set_option("resolvent_stage_mb", m) sets another bound, ("resolvent_slots", s) another number of waves.
+ * The scratch of a call is freed when it returns.  BSPATOM_ERR_ARG: a null p, l, z, B or info, X and R both NULL, R given with P NULL
+ * or nproj < 1, nmat < 1, nrhs < 1, nabs < 0, nabs > 0 with WB NULL, a channel outside the bands held, w[m] outside -1 .. nabs-1.
+ * The _dev variant: WB, B, P, X, R in device memory of the problem's device, written in place; l, z, w, info stay host pointers. */
+int bspatom_resolvent(bspatom_problem *p, int nmat, const int32_t *l, const double *z, int nabs, const double *WB, const int32_t *w,
+                      int nrhs, const double *B, int nproj, const double *P, double *X, double *R, int32_t *info);
+int bspatom_resolvent_dev(bspatom_problem *p, int nmat, const int32_t *l, const double *z, int nabs, const double *WB_dev,
+                          const int32_t *w, int nrhs, const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev,
+                          int32_t *info);
+
 /* WRITE_WF (Bsp_Atom.f90:118-146): u(r_i) = sum_j c_j B_j(r_i), r_i = ra + i*(rb-ra)/npts,
  * i = 0..npts.  Returns BSPATOM_ERR_BSPLVB where the reference STOPs. r[npts+1], u[npts+1]. */
 int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u);
