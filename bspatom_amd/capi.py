@@ -82,18 +82,14 @@ def lib():
         L.bspatom_tabulate_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
         L.bspatom_wavefunctions.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.bspatom_wavefunctions_dev.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
-        L.bspatom_tdse_propagate.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp]
-        L.bspatom_tdse_propagate_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp]
-        L.bspatom_tdse_observe.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
-        L.bspatom_tdse_observe_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
-        L.bspatom_tdse_lawson.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
-        L.bspatom_tdse_lawson_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp]
-        L.bspatom_tdse_static.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
-        L.bspatom_tdse_static_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
-        L.bspatom_tdse_fields.argtypes = L.bspatom_tdse_static.argtypes + [i32, vp]
-        L.bspatom_tdse_fields_dev.argtypes = L.bspatom_tdse_static_dev.argtypes + [i32, vp]
-        L.bspatom_tdse_adaptive.argtypes = L.bspatom_tdse_static.argtypes + [i32, dbl, i32, i32, vp, i32, vp, vp, vp]
-        L.bspatom_tdse_adaptive_dev.argtypes = L.bspatom_tdse_static_dev.argtypes + [i32, dbl, i32, i32, vp, i32, vp, vp, vp]
+        # the TDSE calls: propagate's 16 arguments, + obs_every, obs, + scheme and the static lists, + what fields and adaptive add
+        t16 = [vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, dbl, vp, vp, i32, vp, vp]
+        t18 = t16 + [i32, vp]
+        t24 = t18 + [i32, i32, vp, vp, vp, vp]
+        for name, types in (("propagate", t16), ("observe", t18), ("lawson", t18), ("static", t24), ("fields", t24 + [i32, vp]),
+                            ("adaptive", t24 + [i32, dbl, i32, i32, vp, i32, vp, vp, vp])):
+            getattr(L, "bspatom_tdse_" + name).argtypes = list(types)
+            getattr(L, "bspatom_tdse_" + name + "_dev").argtypes = list(types)
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -118,6 +114,13 @@ def lib():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _ptr(x):
+    """a pointer argument from a host array, a device address (0: NULL) or None"""
+    if x is None or isinstance(x, np.ndarray):
+        return _p(x)
+    return C.c_void_p(x) if x else None
 
 
 def _chk(rc, where):
@@ -426,31 +429,59 @@ class Problem:
         pr = np.asarray(list(pairs), dtype=np.int32).reshape(-1, 2)
         return np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
 
+    # What the twelve tdse_* methods share.  A host method: _tdse_host, its own check of the field, _tdse_out, the call on
+    # _tdse_common (+ _tdse_static_args), _tdse_result; a _dev method: the call on the same lists with addresses in the arrays' places.
+    @staticmethod
+    def _tdse_host(E, pairs, D, a0):
+        """(E, ci, cf, D, a, one, nscan): contiguous E (nch, count), D (npairs, count, count) and a fresh a (nscan, nch, count);
+        one: a0 was a single wave packet (nch, count)"""
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        nch, count = E.shape
+        ci, cf = Problem._tdse_pairs(pairs)
+        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
+        a = np.array(a0, dtype=np.complex128, order="C")
+        one = a.ndim == 2
+        a = np.ascontiguousarray(a.reshape(-1, nch, count))
+        return E, ci, cf, D, a, one, a.shape[0]
+
+    @staticmethod
+    def _tdse_out(a, nsteps, snap_every, obs_every=0, ow=4):
+        """(err, snaps, obs) for a (nscan, nch, count): snaps None without snap_every, obs (rows of ow) None without obs_every"""
+        nscan, nch, count = a.shape
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((Problem.tdse_nobs(nsteps, obs_every), nscan, nch, ow)) if obs_every > 0 else None
+        return np.zeros(nscan), snaps, obs
+
+    def _tdse_common(self, nch, count, E, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snap, err):
+        """the 16 arguments every bspatom_tdse_* call begins with; E, D, field, a, snap: host arrays, device addresses or None"""
+        D, ci_, cf_ = (D, ci, cf) if len(ci) else (None, None, None)
+        return [self._h, nch, count, _ptr(E), len(ci), _p(ci_), _p(cf_), _ptr(D), nscan, nsteps, float(dt), _ptr(field), _ptr(a),
+                snap_every, _ptr(snap), _p(err)]
+
+    @staticmethod
+    def _tdse_static_args(scheme, si, sf, skind, W):
+        """scheme and the static lists as bspatom_tdse_static takes them; W: a host array or a device address"""
+        ns = len(si)
+        return [int(scheme), ns] + ([_p(si), _p(sf), _p(skind), _ptr(W)] if ns else [None] * 4)
+
+    @staticmethod
+    def _tdse_result(a, one, err, obs=None, snaps=None):
+        return (a[0] if one else a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+
     def tdse_propagate(self, E, pairs, D, a0, field, dt, snap_every=0):
         """nsteps fixed Runge-Kutta steps dt of i da/dt = (E + f(t) D) a in the eigenstate basis (bspatom_tdse_propagate) for nscan
         wave packets at once.  E: (nch, count); pairs: [(ci, cf)] channel positions; D: (npairs, count, count), D[p, i, f] between
         state i of channel ci and state f of cf (dipole_matrix's layout); a0: complex (nscan, nch, count) or (nch, count);
         field: complex (nsteps, 6, nscan), f_q at the stage times (host.field_table).  Returns (a, err), err (nscan,) the largest
         embedded error estimate of a step, or (a, err, snaps) with snaps (nsteps // snap_every, nscan, nch, count)."""
-        E = np.ascontiguousarray(E, dtype=np.float64)
-        nch, count = E.shape
-        ci, cf = self._tdse_pairs(pairs)
-        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
-        a = np.array(a0, dtype=np.complex128, order="C")
-        one = a.ndim == 2
-        a = np.ascontiguousarray(a.reshape(-1, nch, count))
-        nscan = a.shape[0]
+        E, ci, cf, D, a, one, nscan = self._tdse_host(E, pairs, D, a0)
         field = np.ascontiguousarray(field, dtype=np.complex128)
         nsteps = field.shape[0] if field.ndim == 3 else 0
         assert field.shape == (nsteps, 6, nscan), (field.shape, nscan)
-        err = np.zeros(nscan)
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
-        _chk(lib().bspatom_tdse_propagate(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
-                                          _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
-                                          _p(snaps), _p(err)), "bspatom_tdse_propagate")
-        if one:
-            a = a[0]
-        return (a, err) if snaps is None else (a, err, snaps)
+        err, snaps, _ = self._tdse_out(a, nsteps, snap_every)
+        _chk(lib().bspatom_tdse_propagate(*self._tdse_common(*E.shape, E, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snaps, err)),
+             "bspatom_tdse_propagate")
+        return self._tdse_result(a, one, err, None, snaps)
 
     def tdse_propagate_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, snap_every=0, snap_ptr=None):
         """tdse_propagate with E (nch * count doubles at E_ptr), D, the field table (nsteps * 6 * nscan complex) and the amplitudes
@@ -458,10 +489,8 @@ class Problem:
         data_ptr(); snapshots, if asked for, at snap_ptr.  pairs is a host list.  Returns err (nscan,) when the result is there."""
         ci, cf = self._tdse_pairs(pairs)
         err = np.zeros(nscan)
-        _chk(lib().bspatom_tdse_propagate_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
-                                              _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
-                                              float(dt), C.c_void_p(field_ptr), C.c_void_p(a_ptr), snap_every,
-                                              C.c_void_p(snap_ptr) if snap_ptr else None, _p(err)), "bspatom_tdse_propagate_dev")
+        _chk(lib().bspatom_tdse_propagate_dev(*self._tdse_common(nch, count, E_ptr, ci, cf, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr,
+                                                                 snap_every, snap_ptr, err)), "bspatom_tdse_propagate_dev")
         return err
 
     @staticmethod
@@ -477,26 +506,14 @@ class Problem:
         no steps (shape (0, 6, nscan)) measures a0 as given: the expectation values of any blocks over any wave packets."""
         if obs_every < 1:
             raise ValueError("tdse_observe needs obs_every >= 1 (tdse_propagate is the call without observables)")
-        E = np.ascontiguousarray(E, dtype=np.float64)
-        nch, count = E.shape
-        ci, cf = self._tdse_pairs(pairs)
-        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
-        a = np.array(a0, dtype=np.complex128, order="C")
-        one = a.ndim == 2
-        a = np.ascontiguousarray(a.reshape(-1, nch, count))
-        nscan = a.shape[0]
+        E, ci, cf, D, a, one, nscan = self._tdse_host(E, pairs, D, a0)
         field = np.ascontiguousarray(field, dtype=np.complex128)
         nsteps = field.shape[0] if field.ndim == 3 else 0
         assert field.shape == (nsteps, 6, nscan), (field.shape, nscan)
-        err = np.zeros(nscan)
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 4))
-        _chk(lib().bspatom_tdse_observe(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
-                                        _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
-                                        _p(snaps), _p(err), obs_every, _p(obs)), "bspatom_tdse_observe")
-        if one:
-            a = a[0]
-        return (a, err, obs) if snaps is None else (a, err, obs, snaps)
+        err, snaps, obs = self._tdse_out(a, nsteps, snap_every, obs_every)
+        _chk(lib().bspatom_tdse_observe(*self._tdse_common(*E.shape, E, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snaps, err),
+                                        obs_every, _p(obs)), "bspatom_tdse_observe")
+        return self._tdse_result(a, one, err, obs, snaps)
 
     def tdse_observe_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, obs_every, obs_ptr, snap_every=0,
                          snap_ptr=None):
@@ -504,11 +521,8 @@ class Problem:
         doubles of device memory).  Returns err (nscan,) when the result is there."""
         ci, cf = self._tdse_pairs(pairs)
         err = np.zeros(nscan)
-        _chk(lib().bspatom_tdse_observe_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
-                                            _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
-                                            float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
-                                            C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
-                                            C.c_void_p(obs_ptr) if obs_ptr else None), "bspatom_tdse_observe_dev")
+        _chk(lib().bspatom_tdse_observe_dev(*self._tdse_common(nch, count, E_ptr, ci, cf, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, snap_every,
+                                                               snap_ptr, err), obs_every, _ptr(obs_ptr)), "bspatom_tdse_observe_dev")
         return err
 
     def tdse_lawson(self, E, pairs, D, a0, field, dt, obs_every=0, snap_every=0):
@@ -516,26 +530,14 @@ class Problem:
         evolution exp(-i E t) is exact, so the step is bounded by |f| ||D|| and not by dt max|E|.  The arguments and layouts are
         tdse_observe's; obs_every = 0 propagates only.  Returns (a, err[, obs][, snaps]) as tdse_propagate / tdse_observe do, all in
         the Schroedinger picture at step boundaries."""
-        E = np.ascontiguousarray(E, dtype=np.float64)
-        nch, count = E.shape
-        ci, cf = self._tdse_pairs(pairs)
-        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
-        a = np.array(a0, dtype=np.complex128, order="C")
-        one = a.ndim == 2
-        a = np.ascontiguousarray(a.reshape(-1, nch, count))
-        nscan = a.shape[0]
+        E, ci, cf, D, a, one, nscan = self._tdse_host(E, pairs, D, a0)
         field = np.ascontiguousarray(field, dtype=np.complex128)
         nsteps = field.shape[0] if field.ndim == 3 else 0
         assert field.shape == (nsteps, 6, nscan), (field.shape, nscan)
-        err = np.zeros(nscan)
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 4)) if obs_every > 0 else None
-        _chk(lib().bspatom_tdse_lawson(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
-                                       _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
-                                       _p(snaps), _p(err), obs_every, _p(obs)), "bspatom_tdse_lawson")
-        if one:
-            a = a[0]
-        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+        err, snaps, obs = self._tdse_out(a, nsteps, snap_every, obs_every)
+        _chk(lib().bspatom_tdse_lawson(*self._tdse_common(*E.shape, E, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snaps, err),
+                                       obs_every, _p(obs)), "bspatom_tdse_lawson")
+        return self._tdse_result(a, one, err, obs, snaps)
 
     def tdse_lawson_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, obs_every=0, obs_ptr=None, snap_every=0,
                         snap_ptr=None):
@@ -543,11 +545,8 @@ class Problem:
         Returns err (nscan,) when the result is there."""
         ci, cf = self._tdse_pairs(pairs)
         err = np.zeros(nscan)
-        _chk(lib().bspatom_tdse_lawson_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
-                                           _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
-                                           float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
-                                           C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
-                                           C.c_void_p(obs_ptr) if obs_ptr else None), "bspatom_tdse_lawson_dev")
+        _chk(lib().bspatom_tdse_lawson_dev(*self._tdse_common(nch, count, E_ptr, ci, cf, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, snap_every,
+                                                              snap_ptr, err), obs_every, _ptr(obs_ptr)), "bspatom_tdse_lawson_dev")
         return err
 
     @staticmethod
@@ -572,29 +571,15 @@ class Problem:
         partner and without the field.  scheme: 1 = Lawson steps, 0 = the plain tableau.  Returns (a, err[, obs][, snaps]) as
         tdse_lawson does; obs: (nobs, nscan, nch, 6), [..., :4] as tdse_observe, [..., 4:] = Re, Im of s_c = conj(a_c) . S_c
         (host.tdse_static_rates, host.tdse_yield)."""
-        E = np.ascontiguousarray(E, dtype=np.float64)
-        nch, count = E.shape
-        ci, cf = self._tdse_pairs(pairs)
-        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
-        si, sf, skind, W = self._tdse_static(static, count)
-        a = np.array(a0, dtype=np.complex128, order="C")
-        one = a.ndim == 2
-        a = np.ascontiguousarray(a.reshape(-1, nch, count))
-        nscan = a.shape[0]
+        E, ci, cf, D, a, one, nscan = self._tdse_host(E, pairs, D, a0)
+        si, sf, skind, W = self._tdse_static(static, E.shape[1])
         field = np.ascontiguousarray(field, dtype=np.complex128)
         nsteps = field.shape[0] if field.ndim == 3 else 0
         assert field.shape == (nsteps, 6, nscan), (field.shape, nscan)
-        err = np.zeros(nscan)
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 6)) if obs_every > 0 else None
-        ns = len(si)
-        _chk(lib().bspatom_tdse_static(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
-                                       _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
-                                       _p(snaps), _p(err), obs_every, _p(obs), int(scheme), ns, _p(si) if ns else None,
-                                       _p(sf) if ns else None, _p(skind) if ns else None, _p(W) if ns else None), "bspatom_tdse_static")
-        if one:
-            a = a[0]
-        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+        err, snaps, obs = self._tdse_out(a, nsteps, snap_every, obs_every, 6)
+        _chk(lib().bspatom_tdse_static(*self._tdse_common(*E.shape, E, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snaps, err),
+                                       obs_every, _p(obs), *self._tdse_static_args(scheme, si, sf, skind, W)), "bspatom_tdse_static")
+        return self._tdse_result(a, one, err, obs, snaps)
 
     def tdse_static_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, static, scheme=1, obs_every=0,
                         obs_ptr=None, snap_every=0, snap_ptr=None):
@@ -602,15 +587,10 @@ class Problem:
         doubles of W at W_ptr, and rows of 6 doubles per (scan, channel) at obs_ptr.  Returns err (nscan,) when the result is there."""
         ci, cf = self._tdse_pairs(pairs)
         si, sf, skind, W_ptr = self._tdse_static(static)
-        ns = len(si)
         err = np.zeros(nscan)
-        _chk(lib().bspatom_tdse_static_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
-                                           _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
-                                           float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
-                                           C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
-                                           C.c_void_p(obs_ptr) if obs_ptr else None, int(scheme), ns, _p(si) if ns else None,
-                                           _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None),
-             "bspatom_tdse_static_dev")
+        _chk(lib().bspatom_tdse_static_dev(*self._tdse_common(nch, count, E_ptr, ci, cf, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, snap_every,
+                                                              snap_ptr, err), obs_every, _ptr(obs_ptr),
+                                           *self._tdse_static_args(scheme, si, sf, skind, W_ptr)), "bspatom_tdse_static_dev")
         return err
 
     def tdse_adaptive(self, E, pairs, D, a0, fn, dt, static, tol, max_level, nsub=1, level0=0, scheme=1, obs_every=0, snap_every=0,
@@ -623,39 +603,26 @@ class Problem:
         gives them, stats int64 (6,) = accepted, rejected, forced, deepest level, level at the end (level0 of a continued run),
         attempts; log = (log_i (nlog, 4) int32 rows (n, m, j, flag), log_e (nlog, nscan), log_f (nlog, 6, nscan) complex) of the first
         log_cap attempts (host.adapt_steps).  The step sequence depends on all scans of the call; a forced step (flag 2) may exceed tol."""
-        E = np.ascontiguousarray(E, dtype=np.float64)
-        nch, count = E.shape
-        ci, cf = self._tdse_pairs(pairs)
-        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
-        si, sf, skind, W = self._tdse_static(static, count)
-        a = np.array(a0, dtype=np.complex128, order="C")
-        one = a.ndim == 2
-        a = np.ascontiguousarray(a.reshape(-1, nch, count))
-        nscan = a.shape[0]
+        E, ci, cf, D, a, one, nscan = self._tdse_host(E, pairs, D, a0)
+        si, sf, skind, W = self._tdse_static(static, E.shape[1])
         fn = np.ascontiguousarray(fn, dtype=np.complex128)
         nsub = int(nsub)
         if fn.ndim != 3 or fn.shape[1:] != (2, nscan) or nsub < 1 or (fn.shape[0] - 1) % nsub:
             raise ValueError("fn must be (nsteps * nsub + 1, 2, nscan) with nscan = %d, nsub = %d, got %s" % (nscan, nsub, fn.shape))
         nsteps = (fn.shape[0] - 1) // nsub
-        err = np.zeros(nscan)
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 6)) if obs_every > 0 else None
+        err, snaps, obs = self._tdse_out(a, nsteps, snap_every, obs_every, 6)
         stats = np.zeros(6, dtype=np.int64)
         log_i = np.zeros((log_cap, 4), dtype=np.int32) if log_cap > 0 else None
         log_e = np.zeros((log_cap, nscan)) if log_cap > 0 else None
         log_f = np.zeros((log_cap, 6, nscan), dtype=np.complex128) if log_cap > 0 else None
-        ns = len(si)
-        _chk(lib().bspatom_tdse_adaptive(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
-                                         _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(fn), _p(a), snap_every, _p(snaps),
-                                         _p(err), obs_every, _p(obs), int(scheme), ns, _p(si) if ns else None, _p(sf) if ns else None,
-                                         _p(skind) if ns else None, _p(W) if ns else None, nsub, float(tol), int(max_level), int(level0),
-                                         _p(stats), int(log_cap), _p(log_i), _p(log_e), _p(log_f)), "bspatom_tdse_adaptive")
-        if one:
-            a = a[0]
+        _chk(lib().bspatom_tdse_adaptive(*self._tdse_common(*E.shape, E, ci, cf, D, nscan, nsteps, dt, fn, a, snap_every, snaps, err),
+                                         obs_every, _p(obs), *self._tdse_static_args(scheme, si, sf, skind, W), nsub, float(tol),
+                                         int(max_level), int(level0), _p(stats), int(log_cap), _p(log_i), _p(log_e), _p(log_f)),
+             "bspatom_tdse_adaptive")
         nlog = int(min(stats[5], log_cap))
         log = (log_i[:nlog], log_e[:nlog], log_f[:nlog]) if log_cap > 0 else (np.zeros((0, 4), dtype=np.int32), np.zeros((0, nscan)),
                                                                              np.zeros((0, 6, nscan), dtype=np.complex128))
-        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,)) + (stats, log)
+        return self._tdse_result(a, one, err, obs, snaps) + (stats, log)
 
     def tdse_adaptive_dev(self, nch, count, E_ptr, pairs, D_ptr, nscan, nsteps, dt, fn_ptr, a_ptr, static, tol, max_level, nsub=1, level0=0,
                           scheme=1, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None, log_cap=0, log_ptrs=None):
@@ -664,17 +631,12 @@ class Problem:
         each).  Returns (err (nscan,), stats (6,) int64) when the result is there."""
         ci, cf = self._tdse_pairs(pairs)
         si, sf, skind, W_ptr = self._tdse_static(static)
-        ns = len(si)
         err = np.zeros(nscan)
         stats = np.zeros(6, dtype=np.int64)
-        lp = [C.c_void_p(x) if x else None for x in (log_ptrs or (None, None, None))]
-        _chk(lib().bspatom_tdse_adaptive_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
-                                             _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
-                                             float(dt), C.c_void_p(fn_ptr) if fn_ptr else None, C.c_void_p(a_ptr), snap_every,
-                                             C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
-                                             C.c_void_p(obs_ptr) if obs_ptr else None, int(scheme), ns, _p(si) if ns else None,
-                                             _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None,
-                                             int(nsub), float(tol), int(max_level), int(level0), _p(stats), int(log_cap), lp[0], lp[1], lp[2]),
+        _chk(lib().bspatom_tdse_adaptive_dev(*self._tdse_common(nch, count, E_ptr, ci, cf, D_ptr, nscan, nsteps, dt, fn_ptr, a_ptr, snap_every,
+                                                                snap_ptr, err), obs_every, _ptr(obs_ptr),
+                                             *self._tdse_static_args(scheme, si, sf, skind, W_ptr), int(nsub), float(tol), int(max_level),
+                                             int(level0), _p(stats), int(log_cap), *[_ptr(x) for x in (log_ptrs or (None,) * 3)]),
              "bspatom_tdse_adaptive_dev")
         return err, stats
 
@@ -695,32 +657,18 @@ class Problem:
         does; obs: (nobs, nscan, nch, 4 + 2 nfield), [..., :2] population and sum E |a|^2, [..., 2:4] = Re, Im of z_{c,0}, [..., 4:6] of s_c,
         [..., 4 + 2g: 6 + 2g] of z_{c,g}, z_{c,g} the sum over the pairs of field g that end in c (host.tdse_dipole_vector).  A field of
         shape (0, 6, nfield, nscan) measures a0 as given."""
-        E = np.ascontiguousarray(E, dtype=np.float64)
-        nch, count = E.shape
-        ci, cf = self._tdse_pairs(pairs)
-        D = np.ascontiguousarray(D, dtype=np.float64).reshape(len(ci), count, count)
+        E, ci, cf, D, a, one, nscan = self._tdse_host(E, pairs, D, a0)
         fidx = self._tdse_fidx(fidx, len(ci))
-        si, sf, skind, W = self._tdse_static(static, count)
-        a = np.array(a0, dtype=np.complex128, order="C")
-        one = a.ndim == 2
-        a = np.ascontiguousarray(a.reshape(-1, nch, count))
-        nscan = a.shape[0]
+        si, sf, skind, W = self._tdse_static(static, E.shape[1])
         field = np.ascontiguousarray(field, dtype=np.complex128)
         if field.ndim != 4 or field.shape[1] != 6 or field.shape[3] != nscan:
             raise ValueError("field must have shape (nsteps, 6, nfield, %d), got %s" % (nscan, field.shape))
         nsteps, nfield = field.shape[0], field.shape[2]
-        err = np.zeros(nscan)
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, count), dtype=np.complex128) if snap_every > 0 else None
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch, 4 + 2 * max(nfield, 1))) if obs_every > 0 else None
-        ns = len(si)
-        _chk(lib().bspatom_tdse_fields(self._h, nch, count, _p(E), len(ci), _p(ci) if len(ci) else None, _p(cf) if len(ci) else None,
-                                       _p(D) if len(ci) else None, nscan, nsteps, float(dt), _p(field), _p(a), snap_every,
-                                       _p(snaps), _p(err), obs_every, _p(obs), int(scheme), ns, _p(si) if ns else None,
-                                       _p(sf) if ns else None, _p(skind) if ns else None, _p(W) if ns else None, nfield,
-                                       _p(fidx) if fidx is not None and len(ci) else None), "bspatom_tdse_fields")
-        if one:
-            a = a[0]
-        return (a, err) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+        err, snaps, obs = self._tdse_out(a, nsteps, snap_every, obs_every, 4 + 2 * max(nfield, 1))
+        _chk(lib().bspatom_tdse_fields(*self._tdse_common(*E.shape, E, ci, cf, D, nscan, nsteps, dt, field, a, snap_every, snaps, err),
+                                       obs_every, _p(obs), *self._tdse_static_args(scheme, si, sf, skind, W), nfield,
+                                       _p(fidx) if len(ci) else None), "bspatom_tdse_fields")
+        return self._tdse_result(a, one, err, obs, snaps)
 
     def tdse_fields_dev(self, nch, count, E_ptr, pairs, D_ptr, fidx, nfield, nscan, nsteps, dt, field_ptr, a_ptr, static=None, scheme=1,
                         obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None):
@@ -730,15 +678,11 @@ class Problem:
         ci, cf = self._tdse_pairs(pairs)
         fidx = self._tdse_fidx(fidx, len(ci))
         si, sf, skind, W_ptr = self._tdse_static(static)
-        ns = len(si)
         err = np.zeros(nscan)
-        _chk(lib().bspatom_tdse_fields_dev(self._h, nch, count, C.c_void_p(E_ptr), len(ci), _p(ci) if len(ci) else None,
-                                           _p(cf) if len(ci) else None, C.c_void_p(D_ptr) if len(ci) else None, nscan, nsteps,
-                                           float(dt), C.c_void_p(field_ptr) if field_ptr else None, C.c_void_p(a_ptr), snap_every,
-                                           C.c_void_p(snap_ptr) if snap_ptr else None, _p(err), obs_every,
-                                           C.c_void_p(obs_ptr) if obs_ptr else None, int(scheme), ns, _p(si) if ns else None,
-                                           _p(sf) if ns else None, _p(skind) if ns else None, C.c_void_p(W_ptr) if ns else None,
-                                           int(nfield), _p(fidx) if fidx is not None and len(ci) else None), "bspatom_tdse_fields_dev")
+        _chk(lib().bspatom_tdse_fields_dev(*self._tdse_common(nch, count, E_ptr, ci, cf, D_ptr, nscan, nsteps, dt, field_ptr, a_ptr, snap_every,
+                                                              snap_ptr, err), obs_every, _ptr(obs_ptr),
+                                           *self._tdse_static_args(scheme, si, sf, skind, W_ptr), int(nfield), _p(fidx) if len(ci) else None),
+             "bspatom_tdse_fields_dev")
         return err
 
     def early_vector_state(self):

@@ -343,7 +343,6 @@ struct TdseBufs {
     // is [nf][nscan][2]; part and the rows are ow = 4 + 2 nf doubles wide, and the kernels of tdse_fields.hip run, with or without W
     int nf = 1;
 };
-extern const double TDSE_A[6][5], TDSE_D[6], TDSE_B[6];
 int tdse_columns(int nscan);
 // one step: six stage launches and the step kernel; d_field: the 6 * w.nf * nscan complex values of this step; d_snap: null, or where the
 // new amplitudes go in the caller's layout [nscan][nch][count] complex; d_obs: null, or where the observables of the amplitudes
@@ -354,14 +353,7 @@ int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field
 int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *d_field, double *d_row, hipStream_t st);
 // the phase table of bspatom_tdse_lawson from d_E, once per call
 int launch_tdse_phases(const TdseDims &d, const double *d_E, double dt, double *d_ph, hipStream_t st);
-// tdse_static.hip: what the launchers above launch when w.W is set (stage S, the observing stage 0) or w.ow is 6 (the reduction)
-int launch_tdse_static_stage(int S, const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st);
-int launch_tdse_static_observe(const TdseDims &d, const TdseBufs &w, const double *fld, bool lawson, hipStream_t st);
-int launch_tdse_static_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st);
-// tdse_fields.hip: what they launch instead when w.nf > 1
-int launch_tdse_fields_stage(int S, const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st);
-int launch_tdse_fields_observe(const TdseDims &d, const TdseBufs &w, const double *fld, bool lawson, hipStream_t st);
-int launch_tdse_fields_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st);
+// (with w.W set, w.ow = 6 or w.nf > 1 these launch the kernels of tdse_static.hip and tdse_fields.hip: tdse_launch.h)
 int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st);
 int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st);
 

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "mfma_tile.h"
 #include "tdse_stage.h"
+#include "tdse_launch.h"
 
 namespace bsp {
 
@@ -151,31 +152,20 @@ int tdse_columns(int nscan) { return (2 * nscan + 15) / 16 * 16; }
 template <int S>
 static int launch_stage_s(const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st)
 {
-    StageCoef cf;
-    for (int j = 0; j < 5; ++j) cf.w[j] = TDSE_A[S][j];
-    const int tm = (d.count + TBM - 1) / TBM;
-    const size_t ks = (size_t)d.nch * d.count * d.NC;
     KScope ks_(KS_TDSE, st);
     if (w.nf > 1) return launch_tdse_fields_stage(S, d, w, fld, dt, st);         // several drive fields (tdse_fields.hip)
     if (w.W) return launch_tdse_static_stage(S, d, w, fld, dt, st);              // static blocks, either scheme (tdse_static.hip)
-    const int tn = d.NC == 16 ? 1 : (d.NC + 31) / 32;
-    const long long grid = (long long)d.nch * tm * tn;
-    if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    const int TN = d.NC == 16 ? 1 : 2;
+    const StageGrid g = stage_grid(d, TN);
+    if (!g.ok) return BSP_ERR_UNSUPPORTED;
     if (w.ph) {
-        // Lawson: the phases of stage S (stage 0 has none)
-        const double *phs = S > 0 ? w.ph + (size_t)(S - 1) * d.nch * d.count * 2 : nullptr;
-        if (d.NC == 16)
-            hipLaunchKernelGGL((tdse_lawson_stage_kernel<S, 1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr,
-                               w.ent, w.D, w.a, w.K, ks, fld, cf, dt, phs);
-        else
-            hipLaunchKernelGGL((tdse_lawson_stage_kernel<S, 2>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr,
-                               w.ent, w.D, w.a, w.K, ks, fld, cf, dt, phs);
-    } else if (d.NC == 16) {
-        hipLaunchKernelGGL((tdse_stage_kernel<S, 1>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent,
-                           w.E, w.D, w.a, w.K, ks, fld, cf, dt);
+        auto kern = TN == 1 ? tdse_lawson_stage_kernel<S, 1> : tdse_lawson_stage_kernel<S, 2>;
+        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.D, w.a, w.K, k_stride(d),
+                           fld, stage_coef<S>(), dt, stage_phases(S, d, w));
     } else {
-        hipLaunchKernelGGL((tdse_stage_kernel<S, 2>), dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent,
-                           w.E, w.D, w.a, w.K, ks, fld, cf, dt);
+        auto kern = TN == 1 ? tdse_stage_kernel<S, 1> : tdse_stage_kernel<S, 2>;
+        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.a, w.K,
+                           k_stride(d), fld, stage_coef<S>(), dt);
     }
     BSP_HIP(hipGetLastError());
     return BSP_OK;
@@ -183,12 +173,11 @@ static int launch_stage_s(const TdseDims &d, const TdseBufs &w, const double *fl
 
 int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld, double *d_row, hipStream_t st)
 {
-    const int tm = (d.count + TBM - 1) / TBM;
+    const int TN = d.NC == 16 ? 1 : 2;
+    const StageGrid g = stage_grid(d, TN);
     {
         KScope ks_(KS_TDSE, st);
-        const int tn = d.NC == 16 ? 1 : (d.NC + 31) / 32;
-        const long long grid = (long long)d.nch * tm * tn;
-        if (grid > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+        if (!g.ok) return BSP_ERR_UNSUPPORTED;
         // a Lawson step's stage 0 leaves another k_0; a measurement alone (fld null) is the same kernel for both schemes
         const bool lawson = w.ph && fld;
         if (w.nf > 1) {
@@ -198,18 +187,18 @@ int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld,
             const int rc = launch_tdse_static_observe(d, w, fld, lawson, st);
             if (rc) return rc;
         } else {
-            auto kern = d.NC == 16 ? (lawson ? tdse_lawson_observe_kernel<1> : tdse_observe_kernel<1>)
-                                   : (lawson ? tdse_lawson_observe_kernel<2> : tdse_observe_kernel<2>);
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, d.count, d.NC, d.nscan, tm, tn, w.cptr, w.ent, w.E, w.D, w.a, w.K,
+            auto kern = TN == 1 ? (lawson ? tdse_lawson_observe_kernel<1> : tdse_observe_kernel<1>)
+                                : (lawson ? tdse_lawson_observe_kernel<2> : tdse_observe_kernel<2>);
+            hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.a, w.K,
                                fld, w.part);
             BSP_HIP(hipGetLastError());
         }
     }
     if (w.nf > 1) return launch_tdse_fields_reduce(d, w, d_row, st);            // rows of 4 + 2 nf (bspatom_tdse_fields)
     if (w.ow == 6) return launch_tdse_static_reduce(d, w, d_row, st);           // rows of 6 (bspatom_tdse_static)
-    const long long blocks = ((long long)d.nscan * d.nch + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(tdse_obs_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d.nch, tm, d.NC / 2, d.nscan, w.part, d_row);
+    const Blocks b = reduce_blocks(d);
+    if (!b.ok) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_obs_reduce_kernel, dim3(b.n), dim3(256), 0, st, d.nch, g.tm, d.NC / 2, d.nscan, w.part, d_row);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
@@ -217,24 +206,19 @@ int launch_tdse_observe(const TdseDims &d, const TdseBufs &w, const double *fld,
 int launch_tdse_step(const TdseDims &d, const TdseBufs &w, const double *d_field, double dt, double *d_snap, double *d_obs, hipStream_t st)
 {
     const size_t fs = (size_t)2 * d.nscan * w.nf;
-    int rc;
-    if ((rc = d_obs ? launch_tdse_observe(d, w, d_field, d_obs, st) : launch_stage_s<0>(d, w, d_field, dt, st)) ||
-        (rc = launch_stage_s<1>(d, w, d_field + fs, dt, st)) ||
-        (rc = launch_stage_s<2>(d, w, d_field + 2 * fs, dt, st)) || (rc = launch_stage_s<3>(d, w, d_field + 3 * fs, dt, st)) ||
-        (rc = launch_stage_s<4>(d, w, d_field + 4 * fs, dt, st)) || (rc = launch_stage_s<5>(d, w, d_field + 5 * fs, dt, st)))
-        return rc;
-    StepCoef sc;
-    for (int j = 0; j < 6; ++j) { sc.d[j] = TDSE_D[j]; sc.e[j] = TDSE_D[j] - TDSE_B[j]; }
-    const long long rows = (long long)d.nch * d.count;
-    const long long gx = (rows + 31) / 32;
-    const int gy = (d.NC / 2 + 7) / 8;
-    if (gx > 0x7fffffffLL || gy > 65535) return BSP_ERR_UNSUPPORTED;
+    for (int S = 0; S < 6; ++S) {
+        const int rc = S == 0 && d_obs ? launch_tdse_observe(d, w, d_field, d_obs, st)
+                                       : dispatch_stage(S, [&](auto s) { return launch_stage_s<decltype(s)::value>(d, w, d_field + S * fs, dt, st); });
+        if (rc) return rc;
+    }
+    const StepGrid g = step_grid(d);
+    if (!g.ok) return BSP_ERR_UNSUPPORTED;
     if (w.ph)
-        hipLaunchKernelGGL(tdse_lawson_step_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
-                           (size_t)rows * d.NC, sc, dt, w.err2, d_snap, w.ph + (size_t)3 * rows * 2);
+        hipLaunchKernelGGL(tdse_lawson_step_kernel, g.grid, dim3(256), 0, st, g.rows, d.NC, d.nscan, w.a, w.K, k_stride(d), step_coef(), dt,
+                           w.err2, d_snap, step_phases(d, w));
     else
-        hipLaunchKernelGGL(tdse_step_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
-                           (size_t)rows * d.NC, sc, dt, w.err2, d_snap);
+        hipLaunchKernelGGL(tdse_step_kernel, g.grid, dim3(256), 0, st, g.rows, d.NC, d.nscan, w.a, w.K, k_stride(d), step_coef(), dt, w.err2,
+                           d_snap);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
@@ -244,28 +228,31 @@ int launch_tdse_phases(const TdseDims &d, const double *d_E, double dt, double *
     const double c[5] = {2.0 / 9.0, 1.0 / 3.0, 3.0 / 4.0, 1.0, 5.0 / 6.0};      // c_1 .. c_5: the doubles nearest the fractions
     PhaseCoef pc;
     for (int s = 0; s < 5; ++s) pc.cdt[s] = c[s] * dt;
-    const long long rows = (long long)d.nch * d.count, blocks = (rows + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    const long long rows = (long long)d.nch * d.count;
+    const Blocks b = blocks256(rows);
+    if (!b.ok) return BSP_ERR_UNSUPPORTED;
     KScope ks_(KS_TDSE, st);
-    hipLaunchKernelGGL(tdse_phase_kernel, dim3((unsigned)blocks), dim3(256), 0, st, rows, d_E, pc, d_ph);
+    hipLaunchKernelGGL(tdse_phase_kernel, dim3(b.n), dim3(256), 0, st, rows, d_E, pc, d_ph);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
 
 int launch_tdse_pack(const TdseDims &d, const double *d_user, double *d_work, hipStream_t st)
 {
-    const long long rows = (long long)d.nch * d.count, total = rows * d.NC, blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(tdse_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, rows, d.NC, d.nscan, d_user, d_work);
+    const long long rows = (long long)d.nch * d.count;
+    const Blocks b = blocks256(rows * d.NC);
+    if (!b.ok) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_pack_kernel, dim3(b.n), dim3(256), 0, st, rows, d.NC, d.nscan, d_user, d_work);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
 
 int launch_tdse_unpack(const TdseDims &d, const double *d_work, double *d_user, hipStream_t st)
 {
-    const long long rows = (long long)d.nch * d.count, total = rows * 2 * d.nscan, blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(tdse_unpack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, rows, d.NC, d.nscan, d_work, d_user);
+    const long long rows = (long long)d.nch * d.count;
+    const Blocks b = blocks256(rows * 2 * d.nscan);
+    if (!b.ok) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_unpack_kernel, dim3(b.n), dim3(256), 0, st, rows, d.NC, d.nscan, d_work, d_user);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }

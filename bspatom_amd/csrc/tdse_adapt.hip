@@ -8,6 +8,7 @@
 #include "common.h"
 #include "mfma_tile.h"
 #include "tdse_stage.h"
+#include "tdse_launch.h"
 
 namespace bsp {
 
@@ -187,30 +188,17 @@ __global__ __launch_bounds__(256) void tdse_adapt_control_kernel(TdseAdaptCtl *_
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
 // The column tile is the one bspatom_tdse_static takes on the same arguments: 16 columns with static blocks (tdse_static.hip), and
 // without them 16 up to 8 scans, 32 above (tdse.hip).  The sums of an element do not depend on it.
-struct AdaptGrid { int tm, tn, TN; unsigned grid; bool ok; };
-static AdaptGrid adapt_grid(const TdseDims &d, const TdseBufs &w)
-{
-    const int tm = (d.count + TBM - 1) / TBM;
-    const int TN = (w.W || d.NC == 16) ? 1 : 2;
-    const int tn = TN == 1 ? d.NC / 16 : (d.NC + 31) / 32;
-    const long long grid = (long long)d.nch * tm * tn;
-    return {tm, tn, TN, (unsigned)grid, grid <= 0x7fffffffLL};
-}
-
 template <int S, bool OBS>
 static int launch_adapt_stage_s(const TdseDims &d, const TdseBufs &w, const TdseAdaptCtl *ctl, double dt, size_t phlev, hipStream_t st)
 {
-    StageCoef cf;
-    for (int j = 0; j < 5; ++j) cf.w[j] = TDSE_A[S][j];
-    const AdaptGrid g = adapt_grid(d, w);
+    const int TN = (w.W || d.NC == 16) ? 1 : 2;
+    const StageGrid g = stage_grid(d, TN);
     if (!g.ok) return BSP_ERR_UNSUPPORTED;
-    const size_t ks = (size_t)d.nch * d.count * d.NC;
-    const double *phs = w.ph && S > 0 ? w.ph + (size_t)(S - 1) * d.nch * d.count * 2 : nullptr;
-    auto kern = w.ph ? (g.TN == 1 ? tdse_adapt_stage_kernel<S, 1, OBS, true> : tdse_adapt_stage_kernel<S, 2, OBS, true>)
-                     : (g.TN == 1 ? tdse_adapt_stage_kernel<S, 1, OBS, false> : tdse_adapt_stage_kernel<S, 2, OBS, false>);
+    auto kern = w.ph ? (TN == 1 ? tdse_adapt_stage_kernel<S, 1, OBS, true> : tdse_adapt_stage_kernel<S, 2, OBS, true>)
+                     : (TN == 1 ? tdse_adapt_stage_kernel<S, 1, OBS, false> : tdse_adapt_stage_kernel<S, 2, OBS, false>);
     KScope ks_(KS_TDSE, st);
     hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.W, w.a, w.K,
-                       OBS ? (size_t)0 : ks, cf, dt, OBS ? w.part : nullptr, phs, phlev, ctl);
+                       OBS ? (size_t)0 : k_stride(d), stage_coef<S>(), dt, OBS ? w.part : nullptr, stage_phases(S, d, w), phlev, ctl);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
@@ -231,41 +219,35 @@ int launch_tdse_adapt_init(const TdseDims &d, const TdseBufs &w, TdseAdaptCtl *c
 int launch_tdse_adapt_attempt(const TdseDims &d, const TdseBufs &w, TdseAdaptCtl *ctl, const TdseAdaptArgs &g, long long t, double *cand,
                               size_t phlev, double *d_snap, double *d_obs, hipStream_t st)
 {
-    const long long rows = (long long)d.nch * d.count;
-    const size_t odbl = (size_t)6 * d.nscan * d.nch, adbl = (size_t)rows * d.nscan * 2;
+    const size_t odbl = (size_t)6 * d.nscan * d.nch;
     int rc;
     if ((rc = d_obs ? launch_adapt_stage_s<0, true>(d, w, ctl, g.dt, phlev, st) : launch_adapt_stage_s<0, false>(d, w, ctl, g.dt, phlev, st)))
         return rc;
     if (d_obs) {
-        const long long blocks = ((long long)d.nscan * d.nch + 255) / 256;
-        if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+        const Blocks b = reduce_blocks(d);
+        if (!b.ok) return BSP_ERR_UNSUPPORTED;
         KScope ks_(KS_TDSE, st);
-        hipLaunchKernelGGL(tdse_adapt_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d.nch, (d.count + TBM - 1) / TBM, d.NC / 2,
-                           d.nscan, w.part, d_obs, odbl, ctl);
+        hipLaunchKernelGGL(tdse_adapt_reduce_kernel, dim3(b.n), dim3(256), 0, st, d.nch, stage_grid(d, 1).tm, d.NC / 2, d.nscan, w.part, d_obs,
+                           odbl, ctl);
         BSP_HIP(hipGetLastError());
     }
-    if ((rc = launch_adapt_stage_s<1, false>(d, w, ctl, g.dt, phlev, st)) || (rc = launch_adapt_stage_s<2, false>(d, w, ctl, g.dt, phlev, st)) ||
-        (rc = launch_adapt_stage_s<3, false>(d, w, ctl, g.dt, phlev, st)) || (rc = launch_adapt_stage_s<4, false>(d, w, ctl, g.dt, phlev, st)) ||
-        (rc = launch_adapt_stage_s<5, false>(d, w, ctl, g.dt, phlev, st)))
-        return rc;
-    StepCoef sc;
-    for (int j = 0; j < 6; ++j) { sc.d[j] = TDSE_D[j]; sc.e[j] = TDSE_D[j] - TDSE_B[j]; }
-    const long long gx = (rows + 31) / 32, cb = (rows * d.NC + 255) / 256;
-    const int gy = (d.NC / 2 + 7) / 8;
-    if (gx > 0x7fffffffLL || gy > 65535 || cb > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
+    for (int S = 1; S < 6; ++S)
+        if ((rc = dispatch_stage(S, [&](auto s) { return launch_adapt_stage_s<decltype(s)::value, false>(d, w, ctl, g.dt, phlev, st); })))
+            return rc;
+    const StepGrid sg = step_grid(d);
+    const Blocks cb = blocks256(sg.rows * d.NC);
+    if (!sg.ok || !cb.ok) return BSP_ERR_UNSUPPORTED;
+    const size_t adbl = (size_t)sg.rows * d.nscan * 2;
     {
         KScope ks_(KS_TDSE, st);
-        if (w.ph)
-            hipLaunchKernelGGL(tdse_adapt_step_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
-                               (size_t)rows * d.NC, sc, g.dt, w.err2, w.ph + (size_t)3 * rows * 2, phlev, ctl, cand);
-        else
-            hipLaunchKernelGGL(tdse_adapt_step_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, rows, d.NC, d.nscan, w.a, w.K,
-                               (size_t)rows * d.NC, sc, g.dt, w.err2, nullptr, phlev, ctl, cand);
+        auto kern = w.ph ? tdse_adapt_step_kernel<true> : tdse_adapt_step_kernel<false>;
+        hipLaunchKernelGGL(kern, sg.grid, dim3(256), 0, st, sg.rows, d.NC, d.nscan, w.a, w.K, k_stride(d), step_coef(), g.dt, w.err2,
+                           step_phases(d, w), phlev, ctl, cand);
         BSP_HIP(hipGetLastError());
     }
     if ((rc = launch_adapt_control(d, w, ctl, g, 0, st))) return rc;
     KScope ks_(KS_TDSE, st);
-    hipLaunchKernelGGL(tdse_adapt_commit_kernel, dim3((unsigned)cb), dim3(256), 0, st, rows, d.NC, d.nscan, cand, w.a, d_snap, adbl, ctl, t);
+    hipLaunchKernelGGL(tdse_adapt_commit_kernel, dim3(cb.n), dim3(256), 0, st, sg.rows, d.NC, d.nscan, cand, w.a, d_snap, adbl, ctl, t);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }

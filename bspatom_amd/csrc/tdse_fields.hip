@@ -6,6 +6,7 @@
 #include "common.h"
 #include "mfma_tile.h"
 #include "tdse_stage.h"
+#include "tdse_launch.h"
 
 namespace bsp {
 
@@ -55,53 +56,31 @@ __global__ __launch_bounds__(256) void tdse_obs_reduce_fields_kernel(int nch, in
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
 // The narrow column tile (TN = 1, 8 scans per workgroup) for every nscan, as tdse_static.hip and for its reason
-struct FieldsGrid { int tm, tn; unsigned grid; bool ok; };
-static FieldsGrid fields_grid(const TdseDims &d)
-{
-    const int tm = (d.count + TBM - 1) / TBM, tn = d.NC / 16;
-    const long long grid = (long long)d.nch * tm * tn;
-    return {tm, tn, (unsigned)grid, grid <= 0x7fffffffLL};
-}
-
 template <int S, int NF>
 static int launch_fields_stage_sn(const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st)
 {
-    StageCoef cf;
-    for (int j = 0; j < 5; ++j) cf.w[j] = TDSE_A[S][j];
-    const FieldsGrid g = fields_grid(d);
+    const StageGrid g = stage_grid(d, 1);
     if (!g.ok) return BSP_ERR_UNSUPPORTED;
-    const size_t ks = (size_t)d.nch * d.count * d.NC;
-    const double *phs = w.ph && S > 0 ? w.ph + (size_t)(S - 1) * d.nch * d.count * 2 : nullptr;
     auto kern = w.ph ? tdse_fields_stage_kernel<S, NF, true> : tdse_fields_stage_kernel<S, NF, false>;
-    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.W, w.a, w.K, ks,
-                       fld, cf, dt, phs);
+    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.W, w.a, w.K,
+                       k_stride(d), fld, stage_coef<S>(), dt, stage_phases(S, d, w));
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
 
-template <int S>
-static int launch_fields_stage_s(const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st)
-{
-    if (w.nf == 2) return launch_fields_stage_sn<S, 2>(d, w, fld, dt, st);
-    if (w.nf == 3) return launch_fields_stage_sn<S, 3>(d, w, fld, dt, st);
-    return BSP_ERR_UNSUPPORTED;
-}
-
 int launch_tdse_fields_stage(int S, const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st)
 {
-    switch (S) {
-    case 0: return launch_fields_stage_s<0>(d, w, fld, dt, st);
-    case 1: return launch_fields_stage_s<1>(d, w, fld, dt, st);
-    case 2: return launch_fields_stage_s<2>(d, w, fld, dt, st);
-    case 3: return launch_fields_stage_s<3>(d, w, fld, dt, st);
-    case 4: return launch_fields_stage_s<4>(d, w, fld, dt, st);
-    default: return launch_fields_stage_s<5>(d, w, fld, dt, st);
-    }
+    return dispatch_stage(S, [&](auto s) {
+        constexpr int S_ = decltype(s)::value;
+        if (w.nf == 2) return launch_fields_stage_sn<S_, 2>(d, w, fld, dt, st);
+        if (w.nf == 3) return launch_fields_stage_sn<S_, 3>(d, w, fld, dt, st);
+        return (int)BSP_ERR_UNSUPPORTED;
+    });
 }
 
 int launch_tdse_fields_observe(const TdseDims &d, const TdseBufs &w, const double *fld, bool lawson, hipStream_t st)
 {
-    const FieldsGrid g = fields_grid(d);
+    const StageGrid g = stage_grid(d, 1);
     if (!g.ok || w.nf < 2 || w.nf > 3) return BSP_ERR_UNSUPPORTED;
     auto kern = w.nf == 2 ? (lawson ? tdse_fields_observe_kernel<2, true> : tdse_fields_observe_kernel<2, false>)
                           : (lawson ? tdse_fields_observe_kernel<3, true> : tdse_fields_observe_kernel<3, false>);
@@ -113,10 +92,10 @@ int launch_tdse_fields_observe(const TdseDims &d, const TdseBufs &w, const doubl
 
 int launch_tdse_fields_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st)
 {
-    const long long blocks = ((long long)d.nscan * d.nch + 255) / 256;
-    if (blocks > 0x7fffffffLL || w.nf < 2 || w.nf > 3) return BSP_ERR_UNSUPPORTED;
+    const Blocks b = reduce_blocks(d);
+    if (!b.ok || w.nf < 2 || w.nf > 3) return BSP_ERR_UNSUPPORTED;
     auto kern = w.nf == 2 ? tdse_obs_reduce_fields_kernel<8> : tdse_obs_reduce_fields_kernel<10>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, st, d.nch, (d.count + TBM - 1) / TBM, d.NC / 2, d.nscan, w.part, d_row);
+    hipLaunchKernelGGL(kern, dim3(b.n), dim3(256), 0, st, d.nch, stage_grid(d, 1).tm, d.NC / 2, d.nscan, w.part, d_row);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "mfma_tile.h"
 #include "tdse_stage.h"
+#include "tdse_launch.h"
 
 namespace bsp {
 
@@ -58,45 +59,26 @@ __global__ __launch_bounds__(256) void tdse_obs_reduce6_kernel(int nch, int tm, 
 // The static kernels run on the narrow column tile (TN = 1, 16 columns = 8 scans per workgroup) for every nscan: the wide tile of
 // tdse.hip (TN = 2 above 8 scans) would hold 180 .. 208 registers as a static Lawson stage, two waves per SIMD, and measured 0.615
 // against 0.443 ms per step at nscan = 16.
-struct StaticGrid { int tm, tn; unsigned grid; bool ok; };
-static StaticGrid static_grid(const TdseDims &d)
-{
-    const int tm = (d.count + TBM - 1) / TBM, tn = d.NC / 16;
-    const long long grid = (long long)d.nch * tm * tn;
-    return {tm, tn, (unsigned)grid, grid <= 0x7fffffffLL};
-}
-
 template <int S>
 static int launch_static_stage_s(const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st)
 {
-    StageCoef cf;
-    for (int j = 0; j < 5; ++j) cf.w[j] = TDSE_A[S][j];
-    const StaticGrid g = static_grid(d);
+    const StageGrid g = stage_grid(d, 1);
     if (!g.ok) return BSP_ERR_UNSUPPORTED;
-    const size_t ks = (size_t)d.nch * d.count * d.NC;
-    const double *phs = w.ph && S > 0 ? w.ph + (size_t)(S - 1) * d.nch * d.count * 2 : nullptr;
     auto kern = w.ph ? tdse_static_stage_kernel<S, 1, true> : tdse_static_stage_kernel<S, 1, false>;
-    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.W, w.a, w.K, ks,
-                       fld, cf, dt, phs);
+    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.W, w.a, w.K,
+                       k_stride(d), fld, stage_coef<S>(), dt, stage_phases(S, d, w));
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
 
 int launch_tdse_static_stage(int S, const TdseDims &d, const TdseBufs &w, const double *fld, double dt, hipStream_t st)
 {
-    switch (S) {
-    case 0: return launch_static_stage_s<0>(d, w, fld, dt, st);
-    case 1: return launch_static_stage_s<1>(d, w, fld, dt, st);
-    case 2: return launch_static_stage_s<2>(d, w, fld, dt, st);
-    case 3: return launch_static_stage_s<3>(d, w, fld, dt, st);
-    case 4: return launch_static_stage_s<4>(d, w, fld, dt, st);
-    default: return launch_static_stage_s<5>(d, w, fld, dt, st);
-    }
+    return dispatch_stage(S, [&](auto s) { return launch_static_stage_s<decltype(s)::value>(d, w, fld, dt, st); });
 }
 
 int launch_tdse_static_observe(const TdseDims &d, const TdseBufs &w, const double *fld, bool lawson, hipStream_t st)
 {
-    const StaticGrid g = static_grid(d);
+    const StageGrid g = stage_grid(d, 1);
     if (!g.ok) return BSP_ERR_UNSUPPORTED;
     auto kern = lawson ? tdse_static_observe_kernel<1, true> : tdse_static_observe_kernel<1, false>;
     hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), 0, st, d.count, d.NC, d.nscan, g.tm, g.tn, w.cptr, w.ent, w.E, w.D, w.W, w.a, w.K, fld,
@@ -107,10 +89,10 @@ int launch_tdse_static_observe(const TdseDims &d, const TdseBufs &w, const doubl
 
 int launch_tdse_static_reduce(const TdseDims &d, const TdseBufs &w, double *d_row, hipStream_t st)
 {
-    const long long blocks = ((long long)d.nscan * d.nch + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BSP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(tdse_obs_reduce6_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d.nch, (d.count + TBM - 1) / TBM, d.NC / 2, d.nscan,
-                       w.W ? 6 : 4, w.part, d_row);
+    const Blocks b = reduce_blocks(d);
+    if (!b.ok) return BSP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tdse_obs_reduce6_kernel, dim3(b.n), dim3(256), 0, st, d.nch, stage_grid(d, 1).tm, d.NC / 2, d.nscan, w.W ? 6 : 4, w.part,
+                       d_row);
     BSP_HIP(hipGetLastError());
     return BSP_OK;
 }
