@@ -198,7 +198,8 @@ struct CrawfordWork {
     double *SBf, *UBf, *rdiagf;  // [2][k][n] overlap in reversed order and as it is, their Cholesky factors, [2][n] reciprocal pivots
     double *Qel, *LiB;           // [2][N][256] elimination transforms, [2][N][64] inverse diagonal blocks of L (N = ceil(n / 8))
     double *D, *E, *G;           // [nl][2 (N + 2)][64] diagonal / sub-diagonal blocks of the working matrix, the fill in flight (run from
-                                 // both ends: [2 nl][blocks of the longer part + 2][64])
+                                 // both ends: [2 nl][blocks of the longer part + 2][64]); D holds packed lower triangles, 36 doubles a block
+    double *U;                   // [2 nl][28] the strict upper triangle of diagonal block 0 (inside D's region, behind the records)
     int *info;                   // device word: order of the minor at which the Cholesky factorisation of the reversed overlap broke down
 };
 bool crawford_supported(int n, int k);

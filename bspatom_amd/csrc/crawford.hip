@@ -39,6 +39,16 @@ namespace {
 
 constexpr int CB = 8;              // block size = largest half-width of the pencil this route takes
 constexpr int CBB = CB * CB;
+// DIAGONAL BLOCKS ARE STORED AS PACKED LOWER TRIANGLES.  D_p is symmetric and every reader of the chase takes its lower triangle, so a
+// record is the 36 doubles of that triangle by rows (288 B instead of 512; a window D_p, D_{p+1} is one run of 576 B, 16-byte aligned):
+// 28 of 64 doubles are neither written, written back at the launch boundary nor fetched again.  The one block whose full square is read
+// is D_0 (crawford_corner_kernel, rows of both triangles as the congruences computed them -- they agree to rounding only): its strict
+// upper triangle lives in a side array of CWU doubles per channel, written by whoever writes block 0.  E and G keep their squares.
+constexpr int CWD = CB * (CB + 1) / 2;                                   // doubles of a diagonal block's record
+constexpr int CWU = CBB - CWD;                                           // ... of block 0's strict upper triangle
+__host__ __device__ constexpr int cw_pk(int i, int j) { return i * (i + 1) / 2 + j; }   // (i, j), i >= j, in a record
+__host__ __device__ constexpr int cw_up(int i, int j) { return cw_pk(j - 1, i); }       // (i, j), i < j, in block 0's side array
+static_assert(cw_pk(CB - 1, CB - 1) == CWD - 1 && cw_up(CB - 2, CB - 1) == CWU - 1, "the last places of the two triangles");
 
 template <int CTRL>
 __device__ __forceinline__ double cw_dpp(double x)
@@ -132,7 +142,7 @@ __device__ __forceinline__ double4_t cw_mfma(double a, double b, double4_t acc)
 // from both ends, below: the second half of the batch is the leading part of the pencil, with the factor of S itself)
 template <bool ONEDIV>
 __global__ __launch_bounds__(256) void crawford_item_kernel(int N, int t, int jlo, int nch, int jel, int nlh, int qstride, int nlead,
-                                                           const double *__restrict__ Qel, double *Dall, double *Eall, double *Gall)
+                                                           const double *__restrict__ Qel, double *Dall, double *Eall, double *Gall, double *Uall)
 {
     if ((int)blockIdx.y >= nlh) {                                          // a leading part of nlead blocks: the items beyond do not exist
         if (jlo + nch > nlead) nch = nlead > jlo ? nlead - jlo : 0;
@@ -148,8 +158,8 @@ __global__ __launch_bounds__(256) void crawford_item_kernel(int N, int t, int jl
     else if (idx == nch && jel > 0) { elim = true; j = jel; p = j - 1; }
     else return;
     const size_t chn = (size_t)blockIdx.y * N * CBB;
-    double *D = Dall + chn, *E = Eall + chn, *G = Gall + chn;
-    double *D0 = D + (size_t)p * CBB, *D1 = D0 + CBB, *E0 = E + (size_t)p * CBB;
+    double *D = Dall + (size_t)blockIdx.y * N * CWD, *E = Eall + chn, *G = Gall + chn, *U0 = Uall + (size_t)blockIdx.y * CWU;
+    double *D0 = D + (size_t)p * CWD, *D1 = D0 + CWD, *E0 = E + (size_t)p * CBB;
 
     // ---- loads: the window, symmetric by construction (lower triangles of D), and the block in front of it ----
     double w[4], sd[2];
@@ -157,8 +167,8 @@ __global__ __launch_bounds__(256) void crawford_item_kernel(int N, int t, int jl
     for (int r = 0; r < 2; ++r) {
         const int R = 4 * r + g;
         const int hi = R > c8 ? R : c8, lo = R > c8 ? c8 : R;
-        w[r] = *(left ? D0 + hi * CB + lo : E0 + c8 * CB + R);
-        w[r + 2] = *(left ? E0 + R * CB + c8 : D1 + hi * CB + lo);
+        w[r] = *(left ? D0 + cw_pk(hi, lo) : E0 + c8 * CB + R);
+        w[r + 2] = *(left ? E0 + R * CB + c8 : D1 + cw_pk(hi, lo));
     }
     const bool side = p >= 1;
     {
@@ -208,16 +218,21 @@ __global__ __launch_bounds__(256) void crawford_item_kernel(int N, int t, int jl
     O = cw_mfma(q[0], sd[0], O);
     O = cw_mfma(q[1], sd[1], O);
 
-    // ---- stores ----
+    // ---- stores: of the diagonal blocks the lower triangles, and block 0's upper one to its side array ----
     if (left) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-            D0[(4 * r + g) * CB + c8] = Wn[r];
-            E0[(4 * r + g) * CB + c8] = Wn[r + 2];
+            const int R = 4 * r + g;
+            if (R >= c8) D0[cw_pk(R, c8)] = Wn[r];
+            else if (p == 0) U0[cw_up(R, c8)] = Wn[r];
+            E0[R * CB + c8] = Wn[r + 2];
         }
     } else {
 #pragma unroll
-        for (int r = 0; r < 2; ++r) D1[(4 * r + g) * CB + c8] = Wn[r + 2];
+        for (int r = 0; r < 2; ++r) {
+            const int R = 4 * r + g;
+            if (R >= c8) D1[cw_pk(R, c8)] = Wn[r + 2];
+        }
     }
     if (side && left) {
         double *Em = E + (size_t)(p - 1) * CBB, *Gm = G + (size_t)(p - 1) * CBB;
@@ -465,7 +480,7 @@ template <bool ONEDIV, bool BCAST>
 __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo, int nch, int jel, const int ipw, const int nlh,
                                         const int qstride, const int nlead, const int chan, const int idx0, const int lane,
                                         double *Qsw, double *Bcw, double *Wsw, const double *__restrict__ Qel, double *Dall, double *Eall,
-                                        double *Gall, unsigned long long *diag)
+                                        double *Gall, double *Uall, unsigned long long *diag)
 {
     unsigned long long ts0 = 0, tsa = 0, tsb = 0, tsc = 0, tsd = 0, tse = 0;
     if (diag) ts0 = __builtin_amdgcn_s_memtime();
@@ -475,25 +490,27 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     }
     const int items = nch + (jel > 0 ? 1 : 0);
     if (idx0 >= items) return;
-    const size_t chn = (size_t)chan * N * CBB;
-    double *D = Dall + chn, *E = Eall + chn, *G = Gall + chn;
+    const size_t chn = (size_t)chan * N;                                   // in blocks
+    double *D = Dall + chn * CWD, *E = Eall + chn * CBB, *G = Gall + chn * CBB;
 
     // ---- the operands of phase B, requested now by LDS-DMA (no registers: they land in Wsw while phase A computes; none of them is
-    // written by phase A, which only stores E_{p+1}).  Per item two instructions of 1 KB: D_p and D_{p+1} are neighbours in memory,
-    // E_p goes with the block in front of the window, E_{p-1} (E_p again where there is none). ----
+    // written by phase A, which only stores E_{p+1}).  Per item two instructions: the records of D_p and D_{p+1} are neighbours in
+    // memory, 576 B from lanes 0 .. 35 (the others are masked off: a lane's 16 bytes land at 16 x its number, so the image in Wsw is
+    // the same 576 B); E_p goes with the block in front of the window, E_{p-1} (E_p again where there is none), 1 KB. ----
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         const int idx = idx0 + s;
         const int kd = s >= ipw ? 0 : (idx < nch ? 1 : ((idx == nch && jel > 0) ? 2 : 0));
         if (kd != 0) {                                                   // uniform
             const int jx = kd == 1 ? jlo + idx : jel, p = kd == 2 ? jel - 1 : jx - 2 - (t - 2 * jx);
-            const double *srcD = D + (size_t)p * CBB + 2 * lane;
+            const double *srcD = D + (size_t)p * CWD + 2 * lane;
             const double *srcE = E + (size_t)((lane < 32 || p < 1) ? p : p - 1) * CBB + 2 * (lane & 31);
             // written as assembly: through the builtin the compiler waits for the DMA (vmcnt(0)) before the wave's next LDS operation
             const unsigned ldsD = (unsigned)(size_t)(__attribute__((address_space(3))) void *)(Wsw + s * 4 * CBB);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\t"
-                         "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                         :: "v"(srcD), "v"(srcE), "s"(ldsD), "s"(ldsD + 2 * CBB * 8) : "memory", "m0");
+            unsigned long long ex;                                       // (EXEC by scalar instructions: no wait states towards the DPP steps)
+            asm volatile("s_mov_b32 m0, %3\n\ts_mov_b64 %0, exec\n\ts_bfm_b64 exec, %5, 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+                         "s_mov_b64 exec, %0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off"
+                         : "=&s"(ex) : "v"(srcD), "v"(srcE), "s"(ldsD), "s"(ldsD + 2 * CBB * 8), "i"(CWD) : "memory", "m0");   // CWD lanes: 2 CWD doubles
         }
     }
 
@@ -502,16 +519,24 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     auto read_ws = [&]() {
         const int g = lane >> 4, c8 = lane & 7;
         const bool left = (lane & 15) < CB;
+        // a slot's image: the records of D_p and D_{p+1} at 0 and CWD, E_p at 2 CBB, E_{p-1} at 3 CBB.  The lane's places, once for the four slots:
+        int oa[2], ob[2], om[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int R = 4 * r + g;
+            const int hi = R > c8 ? R : c8, lo = R > c8 ? c8 : R;
+            oa[r] = left ? cw_pk(hi, lo) : 2 * CBB + c8 * CB + R;
+            ob[r] = left ? 2 * CBB + R * CB + c8 : CWD + cw_pk(hi, lo);
+            om[r] = 3 * CBB + R * CB + c8;
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const double *W0 = Wsw + s * 4 * CBB, *W1 = W0 + CBB, *WE = W0 + 2 * CBB, *WM = W0 + 3 * CBB;
+            const double *W0 = Wsw + s * 4 * CBB;
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const int R = 4 * r + g;
-                const int hi = R > c8 ? R : c8, lo = R > c8 ? c8 : R;
-                wv[s][r] = *(left ? W0 + hi * CB + lo : WE + c8 * CB + R);
-                wv[s][r + 2] = *(left ? WE + R * CB + c8 : W1 + hi * CB + lo);
-                sdv[s][r] = WM[(4 * r + g) * CB + c8];
+                wv[s][r] = W0[oa[r]];
+                wv[s][r + 2] = W0[ob[r]];
+                sdv[s][r] = W0[om[r]];
             }
         }
     };
@@ -586,7 +611,8 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     int idx0b = idx0;
     size_t chnb = chn;
     asm volatile("" : "+s"(idx0b), "+s"(chnb));
-    D = Dall + chnb; E = Eall + chnb; G = Gall + chnb;
+    D = Dall + chnb * CWD; E = Eall + chnb * CBB; G = Gall + chnb * CBB;
+    double *U0 = Uall + (size_t)chan * CWU;
 
     // ---- phase B: the congruences, one item at a time, in the layout of the matrix cores.  The operands of all four items are
     // requested before the first product (a slot without an item reads slot 0's addresses and is skipped): one round trip to
@@ -594,6 +620,16 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     const int g = lane >> 4, c = lane & 15, c8 = c & 7;
     const bool left = c < CB;
     int kind[4], jj[4], pp[4];                                           // kind: 0 none, 1 chase, 2 elimination
+    // where the lane's two elements of the window's diagonal blocks go: a lane of the left half holds (4 r + g, c8) of D_p, one of
+    // the right half that of D_{p+1}.  Row >= column: into the records, one run of 2 CWD doubles from D_p (one store under one mask
+    // for both halves).  The others are not stored -- except block 0's, which go to the side array.
+    int dk[2];
+    bool low[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        low[r] = 4 * r + g >= c8;
+        dk[r] = (left ? 0 : CWD) + cw_pk(4 * r + g, c8);                 // (used under low[r] only)
+    }
     double qe[4], xt[2] = {0.0, 0.0};
     if constexpr (!BCAST) read_ws();
 #pragma unroll
@@ -628,7 +664,7 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
         if (kind[s] == 0) break;
         const bool elim = kind[s] == 2;
         const int p = pp[s];
-        double *D0 = D + (size_t)p * CBB, *D1 = D0 + CBB, *E0 = E + (size_t)p * CBB;
+        double *D0 = D + (size_t)p * CWD, *E0 = E + (size_t)p * CBB;
         double q[4];
         if (!elim) {
             const double *qs = Qsw + s * (16 * QLD);
@@ -646,22 +682,29 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
         double4_t O = {0.0, 0.0, 0.0, 0.0};
         O = cw_mfma(q[0], sdv[s][0], O);
         O = cw_mfma(q[1], sdv[s][1], O);
+        // The results as scalars the compiler cannot see through: (1) left ? Wn[r] : Wn[r + 2] as a select between vector elements
+        // becomes an element picked by a computed index, a chain of six selects; (2) the products of O stay in front of the first
+        // masked store, among the other products -- behind it they wait for nothing but themselves, once per item.
+        double wd[4] = {Wn[0], Wn[1], Wn[2], Wn[3]}, od[4] = {O[0], O[1], O[2], O[3]};
+        asm("" : "+v"(wd[0]), "+v"(wd[1]), "+v"(wd[2]), "+v"(wd[3]), "+v"(od[0]), "+v"(od[1]), "+v"(od[2]), "+v"(od[3]));
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            if (low[r]) D0[dk[r]] = left ? wd[r] : wd[r + 2];
         if (left) {
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                D0[(4 * r + g) * CB + c8] = Wn[r];
-                E0[(4 * r + g) * CB + c8] = Wn[r + 2];
-            }
-        } else {
+            for (int r = 0; r < 2; ++r) E0[(4 * r + g) * CB + c8] = wd[r + 2];
+        }
+        if (p == 0) {                                                    // uniform, one item of a wavefront
 #pragma unroll
-            for (int r = 0; r < 2; ++r) D1[(4 * r + g) * CB + c8] = Wn[r + 2];
+            for (int r = 0; r < 2; ++r)
+                if (left && !low[r]) U0[cw_up(4 * r + g, c8)] = wd[r];
         }
         if (p >= 1 && left) {
             double *Em = E + (size_t)(p - 1) * CBB, *Gm = G + (size_t)(p - 1) * CBB;
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                if (!elim) Em[(4 * r + g) * CB + c8] = O[r];
-                Gm[(4 * r + g) * CB + c8] = O[r + 2];
+                if (!elim) Em[(4 * r + g) * CB + c8] = od[r];
+                Gm[(4 * r + g) * CB + c8] = od[r + 2];
             }
         }
         if (elim && has_x) {
@@ -696,14 +739,15 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
 template <bool ONEDIV, int NW, bool BCAST>
 __global__ __launch_bounds__(64 * NW, (BCAST ? 16 : 8) / NW) void crawford_item4_kernel(int N, int t, int jlo, int nch, int jel, int ipw, int nlh, int qstride,
                                                             int nlead, const double *__restrict__ Qel, double *Dall, double *Eall, double *Gall,
-                                                            unsigned long long *diag)
+                                                            double *Uall, unsigned long long *diag)
 {
     // a launch waits for its slowest wave: the waves of these launches go first on a SIMD they share with a long-running wave of
     // another kernel (the consumed eigenvector's workgroup if it was not given a CU of its own, BSP_VEC_OWN_CU=0: it has 60 ms to spare)
     __builtin_amdgcn_s_setprio(3);
     // BSP_CW_DIAG: s_memtime stamps of a wave's phases, summed over the waves of every launch (diag[0..6] ticks, diag[7] waves)
     if (diag && (((blockIdx.x & 7) | (blockIdx.y & 7)) != 0)) diag = nullptr;   // one wave in 64 reports (the sums are atomics)
-    // per wave and item slot: Q, row-major, stride QLD; the row that goes round; D_p, D_{p+1}, E_p, E_{p-1} (phase B's operands).
+    // per wave and item slot: Q, row-major, stride QLD; the row that goes round; phase B's operands: the records of D_p and D_{p+1}
+    // (2 CWD doubles in the slot's first 2 CBB), E_p, E_{p-1}.
     // BCAST: no row goes round, and Q takes the place of phase B's operands once they are in registers: 9 KB per wave, not 17.5
     __shared__ __attribute__((aligned(16))) double Qs[NW][4][16 * QLD];
     __shared__ __attribute__((aligned(16))) double Bc[BCAST ? 1 : NW][BCAST ? 1 : 4][BCAST ? 2 : 16];
@@ -716,7 +760,7 @@ __global__ __launch_bounds__(64 * NW, (BCAST ? 16 : 8) / NW) void crawford_item4
     // sits in: the choice changes no bit (tests/test_gpu_solve.py::test_band_route_properties).
     cw_quad<ONEDIV, BCAST>(N, t, jlo, nch, jel, ipw, nlh, qstride, nlead, (int)blockIdx.y, (blockIdx.x * NW + wave) * ipw, lane,
                            &Qs[wave][0][0], BCAST ? nullptr : &Bc[wave][0][0], Wsw + wave * (BCAST ? 4 * 16 * QLD : 4 * 4 * CBB), Qel, Dall,
-                           Eall, Gall, diag);
+                           Eall, Gall, Uall, diag);
 }
 
 // index-reversed overlap band: SBf[d][i] = S_f(i, i + d) = S(n-1-i-d, n-1-i)
@@ -781,12 +825,13 @@ __global__ __launch_bounds__(64) void crawford_setup_kernel(int n, int k, int fs
 }
 
 // D_p, E_p of the index-reversed H_l (upper band HB[d][i] = H(i, i + d)); block 0 is taken through step 0 of the
-// elimination here: D_0 <- Li_0 D_0 Li_0^T, E_0 <- E_0 Li_0^T.  grid = (N, channels), one wave per block pair.
+// elimination here: D_0 <- Li_0 D_0 Li_0^T, E_0 <- E_0 Li_0^T (both triangles as this product gives them: the upper one to Uall).
+// grid = (N, channels), one wave per block pair.
 // Run from both ends (nlh < number of channels in the grid): channel blockIdx.y >= nlh is the LEADING part of the pencil of channel
 // blockIdx.y - nlh in the original order, with Li_0 of the overlap's own factor (LiB + listride); N is the stride of a channel in
 // blocks (the grid has the blocks of a half).
 __global__ __launch_bounds__(64) void crawford_init_kernel(int n, int k, int N, int nlh, int listride, const double *__restrict__ HBall,
-                                                          const double *__restrict__ LiB, double *Dall, double *Eall)
+                                                          const double *__restrict__ LiB, double *Dall, double *Eall, double *Uall)
 {
     __shared__ double Ds[CB][CB + 1], Es[CB][CB + 1], Ls[CB][CB + 1], Ts[CB][CB + 1];
     const int p = blockIdx.x, t = threadIdx.x, r = t >> 3, c = t & 7, b = k - 1;
@@ -810,9 +855,10 @@ __global__ __launch_bounds__(64) void crawford_init_kernel(int n, int k, int N, 
         for (int kk = 0; kk < CB; ++kk) s += Ts[r][kk] * Ls[c][kk];
         dv = s; ev = e2;
     }
-    const size_t o = ((size_t)blockIdx.y * N + p) * CBB + t;
-    Dall[o] = dv;
-    Eall[o] = ev;
+    const size_t o = (size_t)blockIdx.y * N + p;
+    if (r >= c) Dall[o * CWD + cw_pk(r, c)] = dv;                          // (p > 0: the upper triangle is the lower one's mirror image)
+    else if (p == 0) Uall[(size_t)blockIdx.y * CWU + cw_up(r, c)] = dv;
+    Eall[o * CBB + t] = ev;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -909,7 +955,7 @@ __global__ __launch_bounds__(64) void crawford_cut_prep_kernel(int N, int Nh, in
 {
     __shared__ double X[CB][CB + 1], Lf[CB][CB + 1];
     const int t = threadIdx.x, r = t >> 3, c = t & 7;
-    const size_t c0 = (size_t)blockIdx.x * N * CBB, c1 = (size_t)(nl + blockIdx.x) * N * CBB;
+    const size_t b0 = (size_t)blockIdx.x * N, b1 = (size_t)(nl + blockIdx.x) * N, c0 = b0 * CBB, c1 = b1 * CBB;
     const double *L1 = LiB + (size_t)Nfull * CBB + (size_t)(Nl - 1) * CBB;
     X[r][c] = Eall[c0 + (size_t)(Nh - 1) * CBB + t];
     Lf[r][c] = L1[(CB - 1 - r) * CB + (CB - 1 - c)];
@@ -918,7 +964,8 @@ __global__ __launch_bounds__(64) void crawford_cut_prep_kernel(int N, int Nh, in
 #pragma unroll
     for (int q = 0; q < CB; ++q) v += Lf[r][q] * X[q][c];
     Eall[c0 + (size_t)(Nh - 1) * CBB + t] = v;
-    Dall[c0 + (size_t)Nh * CBB + t] = Dall[c1 + (size_t)(Nl - 1) * CBB + (CB - 1 - r) * CB + (CB - 1 - c)];
+    // the flipped block's lower triangle is the source's upper one: its mirror image from the record (equal to rounding, not to the bit)
+    if (r >= c) Dall[(b0 + Nh) * CWD + cw_pk(r, c)] = Dall[(b1 + Nl - 1) * CWD + cw_pk(CB - 1 - c, CB - 1 - r)];
     Eall[c0 + (size_t)Nh * CBB + t] = Eall[c1 + (size_t)(Nl - 2) * CBB + (CB - 1 - c) * CB + (CB - 1 - r)];
 }
 
@@ -938,14 +985,17 @@ __device__ __forceinline__ double cw_rdl(double x, int l)
     r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
     return r.d;
 }
-__global__ __launch_bounds__(64) void crawford_corner_kernel(int N, double *__restrict__ Dall, double *__restrict__ Eall)
+__global__ __launch_bounds__(64) void crawford_corner_kernel(int N, double *__restrict__ Dall, double *__restrict__ Eall,
+                                                            const double *__restrict__ Uall)
 {
     const int lane = threadIdx.x, i = lane & 7;
     const bool isE = lane < 8, isD = lane >= 8 && lane < 16;
-    double *rowp = (isE ? Eall : Dall) + (size_t)blockIdx.x * N * CBB + i * CB;
+    double *rowE = Eall + (size_t)blockIdx.x * N * CBB + i * CB, *recD = Dall + (size_t)blockIdx.x * N * CWD;
+    const double *upD = Uall + (size_t)blockIdx.x * CWU;
     double a[CB];
+    // row i of D_0 as the congruences left it: up to the diagonal from the record, beyond it from the side array
 #pragma unroll
-    for (int c = 0; c < CB; ++c) a[c] = (isE || isD) ? rowp[c] : 0.0;
+    for (int c = 0; c < CB; ++c) a[c] = isE ? rowE[c] : (isD ? (c <= i ? recD[cw_pk(i, c)] : upD[cw_up(i, c)]) : 0.0);
 #pragma unroll
     for (int r = CB - 1; r >= 1; --r) {
         // the reflector H = I - tau v v^T on columns 0 .. r that leaves row r of E_0 as (0 .. 0, beta, *)
@@ -984,9 +1034,10 @@ __global__ __launch_bounds__(64) void crawford_corner_kernel(int N, double *__re
             if (isD) a[c] = fma(-tau * vi, y, a[c]);
         }
     }
-    if (isE || isD) {
 #pragma unroll
-        for (int c = 0; c < CB; ++c) rowp[c] = a[c];
+    for (int c = 0; c < CB; ++c) {
+        if (isE) rowE[c] = a[c];
+        else if (isD && c <= i) recD[cw_pk(i, c)] = a[c];                  // nothing reads D_0's upper triangle from here on
     }
 }
 
@@ -1007,15 +1058,15 @@ __global__ void crawford_band_kernel(int n, int npad, int N, int hw, int Nh, int
         const int P = ihi >> 3, Pc = ilo >> 3;                             // P - Pc = 2 (d >= 9 only): outside the block tridiagonal
         const int rr = ihi & 7, cc = ilo & 7;
         if (Nh == 0) {
-            const double *blk = (P == Pc ? Dall : Eall) + (ch * N + Pc) * CBB;
-            v = (P - Pc <= 1) ? blk[rr * CB + cc] : 0.0;
+            if (P == Pc) v = Dall[(ch * N + Pc) * CWD + cw_pk(rr, cc)];
+            else if (P - Pc == 1) v = Eall[(ch * N + Pc) * CBB + rr * CB + cc];
         } else if (P - Pc <= 1) {
             // run from both ends: blocks 0 .. Nh (diagonal) / 0 .. Nh (sub-diagonal) of the reversed numbering from the trailing part's
             // arrays, the others from the leading part's (channel nl + ch), flipped: reversed block P is its block Ntot - 1 - P
-            const double *t0 = (P == Pc ? Dall : Eall) + ch * N * CBB, *t1 = (P == Pc ? Dall : Eall) + (nl + ch) * N * CBB;
-            if (Pc <= Nh) v = t0[(size_t)Pc * CBB + rr * CB + cc];
-            else if (P == Pc) v = t1[(size_t)(Ntot - 1 - P) * CBB + (CB - 1 - cc) * CB + (CB - 1 - rr)];   // its lower triangle
-            else v = t1[(size_t)(Ntot - 2 - Pc) * CBB + (CB - 1 - cc) * CB + (CB - 1 - rr)];
+            const size_t b0 = ch * N, b1 = (nl + ch) * N;
+            if (P == Pc) v = Pc <= Nh ? Dall[(b0 + Pc) * CWD + cw_pk(rr, cc)]
+                                      : Dall[(b1 + Ntot - 1 - P) * CWD + cw_pk(CB - 1 - cc, CB - 1 - rr)];   // its lower triangle
+            else v = Pc <= Nh ? Eall[(b0 + Pc) * CBB + rr * CB + cc] : Eall[(b1 + Ntot - 2 - Pc) * CBB + (CB - 1 - cc) * CB + (CB - 1 - rr)];
         }
     }
     ABall[ch * ab_stride(npad) + (size_t)j * 128 + d] = v;
@@ -1040,7 +1091,8 @@ void crawford_carve(void *base, int n, int k, int nl, CrawfordWork *w)
     w->rdiagf = p; p += 2 * n;
     w->Qel = p; p += 2 * N * 256;
     w->LiB = p; p += 2 * N * CBB;
-    w->D = p; p += (size_t)nl * 2 * (N + 2) * CBB;
+    w->D = p; p += (size_t)nl * 2 * (N + 2) * CBB;                          // carved at a square per block; the records take CWD of every CBB
+    w->U = w->D + (size_t)nl * 2 * (N + 2) * CWD;                          // ... and block 0's upper triangles, [2 nl][CWU], the first of the rest
     w->E = p; p += (size_t)nl * 2 * (N + 2) * CBB;
     w->G = p; p += (size_t)nl * 2 * (N + 2) * CBB;
     w->info = reinterpret_cast<int *>(p);
@@ -1130,7 +1182,7 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
     const int ccb = cw_chunk_cols(n) / CB;                                 // blocks per chunk
     int waited = 0;
     if (evc) BSP_HIP(hipStreamWaitEvent(st, evc[0], 0));
-    hipLaunchKernelGGL(crawford_init_kernel, dim3(Nproc, ny), dim3(64), 0, st, n, k, Ns, nl, N * CBB, d_HB, w.LiB, w.D, w.E);
+    hipLaunchKernelGGL(crawford_init_kernel, dim3(Nproc, ny), dim3(64), 0, st, n, k, Ns, nl, N * CBB, d_HB, w.LiB, w.D, w.E, w.U);
     BSP_HIP(hipGetLastError());
     const int qstride = N * 256;
     // one wavefront: chase items j = jlo .. jlo + nch - 1 and, if jel > 0, the elimination of step jel, for cy channels
@@ -1142,7 +1194,8 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
     // c0, cy, ws: the channels c0 .. c0 + cy - 1 of the batch, on stream ws
     auto wavefront = [&](int t, int jlo, int nch, int jel, int cy, int c0 = 0, hipStream_t ws = nullptr) {
         if (!ws) ws = st;
-        double *gD = w.D + (size_t)c0 * Ns * CBB, *gE = w.E + (size_t)c0 * Ns * CBB, *gG = w.G + (size_t)c0 * Ns * CBB;
+        double *gD = w.D + (size_t)c0 * Ns * CWD, *gE = w.E + (size_t)c0 * Ns * CBB, *gG = w.G + (size_t)c0 * Ns * CBB;
+        double *gU = w.U + (size_t)c0 * CWU;
         const int items = nch + (jel ? 1 : 0);
         if (opts().cw_items4) {
             const int nw = opts().cw_nw == 4 ? 4 : 1;                      // waves per workgroup (A/B; a wave never talks to another)
@@ -1153,7 +1206,7 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
             const dim3 grid((waves + nw - 1) / nw, cy), block(64 * nw);
             const size_t pad = (size_t)opts().cw_ldspad * 1024;
 #define CW_LAUNCH4(OD, NWV, BC, G, B, LDS)                                                                                           \
-    hipLaunchKernelGGL((crawford_item4_kernel<OD, NWV, BC>), G, B, LDS, ws, Ns, t, jlo, nch, jel, ipw, nl, qstride, nlead, w.Qel, gD, gE, gG, dg)
+    hipLaunchKernelGGL((crawford_item4_kernel<OD, NWV, BC>), G, B, LDS, ws, Ns, t, jlo, nch, jel, ipw, nl, qstride, nlead, w.Qel, gD, gE, gG, gU, dg)
             if (opts().cw_bcast) {
                 if (opts().cw_onediv) CW_LAUNCH4(true, 1, true, dim3(waves, cy), dim3(64), 0);
                 else if (nw == 4) CW_LAUNCH4(false, 4, true, grid, block, 0);
@@ -1166,8 +1219,8 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
 #undef CW_LAUNCH4
         } else {
             const dim3 grid((items + 3) / 4, cy);
-            if (opts().cw_onediv) hipLaunchKernelGGL(crawford_item_kernel<true>, grid, dim3(256), 0, ws, Ns, t, jlo, nch, jel, nl, qstride, nlead, w.Qel, gD, gE, gG);
-            else hipLaunchKernelGGL(crawford_item_kernel<false>, grid, dim3(256), 0, ws, Ns, t, jlo, nch, jel, nl, qstride, nlead, w.Qel, gD, gE, gG);
+            if (opts().cw_onediv) hipLaunchKernelGGL(crawford_item_kernel<true>, grid, dim3(256), 0, ws, Ns, t, jlo, nch, jel, nl, qstride, nlead, w.Qel, gD, gE, gG, gU);
+            else hipLaunchKernelGGL(crawford_item_kernel<false>, grid, dim3(256), 0, ws, Ns, t, jlo, nch, jel, nl, qstride, nlead, w.Qel, gD, gE, gG, gU);
         }
     };
     // wavefront t: eliminations 2 j - 1 = t (1 <= j <= Nproc - 1), chase items 2 j + s = t with 0 <= s <= j - 2, j <= Nproc - 1
@@ -1241,7 +1294,7 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
                 h[2] / wv, h[3] / wv, h[4] / wv, h[5] / wv, h[6] / wv);
     }
     const bool band8 = opts().cw_band8 != 0;
-    if (band8) hipLaunchKernelGGL(crawford_corner_kernel, dim3(ny), dim3(64), 0, st, Ns, w.D, w.E);
+    if (band8) hipLaunchKernelGGL(crawford_corner_kernel, dim3(ny), dim3(64), 0, st, Ns, w.D, w.E, w.U);
     hipLaunchKernelGGL(crawford_band_kernel, dim3((npad * 32 + 255) / 256, nl), dim3(256), 0, st, n, npad, Ns, band8 ? CB : 2 * CB - 1,
                        Nh, N, nl, w.D, w.E, d_AB);
     BSP_HIP(hipGetLastError());

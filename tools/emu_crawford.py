@@ -1,12 +1,24 @@
 #!/usr/bin/env python3
 """emu_crawford.py -- lane-level NumPy emulation of csrc/crawford.hip (the item kernel's register layouts, DPP row sums,
 bpermute, the operand maps of v_mfma_f64_16x16x4, the wavefront schedule and the set-up kernels), to check the kernel's index
-logic on the CPU before it meets the GPU.  python tools/emu_crawford.py [n k]"""
+logic on the CPU before it meets the GPU.  The diagonal blocks are the kernel's packed records (36 doubles: the lower triangle by
+rows; block 0's strict upper triangle in a side array), E and G squares.  python tools/emu_crawford.py [n k]"""
 import sys
 import numpy as np
 import scipy.linalg as sl
 
 CB = 8
+CWD, CWU = 36, 28                    # a diagonal block's record (packed lower triangle by rows); block 0's strict upper triangle
+
+
+def pk(i, j):                        # (i, j), i >= j, in a record
+    return i * (i + 1) // 2 + j
+
+
+def up(i, j):                        # (i, j), i < j, in block 0's side array
+    return pk(j - 1, i)
+
+
 lane = np.arange(64); g = lane >> 4; c = lane & 15; c8 = c & 7; left = c < 8
 
 
@@ -93,7 +105,7 @@ def rq4(X):
 ITEMS4 = True
 
 
-def item(N, t, idx, jlo, nch, jel, Qel, D, E, G):
+def item(N, t, idx, jlo, nch, jel, Qel, D, E, G, U):
     if idx < nch:
         elim, j = False, jlo + idx; p = j - 2 - (t - 2 * j)
     elif idx == nch and jel > 0:
@@ -105,8 +117,8 @@ def item(N, t, idx, jlo, nch, jel, Qel, D, E, G):
     for r in range(2):
         R = 4 * r + g
         hi = np.maximum(R, c8); lo = np.minimum(R, c8)
-        w[r] = np.where(left, D0[hi * CB + lo], E0[c8 * CB + R])
-        w[r + 2] = np.where(left, E0[R * CB + c8], D1[hi * CB + lo])
+        w[r] = np.where(left, D0[pk(hi, lo)], E0[c8 * CB + R])          # the D window: records of 36, lower triangles only
+        w[r + 2] = np.where(left, E0[R * CB + c8], D1[pk(hi, lo)])
     side = p >= 1
     Em = E[p - 1] if side else E[0]
     for r in range(2):
@@ -138,10 +150,14 @@ def item(N, t, idx, jlo, nch, jel, Qel, D, E, G):
     for r in range(4): Wn = mfma(q[r], P[r], Wn)
     O = mfma(q[0], sd[0], O); O = mfma(q[1], sd[1], O)
     for r in range(2):
-        idxs = (4 * r + g) * CB + c8
-        D0[idxs[left]] = Wn[r][left]
+        R = 4 * r + g
+        idxs = R * CB + c8
+        low = R >= c8
+        D0[pk(R, c8)[left & low]] = Wn[r][left & low]
+        if p == 0:                                                       # block 0 keeps its upper triangle, beside the records
+            U[up(R, c8)[left & ~low]] = Wn[r][left & ~low]
         E0[idxs[left]] = Wn[r + 2][left]
-        D1[idxs[~left]] = Wn[r + 2][~left]
+        D1[pk(R, c8)[~left & low]] = Wn[r + 2][~left & low]
     if side:
         for r in range(2):
             idxs = (4 * r + g) * CB + c8
@@ -191,27 +207,34 @@ def run(SB, HB):
     def Hf(i, i2):
         hi = max(i, i2); d = hi - min(i, i2)
         return HB[d, n - 1 - hi] if (hi < n and d <= b) else 0.0
-    D = np.zeros((N, 64)); E = np.zeros((N, 64)); G = np.full((N, 64), np.nan)
+    D = np.full((N, CWD), np.nan); E = np.zeros((N, 64)); G = np.full((N, 64), np.nan); U = np.full(CWU, np.nan)
+    Li0 = LiB[0].reshape(8, 8)
     for p in range(N):
+        Dp = np.array([[Hf(CB * p + r, CB * p + cc) for cc in range(8)] for r in range(8)])
+        if p == 0:
+            Dp = Li0 @ Dp @ Li0.T
         for r in range(8):
             for cc in range(8):
-                D[p, r * 8 + cc] = Hf(CB * p + r, CB * p + cc); E[p, r * 8 + cc] = Hf(CB * (p + 1) + r, CB * p + cc)
-    Li0 = LiB[0].reshape(8, 8)
-    D[0] = (Li0 @ D[0].reshape(8, 8) @ Li0.T).reshape(-1); E[0] = (E[0].reshape(8, 8) @ Li0.T).reshape(-1)
+                if r >= cc: D[p, pk(r, cc)] = Dp[r, cc]
+                elif p == 0: U[up(r, cc)] = Dp[r, cc]
+                E[p, r * 8 + cc] = Hf(CB * (p + 1) + r, CB * p + cc)
+    E[0] = (E[0].reshape(8, 8) @ Li0.T).reshape(-1)
     tmax = 3 * N - 5 if N >= 3 else (1 if N == 2 else 0)
     for t in range(1, tmax + 1):
         jel = (t + 1) // 2 if (t & 1) and (t + 1) // 2 <= N - 1 else 0
         jlo = (t + 4) // 3; jhi = min(t // 2, N - 1)
         nch = jhi - jlo + 1 if (jhi >= jlo and jlo >= 2) else 0
         for idx in range(nch + (1 if jel else 0)):
-            item(N, t, idx, jlo, nch, jel, Qel, D, E, G)
+            item(N, t, idx, jlo, nch, jel, Qel, D, E, G, U)
+    assert not np.isnan(D).any() and not np.isnan(U).any()
     A = np.zeros((n, n))                         # band in the ORIGINAL order, as crawford_band_kernel writes it
     for jj in range(n):
         for d in range(16):
             if jj + d < n:
                 ihi = n - 1 - jj; ilo = ihi - d; P = ihi >> 3; Pc = ilo >> 3
-                blk = D[Pc] if P == Pc else E[Pc]
-                v = blk[(ihi & 7) * 8 + (ilo & 7)] if P - Pc <= 1 else 0.0
+                if P == Pc: v = D[Pc][pk(ihi & 7, ilo & 7)]
+                elif P - Pc == 1: v = E[Pc][(ihi & 7) * 8 + (ilo & 7)]
+                else: v = 0.0
                 A[jj + d, jj] = v; A[jj, jj + d] = v
     return A
 
