@@ -278,8 +278,7 @@ int launch_dipole_bands(int nfun, int k, int ka, int nkp, const double *d_ptab, 
     if (TI < 4) return BSP_ERR_UNSUPPORTED;
     static bool attr = false;
     if (!attr) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dipole_band_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(allow_lds(dipole_band_kernel, 150 * 1024));
         attr = true;
     }
     hipLaunchKernelGGL(dipole_band_kernel, dim3((nfun + TI - 1) / TI), dim3(256), lds, st, TI, nfun, k, ka, nkp, d_ptab, d_left,
@@ -314,8 +313,7 @@ int launch_assemble_bands(int nfun, int k, int ka, int nkp, int kind_pot, const 
     if (TI < 4) return BSP_ERR_ARG;
     static bool attr_set = false;
     if (!attr_set) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(band_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(allow_lds(band_kernel, 150 * 1024));
         attr_set = true;
     }
     // channels are split over grid.y in chunks of BAND_LCH so that one launch fills the chip

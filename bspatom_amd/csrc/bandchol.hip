@@ -10,6 +10,7 @@
 // npad = n rounded up to a multiple of 64: rows/cols >= n of C are zero (L is extended by the
 // identity there), which keeps the later stages free of edge cases.
 #include "common.h"
+#include "wave_ops.h"
 
 namespace bsp {
 
@@ -69,11 +70,7 @@ __global__ __launch_bounds__(64) void band_cholesky_kernel(int n, int k, int jst
             for (int q = BMAX; q >= 1; --q)                              // rows j - b .. j - 1 in this order: the first version's sum, bit for bit
                 if (q <= b) s = fma(-av[q - 1], (q + t <= b) ? bv[q - 1] : 0.0, s);
             // lane 0 holds the pivot
-            union { double d; int i[2]; } u, r;
-            u.d = s;
-            r.i[0] = __builtin_amdgcn_readfirstlane(u.i[0]);
-            r.i[1] = __builtin_amdgcn_readfirstlane(u.i[1]);
-            const double piv = r.d;
+            const double piv = read_first_lane(s);
             if (!(piv > 0.0) && bad == 0) { bad = 1; if (t == 0 && *info == 0) *info = j + 1; }   // minor j+1 not PD (the first one, over all launches)
             const double dj = sqrt(piv);
             double uv = (t == 0) ? dj : s / dj;

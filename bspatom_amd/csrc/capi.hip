@@ -21,6 +21,42 @@ int process_device_check(int device)
     return BSP_OK;
 }
 void process_device_latch(int device) { int expect = -1; g_process_device.compare_exchange_strong(expect, device); }
+
+int device_cus()
+{
+    static const int cus = [] {
+        int dev = 0, v = 0;
+        return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+    }();
+    return cus;
+}
+
+// ---- LaunchCtx (common.h) -------------------------------------------------------------------------------
+hipError_t LaunchCtx::sync()
+{
+    hipError_t first = hipSuccess;
+    auto wait = [&](hipStream_t s) {
+        const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess;
+        if (first == hipSuccess) first = e;
+    };
+    for (hipStream_t s : cw_aux) wait(s);
+    for (const Sy2sbLane &ln : lanes) { wait(ln.main); wait(ln.side); }
+    return first;
+}
+
+void LaunchCtx::release()
+{
+    (void)sync();
+    auto drop_stream = [](hipStream_t &s) { if (s) (void)hipStreamDestroy(s); s = nullptr; };
+    auto drop_event = [](hipEvent_t &e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
+    for (hipStream_t &s : cw_aux) drop_stream(s);
+    drop_event(cw_fork);
+    for (hipEvent_t &e : cw_join) drop_event(e);
+    for (Sy2sbLane &ln : lanes) { drop_stream(ln.main); drop_stream(ln.side); drop_event(ln.evA); drop_event(ln.evB); drop_event(ln.done); }
+    drop_event(sy_fork);
+    (void)hipFree(bis_tail); (void)hipFree(bis_qcnt); (void)hipFree(sb2st_chk);    // (hipFree waits for the device)
+    bis_tail = nullptr; bis_tail_cap = 0; bis_qcnt = nullptr; sb2st_chk = nullptr;
+}
 }  // namespace bsp
 
 // ---- run-time switches: environment once, then bspatom_set_option ------------------------------------
@@ -234,6 +270,8 @@ extern "C" void bspatom_problem_destroy(bspatom_problem *p)
 {
     if (!p) return;
     hipSetDevice(p->device);
+    if (p->st) (void)hipStreamSynchronize(p->st);
+    p->lc.release();                                        // its streams wait on nothing of p->st's any more
     free_solve_buffers(p);
     hipFree(p->d_rt); hipFree(p->d_aind); hipFree(p->d_xg); hipFree(p->d_wg); hipFree(p->d_vpot);
     hipFree(p->d_bl); hipFree(p->d_ptab); hipFree(p->d_left); hipFree(p->d_status); hipFree(p->d_info);
@@ -293,10 +331,11 @@ extern "C" int bspatom_problem_create(const bspatom_input *in, int device, bspat
         fprintf(stderr, "bspatom: no HIP device %d (libbspatom has no CPU path)\n", device);
         return BSP_ERR_NOGPU;
     }
-    // One process per GPU: the kernels' opt-ins for large LDS, the side streams of sy2sb and the stage-level
-    // scratch buffers are created once per process on the device of the first problem.
+    // One process per GPU.  What is still per process are properties of the device, set or asked once: the kernels'
+    // opt-ins for large LDS (a once-flag beside each), the CU count (device_cus), occupancy figures.  Every stream, event and
+    // scratch block of the launchers belongs to a LaunchCtx (common.h), one per problem, so several problems may be alive at once.
     // The device is latched by the first problem that was created SUCCESSFULLY and stays latched for the life of the process
-    // (those per-process objects live on it); bsp_dsygv_ (dsygv.hip) honours the same latch.
+    // (the once-flags hold for it); bsp_dsygv_ (dsygv.hip) honours the same latch.
     int rc0;
     if ((rc0 = bsp::process_device_check(device))) return rc0;
     bspatom_problem *p = new (std::nothrow) bspatom_problem;
@@ -412,7 +451,7 @@ int pipeline_route(int n, int k)
     return (crawford_supported(n, k) && n >= 32) ? 2 : 1;
 }
 
-int pipeline_enqueue(int n, int npad, int k, int nl, const double *d_SB, const double *d_HB, const PipeBufs &b,
+int pipeline_enqueue(LaunchCtx &cx, int n, int npad, int k, int nl, const double *d_SB, const double *d_HB, const PipeBufs &b,
                      double *d_Eout, hipStream_t st, hipEvent_t *ev, bool with_bisect, bool s_prepared)
 {
     int rc;
@@ -428,13 +467,13 @@ int pipeline_enqueue(int n, int npad, int k, int nl, const double *d_SB, const d
         CrawfordWork cw;
         crawford_carve(b.cwork, n, k, nl, &cw);
         if (ev) BSP_HIP(hipEventRecord(ev[1], st));
-        if ((rc = crawford_run(n, npad, k, nl, d_SB, d_HB, cw, b.AB, st, s_prepared, b.s_events, b.aux0))) return rc;
+        if ((rc = crawford_run(cx, n, npad, k, nl, d_SB, d_HB, cw, b.AB, st, s_prepared, b.s_events))) return rc;
         if (ev) BSP_HIP(hipEventRecord(ev[2], st));
         if (b.chase_after) BSP_HIP(hipStreamWaitEvent(st, b.chase_after, 0));
         if ((rc = launch_sb16st(n, npad, nl, b.AB, b.d, b.e, st, b.status, b.sbctl, opts().cw_band8 ? 8 : 16))) return rc;
         if (ev) BSP_HIP(hipEventRecord(ev[3], st));
         if (!with_bisect) return BSP_OK;
-        if ((rc = launch_bisect(n, npad, nl, b.d, b.e, d_Eout, n, st))) return rc;
+        if ((rc = launch_bisect(cx, n, npad, nl, b.d, b.e, d_Eout, n, st))) return rc;
         if (ev) BSP_HIP(hipEventRecord(ev[4], st));
         return BSP_OK;
     }
@@ -448,13 +487,13 @@ int pipeline_enqueue(int n, int npad, int k, int nl, const double *d_SB, const d
     if (ev) BSP_HIP(hipEventRecord(ev[1], st));
     Sy2sbWork w;
     sy2sb_carve(b.work, npad, 64, nl, &w);
-    if ((rc = sy2sb_run(npad, 64, nl, b.C, w, st))) return rc;
+    if ((rc = sy2sb_run(cx, npad, 64, nl, b.C, w, st))) return rc;
     if ((rc = launch_extract_band(npad, 64, nl, b.C, b.AB, st))) return rc;
     if (ev) BSP_HIP(hipEventRecord(ev[2], st));
-    if ((rc = launch_sb2st(n, npad, 64, nl, b.AB, b.d, b.e, st, b.status, b.sbctl))) return rc;
+    if ((rc = launch_sb2st(cx, n, npad, 64, nl, b.AB, b.d, b.e, st, b.status, b.sbctl))) return rc;
     if (ev) BSP_HIP(hipEventRecord(ev[3], st));
     if (!with_bisect) return BSP_OK;                       // the caller enqueues other work first (see solve_impl)
-    if ((rc = launch_bisect(n, npad, nl, b.d, b.e, d_Eout, n, st))) return rc;
+    if ((rc = launch_bisect(cx, n, npad, nl, b.d, b.e, d_Eout, n, st))) return rc;
     if (ev) BSP_HIP(hipEventRecord(ev[4], st));
     return BSP_OK;
 }
@@ -471,17 +510,13 @@ int bsp::ensure_vec_scratch(bspatom_problem *p)
     return BSP_OK;
 }
 
-static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, double *E_host, int32_t *info)
+// A solve in two parts behind one exit (solve_impl): solve_enqueue puts everything on the streams and waits for p->st, which by then
+// waits for every other stream; solve_collect reads the results back.
+static int solve_enqueue(bspatom_problem *p, int l0, int nl, int route, double *E_dev_out)
 {
-    if (!p || nl <= 0 || l0 < 0) return BSP_ERR_ARG;
-    BSP_HIP(hipSetDevice(p->device));
     const HostSetup &h = p->hs;
     const int n = h.nfun, np = p->npad;
     int rc;
-    if ((rc = ensure_capacity(p, nl))) return rc;
-    const int route = pipeline_route(n, h.k);
-    if ((rc = ensure_route_buffers(p, nl, route))) return rc;
-    p->last_nl = 0; p->band_nl = 0;                          // valid again only when this solve has completed
     BSP_HIP(hipMemsetAsync(p->d_info, 0, sizeof(int), p->st));
     BSP_HIP(hipEventRecord(p->ev[0], p->st));
     // Band route: S is there once the first channel is assembled, and what the reduction does with S alone (the reversed band, its
@@ -534,8 +569,7 @@ static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, dou
         // a CU of its own only where the chase has no CU to spare for it -- more than 32 channels: fewer than eight workgroups per channel
         // or two per CU.  Below that the reduction is over before the vector is, the chase would lose the CU (32 channels: chase 13.9 ->
         // 15.9 ms), and a shared CU has room for both (with 64 channels and a shared CU: chase 16.8 -> 22.5 ms).
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
+        const int cus = device_cus();
         const bool own_cu = opts().vec_own_cu == 2 || (opts().vec_own_cu == 1 && ((nl + 7) / 8) * 8 * 8 > cus);
         BSP_HIP(hipMemsetAsync(p->d_pinfo, 0, sizeof(int), sv));
         if (s_prepared && tl == l0) BSP_HIP(hipStreamWaitEvent(sv, p->evS, 0));     // its channel was assembled first, S with it
@@ -549,9 +583,9 @@ static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, dou
         p->pre_l = tl; p->pre_n0 = tn0; p->pre_early = true;
     }
     PipeBufs pb{p->d_UB, p->d_rdiag, p->d_Y, p->d_C, p->d_AB, p->d_d, p->d_e, p->d_work, p->d_info, p->d_status, p->d_sbctl, p->d_cwork, s_prepared ? p->evC : nullptr,
-                nullptr, (early && opts().vec_early == 3) ? p->evx : nullptr};
+                (early && opts().vec_early == 3) ? p->evx : nullptr};
     double *Eout = E_dev_out ? E_dev_out : p->d_E;
-    if ((rc = pipeline_enqueue(n, np, h.k, nl, p->d_SB, p->d_HB, pb, Eout, p->st, &p->ev[1], false, s_prepared))) return rc;
+    if ((rc = pipeline_enqueue(p->lc, n, np, h.k, nl, p->d_SB, p->d_HB, pb, Eout, p->st, &p->ev[1], false, s_prepared))) return rc;
     if (want_vec && !early) {
         if ((rc = side_stream())) return rc;
         p->pre_ch = tl - l0;
@@ -574,12 +608,20 @@ static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, dou
             p->pre_l = tl; p->pre_n0 = tn0;
         }
     }
-    if ((rc = launch_bisect(n, np, nl, p->d_d, p->d_e, Eout, n, p->st))) return rc;
+    if ((rc = launch_bisect(p->lc, n, np, nl, p->d_d, p->d_e, Eout, n, p->st))) return rc;
     BSP_HIP(hipEventRecord(p->ev[5], p->st));
     if (p->pre_l >= 0) BSP_HIP(hipStreamWaitEvent(p->st, p->evx, 0));
     if (E_dev_out)   // keep a copy for bspatom_eigvec
         BSP_HIP(hipMemcpyAsync(p->d_E, E_dev_out, (size_t)nl * n * sizeof(double), hipMemcpyDeviceToDevice, p->st));
     BSP_HIP(hipStreamSynchronize(p->st));
+    return BSP_OK;
+}
+
+static int solve_collect(bspatom_problem *p, int l0, int nl, int route, double *E_host, int32_t *info)
+{
+    const HostSetup &h = p->hs;
+    const int n = h.nfun, tn0 = h.in.n0_ini;
+    int rc;
     for (int i = 0; i < 5; ++i) {
         float ms = 0.f;
         hipEventElapsedTime(&ms, p->ev[i], p->ev[i + 1]);
@@ -628,6 +670,26 @@ static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, dou
     p->last_l0 = l0; p->last_nl = nl;
     p->band_l0 = l0; p->band_nl = nl;
     return BSP_OK;
+}
+
+static int solve_impl(bspatom_problem *p, int l0, int nl, double *E_dev_out, double *E_host, int32_t *info)
+{
+    if (!p || nl <= 0 || l0 < 0) return BSP_ERR_ARG;
+    BSP_HIP(hipSetDevice(p->device));
+    int rc;
+    if ((rc = ensure_capacity(p, nl))) return rc;
+    const int route = pipeline_route(p->hs.nfun, p->hs.k);
+    if ((rc = ensure_route_buffers(p, nl, route))) return rc;
+    p->last_nl = 0; p->band_nl = 0;                          // valid again only when this solve has completed
+    if (!(rc = solve_enqueue(p, l0, nl, route, E_dev_out))) rc = solve_collect(p, l0, nl, route, E_host, info);
+    if (rc) {
+        // the one exit of a failed solve: nothing of it runs on over d_HB, d_vwork .. once the call has returned
+        (void)hipStreamSynchronize(p->st);
+        if (p->st2) (void)hipStreamSynchronize(p->st2);
+        if (p->stS) (void)hipStreamSynchronize(p->stS);
+        (void)p->lc.sync();
+    }
+    return rc;
 }
 
 extern "C" int bspatom_solve(bspatom_problem *p, int l0, int nl, double *E, int32_t *info)

@@ -11,6 +11,7 @@ struct bspatom_problem {
     bsp::HostSetup hs;
     int device, npad;
     hipStream_t st = nullptr;
+    bsp::LaunchCtx lc;                        // what the launchers of a solve own besides the buffers below (common.h)
     // device: set-up tables
     double *d_rt = nullptr, *d_aind = nullptr, *d_xg = nullptr, *d_wg = nullptr, *d_vpot = nullptr, *d_bl = nullptr;
     double *d_ptab = nullptr; int *d_left = nullptr; int *d_status = nullptr;

@@ -1,5 +1,6 @@
 // capi_stage.hip -- the stage-level entry points of the C ABI (include/bspatom.h: bspatom_stage_*): one kernel stage on host
-// arrays, for the tests.  Each call uploads, runs on the null stream, waits and downloads; nothing here belongs to a problem.
+// arrays, for the tests.  Each call uploads, runs on the null stream, waits and downloads; nothing here belongs to a problem: a call
+// that needs launch-side state holds a LaunchCtx of its own, declared behind its arrays (so it is released, its streams drained, first).
 #include "capi_internal.h"
 
 using namespace bsp;
@@ -79,9 +80,10 @@ extern "C" int bspatom_stage_sy2sb(int npad, int batch, const double *A, double 
     DevArray<char> work;
     if ((rc = dA.put(A, (size_t)batch * npad * npad)) || (rc = dAB.alloc((size_t)batch * ab_stride(npad))) ||
         (rc = work.alloc(sy2sb_work_bytes(npad, 64, batch)))) return rc;
+    LaunchCtx cx;
     Sy2sbWork w;
     sy2sb_carve(work.p, npad, 64, batch, &w);
-    rc = sy2sb_run(npad, 64, batch, dA.p, w, 0);
+    rc = sy2sb_run(cx, npad, 64, batch, dA.p, w, 0);
     if (!rc) rc = launch_extract_band(npad, 64, batch, dA.p, dAB.p, 0);
     const hipError_t e = hipDeviceSynchronize();          // on every path, before the work area is freed
     if (rc) return rc;
@@ -118,9 +120,11 @@ extern "C" int bspatom_stage_sb2st(int n, int npad, int batch, const double *AB,
     int rc;
     if ((rc = need_gpu())) return rc;
     DevArray<double> dAB, dd, de;
+    DevArray<char> ctl;
     if ((rc = dAB.alloc((size_t)batch * ab_stride(npad))) || (rc = copy_band_in(npad, batch, AB, dAB.p)) ||
-        (rc = dd.alloc((size_t)batch * npad)) || (rc = de.alloc((size_t)batch * npad))) return rc;
-    if ((rc = launch_sb2st(n, npad, 64, batch, dAB.p, dd.p, de.p, 0))) return rc;
+        (rc = dd.alloc((size_t)batch * npad)) || (rc = de.alloc((size_t)batch * npad)) || (rc = ctl.alloc(sb2st_ctl_bytes(batch)))) return rc;
+    LaunchCtx cx;
+    if ((rc = launch_sb2st(cx, n, npad, 64, batch, dAB.p, dd.p, de.p, 0, nullptr, ctl.p))) return rc;
     BSP_HIP(hipDeviceSynchronize());
     if ((rc = dd.get(d, (size_t)batch * npad))) return rc;
     return de.get(e, (size_t)batch * npad);
@@ -148,9 +152,10 @@ extern "C" int bspatom_stage_crawford(int n, int k, int nl, const double *SB, co
     if ((rc = dSB.put(SB, (size_t)k * n)) || (rc = dHB.put(HB, (size_t)nl * k * n)) || (rc = dAB.alloc((size_t)nl * ab_stride(npad))) ||
         (rc = dW.alloc(crawford_work_bytes(n, k, nl) / sizeof(double) + 1))) return rc;
     BSP_HIP(hipMemset(dAB.p, 0, (size_t)nl * ab_stride(npad) * sizeof(double)));
+    LaunchCtx cx;
     CrawfordWork cw;
     crawford_carve(dW.p, n, k, nl, &cw);
-    if ((rc = crawford_run(n, npad, k, nl, dSB.p, dHB.p, cw, dAB.p, 0))) return rc;
+    if ((rc = crawford_run(cx, n, npad, k, nl, dSB.p, dHB.p, cw, dAB.p, 0))) return rc;
     BSP_HIP(hipDeviceSynchronize());
     int ci = 0;
     BSP_HIP(hipMemcpy(&ci, cw.info, sizeof(int), hipMemcpyDeviceToHost));
@@ -176,7 +181,8 @@ extern "C" int bspatom_stage_bisect(int n, int batch, const double *d, const dou
     if ((rc = need_gpu())) return rc;
     DevArray<double> dd, de, dw;
     if ((rc = dd.put(d, (size_t)batch * n)) || (rc = de.put(e, (size_t)batch * n)) || (rc = dw.alloc((size_t)batch * n))) return rc;
-    if ((rc = launch_bisect(n, n, batch, dd.p, de.p, dw.p, n, 0))) return rc;
+    LaunchCtx cx;
+    if ((rc = launch_bisect(cx, n, n, batch, dd.p, de.p, dw.p, n, 0))) return rc;
     BSP_HIP(hipDeviceSynchronize());
     return dw.get(w, (size_t)batch * n);
 }

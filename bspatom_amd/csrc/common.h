@@ -124,6 +124,45 @@ Options &opts();
 int process_device();
 int process_device_check(int device);          // BSP_OK, or BSP_ERR_UNSUPPORTED (message on stderr) if another device is latched
 void process_device_latch(int device);
+int device_cus();                              // compute units of the current device, asked once per process (the device is latched); 256 if the query fails
+
+// A kernel's opt-in for `bytes` of dynamic LDS.  A property of the latched device: every caller keeps a once-flag of its own.
+template <class K>
+inline hipError_t allow_lds(K kernel, size_t bytes)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+// ---- launch-side state: the streams, events and small device blocks the launchers need besides the caller's buffers --------
+// One per problem handle (capi_internal.h), one local to every stage-level entry point and to bsp_dsygv_.  Every member is created at
+// first need by the launcher that uses it; release() (and the destructor) waits for the streams it owns before it frees anything.
+// One host thread per problem: nothing here is locked.
+struct Sy2sbLane {                       // one pipeline of sy2sb_run: main + high-priority side stream and their events
+    hipStream_t main = nullptr, side = nullptr;
+    hipEvent_t evA = nullptr, evB = nullptr, done = nullptr;
+};
+constexpr int SY2SB_MAXG = 4;
+struct LaunchCtx {
+    // crawford_run: streams of the further channel groups, fork / join events (re-recorded by every solve)
+    hipStream_t cw_aux[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t cw_fork = nullptr, cw_join[3] = {nullptr, nullptr, nullptr};
+    // sy2sb_run: the lanes and the fork event
+    Sy2sbLane lanes[SY2SB_MAXG];
+    hipEvent_t sy_fork = nullptr;
+    // launch_bisect: rows beyond the LDS (grown on demand), the queue's counters
+    double2 *bis_tail = nullptr;
+    size_t bis_tail_cap = 0;
+    unsigned *bis_qcnt = nullptr;
+    // launch_sb2st: the check word of BSP_SB2ST_CHECK
+    int *sb2st_chk = nullptr;
+
+    LaunchCtx() = default;
+    LaunchCtx(const LaunchCtx &) = delete;
+    LaunchCtx &operator=(const LaunchCtx &) = delete;
+    ~LaunchCtx() { release(); }
+    hipError_t sync();                   // waits for every stream the ctx owns; the first error
+    void release();                      // sync(), then destroys / frees everything; the ctx is as new afterwards
+};
 
 // ---- per-kernel launch timing (off unless opts().ktime) --------------------------------------------
 // Two events per launch, recorded on the launch's own stream; bspatom_kernel_times() sums the elapsed times per slot after
@@ -210,8 +249,8 @@ void crawford_carve(void *base, int n, int k, int nl, CrawfordWork *w);
 // rest of the factor is still being computed (without them the caller orders the run behind the whole of it)
 constexpr int CW_CHUNKS = 4;
 int crawford_prepare(int n, int k, const double *d_SB, const CrawfordWork &w, hipStream_t st, hipEvent_t *evc = nullptr);
-int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const double *d_HB, const CrawfordWork &w, double *d_AB,
-                 hipStream_t st, bool s_prepared = false, hipEvent_t *evc = nullptr, hipStream_t aux0 = nullptr);
+int crawford_run(LaunchCtx &cx, int n, int npad, int k, int nl, const double *d_SB, const double *d_HB, const CrawfordWork &w, double *d_AB,
+                 hipStream_t st, bool s_prepared = false, hipEvent_t *evc = nullptr);
 // sy2sb.hip
 // tsqr.hip: panel factorisation on many workgroups (TSQR + Householder reconstruction), BSP_PANEL_QR=3
 long tsqr_scr_doubles(int npad);
@@ -233,22 +272,19 @@ struct Sy2sbWork {
 constexpr int SY2SB_SPLITK = 16;
 size_t sy2sb_work_bytes(int npad, int nb, int batch);
 void sy2sb_carve(void *base, int npad, int nb, int batch, Sy2sbWork *w);
-int sy2sb_run(int npad, int nb, int batch, double *d_A, const Sy2sbWork &w, hipStream_t st);
+int sy2sb_run(LaunchCtx &cx, int npad, int nb, int batch, double *d_A, const Sy2sbWork &w, hipStream_t st);
 int sy2sb_panel_only(int npad, int c0, int batch, double *d_A, const Sy2sbWork &w, hipStream_t st);
 int launch_extract_band(int npad, int nb, int batch, const double *d_A, double *d_AB, hipStream_t st);
 // sb2st.hip
-// ctl: device scratch of sb2st_ctl_bytes(batch) bytes owned by the caller (per problem); nullptr -> a
-// process-wide buffer (stage-level entry points only).
+// ctl: device scratch of sb2st_ctl_bytes(batch) bytes owned by the caller (per problem)
 size_t sb2st_ctl_bytes(int batch);
 // two-step route (sbr2.hip): band 64 -> 16 by block bulge chasing, then 16 -> tridiagonal in an LDS window
 int launch_sb2sb(int n, int npad, int batch, double *d_AB, hipStream_t st);
-int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double *d_e, hipStream_t st, int *d_status = nullptr,
-                  void *ctl = nullptr, int hb = 16);
-int launch_sb2st(int n, int npad, int b, int batch, double *d_AB, double *d_d, double *d_e,
-                 hipStream_t st, int *d_status = nullptr, void *ctl = nullptr);
+int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double *d_e, hipStream_t st, int *d_status, void *ctl, int hb = 16);
+int launch_sb2st(LaunchCtx &cx, int n, int npad, int b, int batch, double *d_AB, double *d_d, double *d_e, hipStream_t st, int *d_status,
+                 void *ctl);
 // tridiag.hip
-int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_e, double *d_w,
-                  long ldw, hipStream_t st);
+int launch_bisect(LaunchCtx &cx, int n, int ldn, int batch, const double *d_d, const double *d_e, double *d_w, long ldw, hipStream_t st);
 int launch_bisect_one(int n, const double *d_d, const double *d_e, int m, double *d_out, hipStream_t st);
 // bandsect.hip: eigenvalue m (0-based, ascending) of the banded pencil itself (upper bands, k - 1 <= 8), one workgroup
 int launch_band_multisect(int n, int k, const double *d_SB, const double *d_HB, int m, double *d_out, hipStream_t st);
@@ -402,13 +438,12 @@ struct PipeBufs {
     void *sbctl = nullptr;   // sb2st pairing/progress control block (sb2st_ctl_bytes(nl))
     void *cwork = nullptr;   // band route: crawford_work_bytes(n, k, nl); Y, C, work may be null when only that route runs
     hipEvent_t *s_events = nullptr;   // band route, S-only part already enqueued elsewhere (s_prepared): CW_CHUNKS events, see crawford_prepare
-    hipStream_t aux0 = nullptr;       // band route: the caller's stream for the reduction's second group of channels (crawford_run)
     hipEvent_t chase_after = nullptr; // band route: the chase waits for this event (the early vector's kernels hold LDS two workgroups of the chase need)
 };
 // 1 = dense route, 2 = band route, for a pencil of this size under the current switches (BSP_ROUTE)
 int pipeline_route(int n, int k);
 size_t pipe_bytes_per_channel(int npad);
-int pipeline_enqueue(int n, int npad, int k, int nl, const double *d_SB, const double *d_HB,
+int pipeline_enqueue(LaunchCtx &cx, int n, int npad, int k, int nl, const double *d_SB, const double *d_HB,
                      const PipeBufs &b, double *d_Eout, hipStream_t st, hipEvent_t *ev, bool with_bisect = true, bool s_prepared = false);
 
 }  // namespace bsp

@@ -31,8 +31,8 @@
 // next to zero lose a factor of 50 at l = 14 (0.015 against 0.0003 eps lambda_max, measured against 113-bit truth by the
 // prototype).  The band handed to the tridiagonalisation is stored in the original order again.
 #include "common.h"
+#include "wave_ops.h"
 #include <cstdio>
-#include <mutex>
 
 namespace bsp {
 namespace {
@@ -50,41 +50,7 @@ __host__ __device__ constexpr int cw_pk(int i, int j) { return i * (i + 1) / 2 +
 __host__ __device__ constexpr int cw_up(int i, int j) { return cw_pk(j - 1, i); }       // (i, j), i < j, in block 0's side array
 static_assert(cw_pk(CB - 1, CB - 1) == CWD - 1 && cw_up(CB - 2, CB - 1) == CWU - 1, "the last places of the two triangles");
 
-template <int CTRL>
-__device__ __forceinline__ double cw_dpp(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-// sum over the 16 lanes of a DPP row, the same bits in every lane (a butterfly of commutative additions)
-__device__ __forceinline__ double cw_rowsum(double x)
-{
-    x += cw_dpp<0x128>(x);         // row_ror:8
-    x += cw_dpp<0x124>(x);
-    x += cw_dpp<0x122>(x);
-    x += cw_dpp<0x121>(x);
-    return x;
-}
-__device__ __forceinline__ double cw_bperm(double x, int srclane)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_ds_bpermute(srclane << 2, u.i[0]);
-    r.i[1] = __builtin_amdgcn_ds_bpermute(srclane << 2, u.i[1]);
-    return r.d;
-}
-template <int L>
-__device__ __forceinline__ double cw_lane(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], L);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], L);
-    return r.d;
-}
+// (cw_rowsum, the sum over the 16 lanes of a DPP row by row_ror 8, 4, 2, 1: wave_ops.h.)
 
 // One step of the RQ factorisation of X = [F E] (8 x 16; x0: rows 0-3, x1: rows 4-7; lane (g, c) holds rows g and 4 + g at
 // column c): the reflector H = I - t u u^T on columns 0 .. 8 + I that leaves row I as (0 .. 0, beta, *), applied to the rows
@@ -102,9 +68,9 @@ __device__ __forceinline__ void rq_step(double &x0, double &x1, double (&q)[4], 
 {
     constexpr int LEN = CB + I, GI = I & 3;
     double &xr = (I < 4) ? x0 : x1;
-    const double xi = cw_bperm(xr, GI * 16 + c);                       // row I in every DPP row
+    const double xi = bpermute(xr, GI * 16 + c);                       // row I in every DPP row
     const double sig = cw_rowsum(c < LEN ? xi * xi : 0.0);
-    const double alpha = cw_lane<LEN>(xi);
+    const double alpha = read_lane(xi, LEN);
     const double a2s = fma(alpha, alpha, sig);
     const bool ok = (a2s > 1e-280) && (sig != 0.0);                    // nothing (numerically) left of the pivot: H = I
     const double nrm = sqrt(ok ? a2s : 1.0);
@@ -977,14 +943,6 @@ __global__ __launch_bounds__(64) void crawford_cut_prep_kernel(int N, int Nh, in
 // half-width CB except for E_0, which the last item of every sweep leaves full.  One more RQ, E_0 = R Q^T, D_0 <- Q^T D_0 Q (block 0
 // touches nothing else), and the chase that follows works on a band of half-width 8 instead of 15.  One wave per channel: lane
 // i < 8 holds row i of E_0, lane 8 + i row i of D_0.
-__device__ __forceinline__ double cw_rdl(double x, int l)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
-    return r.d;
-}
 __global__ __launch_bounds__(64) void crawford_corner_kernel(int N, double *__restrict__ Dall, double *__restrict__ Eall,
                                                             const double *__restrict__ Uall)
 {
@@ -1001,7 +959,7 @@ __global__ __launch_bounds__(64) void crawford_corner_kernel(int N, double *__re
         // the reflector H = I - tau v v^T on columns 0 .. r that leaves row r of E_0 as (0 .. 0, beta, *)
         double v[CB], nrm2 = 0.0;
 #pragma unroll
-        for (int c = 0; c < CB; ++c) v[c] = c <= r ? cw_rdl(a[c], r) : 0.0;
+        for (int c = 0; c < CB; ++c) v[c] = c <= r ? read_lane(a[c], r) : 0.0;
 #pragma unroll
         for (int c = 0; c < r; ++c) nrm2 = fma(v[c], v[c], nrm2);
         if (nrm2 == 0.0) continue;                                         // uniform: the row is in shape already
@@ -1030,7 +988,7 @@ __global__ __launch_bounds__(64) void crawford_corner_kernel(int N, double *__re
         for (int c = 0; c < CB; ++c) {
             double y = 0.0;
 #pragma unroll
-            for (int q = 0; q <= r; ++q) y = fma(v[q], cw_rdl(a[c], CB + q), y);
+            for (int q = 0; q <= r; ++q) y = fma(v[q], read_lane(a[c], CB + q), y);
             if (isD) a[c] = fma(-tau * vi, y, a[c]);
         }
     }
@@ -1159,19 +1117,13 @@ int crawford_prepare(int n, int k, const double *d_SB, const CrawfordWork &w, hi
     return BSP_OK;
 }
 
-int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const double *d_HB, const CrawfordWork &w, double *d_AB,
-                 hipStream_t st, bool s_prepared, hipEvent_t *evc, hipStream_t aux0)
+int crawford_run(LaunchCtx &cx, int n, int npad, int k, int nl, const double *d_SB, const double *d_HB, const CrawfordWork &w, double *d_AB,
+                 hipStream_t st, bool s_prepared, hipEvent_t *evc)
 {
     if (!crawford_supported(n, k)) return BSP_ERR_UNSUPPORTED;
-    const int N = (n + CB - 1) / CB;
-    // from both ends: both parts whole blocks and long enough to have a chase.  BSP_CW_SPLIT = the share of the blocks, in percent,
-    // that the LEADING part takes (at most half): its fill is chased towards r = 0, which is what costs accuracy (ORIENTATION).
-    int Nl = (opts().cw_split > 0 && n % CB == 0) ? (int)((long)N * (opts().cw_split > 50 ? 50 : opts().cw_split) / 100) : 0;
-    const bool split = Nl >= 3 && N - Nl >= 4;
-    if (!split) Nl = 0;
-    const int Nh = split ? N - Nl : 0;                                     // blocks of the trailing part (the longer one)
-    const int Nproc = split ? Nh : N;                                      // blocks of the longest process
-    const int Ns = split ? Nh + 2 : N;                                     // block slots of a channel of the batch
+    const CwShape c = cw_shape(n);
+    const int N = c.N, Nl = c.Nl, Nh = c.Nh, Nproc = c.Nproc, Ns = c.Ns;
+    const bool split = c.split;
     const int ny = split ? 2 * nl : nl;                                    // channels of the batch
     const int nlead = split ? Nl : 0x7fffffff;
     int rc;
@@ -1234,20 +1186,16 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
         ngrp = opts().cw_streams > 4 ? 4 : opts().cw_streams;
         while (ngrp > 1 && nl / ngrp < 16) --ngrp;
     }
-    // aux0: a stream of the caller's for the second group (the one that prepared S, idle by now: a process has few hardware queues, and
-    // a stream more than those makes two of them wait for each other)
-    static hipStream_t s_aux[3] = {nullptr, nullptr, nullptr};
-    hipStream_t aux[3];
-    hipEvent_t evf = nullptr, evj[3] = {nullptr, nullptr, nullptr};
+    // the further groups' streams and the fork / join events are the ctx's, created at first need and recorded anew by every solve
+    hipStream_t *const aux = cx.cw_aux;
     if (ngrp > 1) {
-        static std::mutex mx;
-        std::lock_guard<std::mutex> lk(mx);
-        for (int g = 0; g < ngrp - 1; ++g)
-            if (!s_aux[g] && !(g == 0 && aux0)) BSP_HIP(hipStreamCreateWithFlags(&s_aux[g], hipStreamNonBlocking));
-        for (int g = 0; g < 3; ++g) aux[g] = (g == 0 && aux0) ? aux0 : s_aux[g];
-        BSP_HIP(hipEventCreateWithFlags(&evf, hipEventDisableTiming));
-        BSP_HIP(hipEventRecord(evf, st));
-        for (int g = 0; g < ngrp - 1; ++g) BSP_HIP(hipStreamWaitEvent(aux[g], evf, 0));
+        if (!cx.cw_fork) BSP_HIP(hipEventCreateWithFlags(&cx.cw_fork, hipEventDisableTiming));
+        for (int g = 0; g < ngrp - 1; ++g) {
+            if (!aux[g]) BSP_HIP(hipStreamCreateWithFlags(&aux[g], hipStreamNonBlocking));
+            if (!cx.cw_join[g]) BSP_HIP(hipEventCreateWithFlags(&cx.cw_join[g], hipEventDisableTiming));
+        }
+        BSP_HIP(hipEventRecord(cx.cw_fork, st));
+        for (int g = 0; g < ngrp - 1; ++g) BSP_HIP(hipStreamWaitEvent(aux[g], cx.cw_fork, 0));
     }
     for (int t = 1; t <= tmax; ++t) {
         const int jel = ((t & 1) && (t + 1) / 2 <= Nproc - 1) ? (t + 1) / 2 : 0;
@@ -1265,14 +1213,9 @@ int crawford_run(int n, int npad, int k, int nl, const double *d_SB, const doubl
             wavefront(t, jlo, nch, jel, c1 - c0, c0, g == 0 ? st : aux[g - 1]);
         }
     }
-    if (ngrp > 1) {
-        for (int g = 0; g < ngrp - 1; ++g) {
-            BSP_HIP(hipEventCreateWithFlags(&evj[g], hipEventDisableTiming));
-            BSP_HIP(hipEventRecord(evj[g], aux[g]));
-            BSP_HIP(hipStreamWaitEvent(st, evj[g], 0));
-        }
-        hipEventDestroy(evf);                                              // released once the work recorded so far has passed them
-        for (int g = 0; g < ngrp - 1; ++g) hipEventDestroy(evj[g]);
+    for (int g = 0; g < ngrp - 1; ++g) {
+        BSP_HIP(hipEventRecord(cx.cw_join[g], aux[g]));
+        BSP_HIP(hipStreamWaitEvent(st, cx.cw_join[g], 0));
     }
     if (evc)
         for (; waited < CW_CHUNKS - 1; ++waited) BSP_HIP(hipStreamWaitEvent(st, evc[waited + 1], 0));   // (a pencil of very few blocks)

@@ -232,6 +232,7 @@ extern "C" void bsp_dsygv_(const int *itype, const char *jobz, const char *uplo,
     DBuf<double> dSB, dHB, dUB, dr, dY, dC, dAB, dd, de, dE, dvw, dvec;
     DBuf<char> dwork, dctl, dcw;
     DBuf<int> dinfo, dchan, dstatus;
+    LaunchCtx cx;                                        // behind the buffers: released, its streams drained, before they are freed
     const size_t nn = (size_t)npad * npad;
     const int route = pipeline_route(n, k);              // 2: the band route (half-width <= 8): no dense matrix at all
     bool ok = dSB.alloc((size_t)k * n) == hipSuccess && dHB.alloc((size_t)k * n) == hipSuccess &&
@@ -255,7 +256,7 @@ extern "C" void bsp_dsygv_(const int *itype, const char *jobz, const char *uplo,
     int rc = BSP_OK;
     // the band route factors the reversed overlap; DSYGV returns the factor of B itself and names ITS leading minor in info
     if (route == 2) rc = launch_band_cholesky(n, k, dSB.p, dUB.p, dr.p, dinfo.p, 0);
-    if (!rc) rc = pipeline_enqueue(n, npad, k, 1, dSB.p, dHB.p, pb, dE.p, 0, nullptr);
+    if (!rc) rc = pipeline_enqueue(cx, n, npad, k, 1, dSB.p, dHB.p, pb, dE.p, 0, nullptr);
     if (rc || hipDeviceSynchronize() != hipSuccess) { fail("the solve pipeline failed"); return; }
     int cinfo = 0, cstat = 0;
     hipMemcpy(&cinfo, dinfo.p, sizeof(int), hipMemcpyDeviceToHost);

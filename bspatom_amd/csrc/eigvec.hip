@@ -11,6 +11,7 @@
 // Output normalisation: c^T S c = 1 (DSYGV ITYPE=1), sign chosen so that the first significant
 // coefficient is positive (LAPACK's sign is arbitrary; CHKPHS is commented out, matrices.f90:382).
 #include "bandsect.h"
+#include "wave_ops.h"
 
 namespace bsp {
 
@@ -28,48 +29,26 @@ __device__ __forceinline__ double pencil_entry(const double *__restrict__ SB, co
 // work layout per vector: U[n][2b+1], L[n][b], ipiv[n] (as doubles), tmp[n]
 // wave reductions on the DPP path (a ds_bpermute butterfly costs an LDS round trip per level, and every one of the
 // n dependent steps of this kernel has a reduction in it)
-template <int CTRL>
-__device__ __forceinline__ double ev_dpp(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-__device__ __forceinline__ double ev_readlane(double x, int l)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
-    return r.d;
-}
-__device__ __forceinline__ double ev_wave_sum(double x)          // every lane gets the sum over the 64 lanes
-{
-    x += ev_dpp<0x111>(x); x += ev_dpp<0x112>(x); x += ev_dpp<0x114>(x); x += ev_dpp<0x118>(x);   // row_shr 1, 2, 4, 8 (zeros shift in)
-    return (ev_readlane(x, 15) + ev_readlane(x, 31)) + (ev_readlane(x, 47) + ev_readlane(x, 63));
-}
 __device__ __forceinline__ double ev_row0_max(double x)          // max over lanes 0..15 (x >= 0 there), uniform
 {
-    x = fmax(x, ev_dpp<0x111>(x)); x = fmax(x, ev_dpp<0x112>(x)); x = fmax(x, ev_dpp<0x114>(x)); x = fmax(x, ev_dpp<0x118>(x));
-    return ev_readlane(x, 15);
+    x = fmax(x, dpp_mov<0x111>(x)); x = fmax(x, dpp_mov<0x112>(x)); x = fmax(x, dpp_mov<0x114>(x)); x = fmax(x, dpp_mov<0x118>(x));
+    return read_lane(x, 15);
 }
 
 // The kernel is ONE wavefront walking n dependent steps: a step's synchronisation must not wait for the global stores
 // of the step before (U, L rows: fire and forget) -- __syncthreads() does (s_waitcnt vmcnt(0)), which put a memory
 // round trip into every column of the factorisation.
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (lds_barrier, wave_ops.h)
 
 // Where y lives (invit_batch_kernel: in global memory, a slot of the work area, instead of LDS) changes what a pass boundary
 // must wait for.  RULE (y in global memory): a wave's own global stores of y must be COMPLETE (s_waitcnt vmcnt(0)) before the
-// pass that reads them -- lane 0 stores y[j] in the solves and lane j % 64 loads it in the next pass; lds_sync() waits for
+// pass that reads them -- lane 0 stores y[j] in the solves and lane j % 64 loads it in the next pass; lds_barrier() waits for
 // LDS traffic only (lgkmcnt) and orders nothing in global memory.  The single-wave workgroup needs no s_barrier for it.
 template <bool YG>
 __device__ __forceinline__ void y_sync()
 {
     if constexpr (YG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else lds_sync();
+    else lds_barrier();
 }
 
 // Start vector of the inverse iteration.  seed 0: the constant vector, the start of every vector of a simple spectrum.  seed r > 0:
@@ -171,13 +150,13 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
             for (int t = 1; t <= BT; ++t)
                 if (t == dp) { const double t1 = a[0]; a[0] = a[t]; a[t] = t1; }
         }
-        double pv = ev_readlane(a[0], 0);
+        double pv = read_lane(a[0], 0);
         if (fabs(pv) < pertol) pv = (pv < 0.0) ? -pertol : pertol;
         const double rpv = 1.0 / pv;
         double lmine = 0.0;                                          // this lane's multiplier (row j + lane), for the store
 #pragma unroll
         for (int t = 1; t <= BT; ++t) {
-            const double lt = (t <= nrow) ? ev_readlane(a[t], 0) * rpv : 0.0;
+            const double lt = (t <= nrow) ? read_lane(a[t], 0) * rpv : 0.0;
             lmine = (lane == t) ? lt : lmine;
             a[t] = (lane >= 1) ? a[t] - lt * a[0] : 0.0;             // columns j + 1 .. j + 2 b; column j is eliminated
         }
@@ -189,7 +168,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
 #pragma unroll
         for (int u = 1; u < PF; ++u) pin = ((j & (PF - 1)) == u) ? pe[u] : pin;
 #pragma unroll
-        for (int t = 0; t < BT; ++t) a[t] = ev_dpp<0x130>(a[t + 1]);  // wave_shl:1 -- lane c takes lane c + 1
+        for (int t = 0; t < BT; ++t) a[t] = dpp_mov<0x130>(a[t + 1]);  // wave_shl:1 -- lane c takes lane c + 1
         a[BT] = 0.0;
 #pragma unroll
         for (int t = 0; t <= BT; ++t)
@@ -232,7 +211,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                     lv[u] = lvn[u]; pvv[u] = pvn[u];
                     lvn[u] = (jn < n && lane >= 1 && lane <= b) ? Lm[(size_t)jn * b + lane - 1] : 0.0;
                     pvn[u] = (jn < n) ? piv[jn] : 0.0;
-                    if constexpr (YG) yin[u] = ev_readlane(yl, u);
+                    if constexpr (YG) yin[u] = read_lane(yl, u);
                     else yin[u] = (j + b + 1 < n) ? y[j + b + 1] : 0.0;
                 }
 #pragma unroll
@@ -241,14 +220,14 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                     if (j < n) {
                         const int p = (int)pvv[u];
                         if (p != j) {                                    // uniform: rows j and p change places (p - j <= b: inside the window)
-                            const double t0 = ev_readlane(w, 0), tq = ev_readlane(w, p - j);
+                            const double t0 = read_lane(w, 0), tq = read_lane(w, p - j);
                             w = lane == 0 ? tq : (lane == p - j ? t0 : w);
                         }
-                        const double yj = ev_readlane(w, 0);
+                        const double yj = read_lane(w, 0);
                         const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;
                         if (lane >= 1 && lane <= nrow) w -= lv[u] * yj;
                         if (lane == 0) y[j] = yj;
-                        w = ev_dpp<0x130>(w);                            // wave_shl:1 -- lane i takes lane i + 1
+                        w = dpp_mov<0x130>(w);                            // wave_shl:1 -- lane i takes lane i + 1
                         if (lane == b) w = yin[u];
                     }
                 }
@@ -283,7 +262,7 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                     ru[u] = (j >= 0) ? 1.0 / udn[u] : 0.0;
                     uvn[u] = (jn >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)jn * (2 * b + 1) + lane] : 0.0;
                     udn[u] = (jn >= 0) ? U[(size_t)jn * (2 * b + 1)] : 1.0;
-                    if constexpr (YG) yv[u] = ev_readlane(yb, u);
+                    if constexpr (YG) yv[u] = read_lane(yb, u);
                     else yv[u] = (j >= 0) ? y[j] : 0.0;
                 }
 #pragma unroll
@@ -292,10 +271,10 @@ __device__ __forceinline__ void invit_body(int n, int k, const double *__restric
                     if (j >= 0) {
                         double s2 = 0.0;
                         if (lane >= 1 && lane <= 2 * b && j + lane < n) s2 = uv[u] * w;
-                        s2 = ev_wave_sum(s2);
+                        s2 = wave_sum(s2);
                         const double xj = (yv[u] - s2) * ru[u];
                         if (lane == 0) y[j] = xj;
-                        w = ev_dpp<0x138>(w);                            // wave_shr:1 -- lane i takes lane i - 1
+                        w = dpp_mov<0x138>(w);                            // wave_shr:1 -- lane i takes lane i - 1
                         if (lane == 1) w = xj;
                     }
                 }
@@ -444,14 +423,10 @@ int launch_inverse_iteration(int n, int k, int nvec, const double *d_SB, const d
     if (lds > 140 * 1024) return BSP_ERR_UNSUPPORTED;
     static bool attr_set = false;
     if (!attr_set) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(invit_kernel<8>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(invit_kernel<EB_MAX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(invit_kernel<8, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(invit_kernel<EB_MAX, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+        BSP_HIP(allow_lds(invit_kernel<8>, 140 * 1024));
+        BSP_HIP(allow_lds(invit_kernel<EB_MAX>, 140 * 1024));
+        BSP_HIP(allow_lds(invit_kernel<8, true>, 140 * 1024));
+        BSP_HIP(allow_lds(invit_kernel<EB_MAX, true>, 140 * 1024));
         attr_set = true;
     }
     if (rank > 0) {
@@ -471,9 +446,8 @@ size_t invit_batch_slot_doubles(int n, int k) { return invit_work_doubles(n, k) 
 int invit_batch_slots(int k, int items, int *slots)
 {
     if (k - 1 > EB_MAX || k < 2 || items < 1) return BSP_ERR_ARG;
-    int dev = 0, cus = 0, per_cu = 0;
-    BSP_HIP(hipGetDevice(&dev));
-    BSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int per_cu = 0;
+    const int cus = device_cus();
     if (k - 1 <= 8) BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, invit_batch_kernel<8>, 64, 0));
     else BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, invit_batch_kernel<EB_MAX>, 64, 0));
     const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
@@ -503,7 +477,7 @@ int launch_early_vector(int n, int k, const double *d_SB, const double *d_HB, in
     if (own_cu && lds + stat < OWN_CU_LDS) lds = OWN_CU_LDS - stat;
     static bool attr_set = false;
     if (!attr_set) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(early_vector_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
+        BSP_HIP(allow_lds(early_vector_kernel, room));
         attr_set = true;
     }
     hipLaunchKernelGGL(early_vector_kernel, dim3(1), dim3(BS_T), lds, st, n, k, d_SB, d_HB, m, d_E, d_work, d_vec, d_info);

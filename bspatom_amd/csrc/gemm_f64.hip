@@ -13,6 +13,7 @@
 // The C store is widest when C is contiguous along j (sCn == 1); the host wrapper transposes the
 // product (C^T = B^T A^T) when C is contiguous along i instead.
 #include "common.h"
+#include "wave_ops.h"
 #include "mfma_tile.h"
 
 namespace bsp {
@@ -292,7 +293,6 @@ int gemm_splitk_f64(const GemmDesc &gin, int splits, double *part, hipStream_t s
 // With beta != 0 the C tile is loaded straight into the accumulators ((beta/alpha) C) while the
 // first tiles are staged, so the epilogue is a pure store.
 // ================================================================================================
-__device__ __forceinline__ void lds_barrier2() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // timing experiments only (BSP_GEMM_DIAG): cycle stamps of one workgroup's phases, summed over its life
 __device__ long long g_gemm2_diag[8];
 #define G2_STAMP(k) if (DIAGG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dacc[k] += t_ - tl; tl = t_; }
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (DIAGG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); G2_STAMP(1) }   // ... and arrived
     tile_store<BM, ALAY, SW>(ra, As[0], tid);
     G2_STORE_B(0, Bs[0], rb)
-    lds_barrier2();
+    lds_barrier();
     G2_STAMP(2)
 
     if constexpr (MODE == 2) {
@@ -548,7 +548,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 tile_store<BM, ALAY, SW>(S1a, As[cur ^ 1], tid);                                                 \
                 G2_STORE_B(((t_) + 1) * BK, Bs[cur ^ 1], S1b)                                                \
             }                                                                                                \
-            lds_barrier2();                                                                                  \
+            lds_barrier();                                                                                  \
         }
         int t = 0;
         for (; t + 1 < nk; t += 2) {
@@ -579,7 +579,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 tile_store<BM, ALAY, SW>(ra, As[cur ^ 1], tid);
                 G2_STORE_B((t + 1) * BK, Bs[cur ^ 1], rb)
             }
-            lds_barrier2();
+            lds_barrier();
             G2_STAMP(5)
         }
 }

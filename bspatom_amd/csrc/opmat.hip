@@ -114,8 +114,7 @@ int launch_operator_bands(int nfun, int k, int ka, int nkp, int nop, int nr, con
     if (TI < 4) return BSP_ERR_UNSUPPORTED;
     static bool attr = false;
     if (!attr) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(operator_band_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(allow_lds(operator_band_kernel, 150 * 1024));
         attr = true;
     }
     KScope ks(KS_OPBAND, st);

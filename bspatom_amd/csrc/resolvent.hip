@@ -16,40 +16,13 @@
 // A matrix is one item, its right-hand sides are solved one after the other: nothing of an x depends on the other matrices, on the
 // number of right-hand sides or projections, or on the slot that took the item (G2).
 #include "common.h"
+#include "wave_ops.h"
 
 namespace bsp {
 namespace {
 constexpr int RS_BMAX = 15;                // half-bandwidth limit (k <= 16)
 constexpr int RS_PF = 8;                   // steps per prefetch block
-
-template <int CTRL>
-__device__ __forceinline__ double rs_dpp(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-__device__ __forceinline__ double rs_readlane(double x, int l)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
-    return r.d;
-}
-// sum over lanes 0 .. 31 (the callers' terms are zero beyond lane 2 b <= 30), the same in every lane: a fixed tree
-__device__ __forceinline__ double rs_sum32(double x)
-{
-    x += rs_dpp<0x111>(x); x += rs_dpp<0x112>(x); x += rs_dpp<0x114>(x); x += rs_dpp<0x118>(x);   // row_shr 1, 2, 4, 8 (zeros shift in)
-    return rs_readlane(x, 15) + rs_readlane(x, 31);
-}
-__device__ __forceinline__ double rs_sum64(double x)
-{
-    x += rs_dpp<0x111>(x); x += rs_dpp<0x112>(x); x += rs_dpp<0x114>(x); x += rs_dpp<0x118>(x);
-    return (rs_readlane(x, 15) + rs_readlane(x, 31)) + (rs_readlane(x, 47) + rs_readlane(x, 63));
-}
+// (sums of wave_ops.h: wave_sum32 over lanes 0 .. 31 -- the callers' terms are zero beyond lane 2 b <= 30 --, wave_sum over all)
 // doubles of one slot's scratch, even (a slot starts on a 16-byte boundary)
 __host__ __device__ inline size_t rs_slot_doubles(int n, int k)
 {
@@ -135,7 +108,7 @@ __device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict_
                     ar[0] = ar[t]; ai[0] = ai[t]; ar[t] = t1; ai[t] = t2;
                 }
         }
-        double pr = rs_readlane(ar[0], 0), pi = rs_readlane(ai[0], 0);
+        double pr = read_lane(ar[0], 0), pi = read_lane(ai[0], 0);
         if (fabs(pr) + fabs(pi) < pertol) { pr = (pr < 0.0) ? -pertol : pertol; pi = 0.0; ++nper; }
         // 1 / pivot, once per column
         const double sc = 1.0 / (fabs(pr) + fabs(pi));
@@ -145,7 +118,7 @@ __device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict_
         double lmr = 0.0, lmi = 0.0;                                 // this lane's multiplier (row j + lane), for the store
 #pragma unroll
         for (int t = 1; t <= BT; ++t) {
-            const double xr = rs_readlane(ar[t], 0), xi = rs_readlane(ai[t], 0);
+            const double xr = read_lane(ar[t], 0), xi = read_lane(ai[t], 0);
             const double ltr = (t <= nrow) ? xr * rr - xi * ri : 0.0;
             const double lti = (t <= nrow) ? xr * ri + xi * rr : 0.0;
             lmr = (lane == t) ? ltr : lmr;
@@ -165,7 +138,7 @@ __device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict_
             pini = ((j & (PF - 1)) == u) ? pei[u] : pini;
         }
 #pragma unroll
-        for (int t = 0; t < BT; ++t) { ar[t] = rs_dpp<0x130>(ar[t + 1]); ai[t] = rs_dpp<0x130>(ai[t + 1]); }   // wave_shl:1
+        for (int t = 0; t < BT; ++t) { ar[t] = dpp_mov<0x130>(ar[t + 1]); ai[t] = dpp_mov<0x130>(ai[t + 1]); }   // wave_shl:1
         ar[BT] = 0.0; ai[BT] = 0.0;
 #pragma unroll
         for (int t = 0; t <= BT; ++t)
@@ -209,20 +182,20 @@ __device__ __forceinline__ void rs_solve(int n, int b, const double2 *U, const d
                 if (j < n) {
                     const int p = __builtin_amdgcn_readfirstlane(pvv[u]);
                     if (p != j) {                                    // uniform: rows j and p change places (p - j <= b: inside the window)
-                        const double t0r = rs_readlane(wr, 0), t0i = rs_readlane(wi, 0);
-                        const double tqr = rs_readlane(wr, p - j), tqi = rs_readlane(wi, p - j);
+                        const double t0r = read_lane(wr, 0), t0i = read_lane(wi, 0);
+                        const double tqr = read_lane(wr, p - j), tqi = read_lane(wi, p - j);
                         wr = lane == 0 ? tqr : (lane == p - j ? t0r : wr);
                         wi = lane == 0 ? tqi : (lane == p - j ? t0i : wi);
                     }
-                    const double yr = rs_readlane(wr, 0), yi = rs_readlane(wi, 0);
+                    const double yr = read_lane(wr, 0), yi = read_lane(wi, 0);
                     const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;
                     if (lane >= 1 && lane <= nrow) {
                         wr -= lv[u].x * yr - lv[u].y * yi;
                         wi -= lv[u].x * yi + lv[u].y * yr;
                     }
                     if (lane == 0) y[j] = make_double2(yr, yi);
-                    wr = rs_dpp<0x130>(wr); wi = rs_dpp<0x130>(wi);  // wave_shl:1 -- lane i takes lane i + 1
-                    const double er = rs_readlane(yl.x, u), ei = rs_readlane(yl.y, u);
+                    wr = dpp_mov<0x130>(wr); wi = dpp_mov<0x130>(wi);  // wave_shl:1 -- lane i takes lane i + 1
+                    const double er = read_lane(yl.x, u), ei = read_lane(yl.y, u);
                     if (lane == b) { wr = er; wi = ei; }
                 }
             }
@@ -261,11 +234,11 @@ __device__ __forceinline__ void rs_solve(int n, int b, const double2 *U, const d
                         sr = uv[u].x * wr - uv[u].y * wi;
                         si = uv[u].x * wi + uv[u].y * wr;
                     }
-                    sr = rs_sum32(sr); si = rs_sum32(si);
-                    const double dr = rs_readlane(yb.x, u) - sr, di = rs_readlane(yb.y, u) - si;
+                    sr = wave_sum32(sr); si = wave_sum32(si);
+                    const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
                     const double xr = dr * ru[u].x - di * ru[u].y, xi = dr * ru[u].y + di * ru[u].x;
                     if (lane == 0) y[j] = make_double2(xr, xi);
-                    wr = rs_dpp<0x138>(wr); wi = rs_dpp<0x138>(wi);  // wave_shr:1 -- lane i takes lane i - 1
+                    wr = dpp_mov<0x138>(wr); wi = dpp_mov<0x138>(wi);  // wave_shr:1 -- lane i takes lane i - 1
                     if (lane == 1) { wr = xr; wi = xi; }
                 }
             }
@@ -317,7 +290,7 @@ __global__ __launch_bounds__(64) void resolvent_kernel(const ResolventArgs a)
                         sr += pv.x * xv.x - pv.y * xv.y;
                         si += pv.x * xv.y + pv.y * xv.x;
                     }
-                    sr = rs_sum64(sr); si = rs_sum64(si);
+                    sr = wave_sum(sr); si = wave_sum(si);
                     if (lane == 0) { a.R[2 * (mr * a.nproj + q)] = sr; a.R[2 * (mr * a.nproj + q) + 1] = si; }
                 }
             rs_sync();                                               // every load of y is back before the next right-hand side overwrites it
@@ -330,9 +303,8 @@ size_t resolvent_slot_doubles(int n, int k) { return rs_slot_doubles(n, k); }
 int resolvent_slots(int k, int nmat, int *slots)
 {
     if (k - 1 > RS_BMAX || k < 2 || nmat < 1) return BSP_ERR_ARG;
-    int dev = 0, cus = 0, per_cu = 0;
-    BSP_HIP(hipGetDevice(&dev));
-    BSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int per_cu = 0;
+    const int cus = device_cus();
     if (k - 1 <= 8) BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_kernel<8>, 64, 0));
     else BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_kernel<RS_BMAX>, 64, 0));
     const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);

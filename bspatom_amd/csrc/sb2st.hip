@@ -17,6 +17,7 @@
 //   8  (default) 7 paired as in 6: four sweeps in flight per channel
 #include <vector>
 #include "common.h"
+#include "wave_ops.h"
 
 namespace bsp {
 
@@ -37,36 +38,7 @@ constexpr int TLD = SB + 1;        // LDS tile row stride (bank-conflict padding
 // and the result stores stay in flight across them (a __syncthreads() would drain vmcnt(0) at every
 // barrier).  Cross-thread HBM dependencies exist only between sweeps; one __syncthreads() per sweep
 // covers them.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Wave-wide sum, result uniform in every lane: DPP row scan (row_shr 1,2,4,8 -> lane 15 of each
-// 16-lane row holds the row total) + four readlanes.  ~10x shorter dependent chain than a
-// ds_bpermute butterfly, which matters because the reflector construction is serial.
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-__device__ __forceinline__ double read_lane(double x, int l)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
-    return r.d;
-}
-__device__ __forceinline__ double wave_sum(double x)
-{
-    x += dpp_mov<0x111>(x);      // row_shr:1
-    x += dpp_mov<0x112>(x);      // row_shr:2
-    x += dpp_mov<0x114>(x);      // row_shr:4
-    x += dpp_mov<0x118>(x);      // row_shr:8
-    return (read_lane(x, 15) + read_lane(x, 31)) + (read_lane(x, 47) + read_lane(x, 63));
-}
+// (lds_barrier, wave_ops.h.)  The wave sums are DPP row scans (wave_sum): the reflector construction is serial.
 
 // lane-parallel dlarfg on one wavefront: xi = element i of x (0 beyond L).  Returns v_i.
 __device__ __forceinline__ double wave_house(double xi, int lane, int L, double *beta, double *tau)
@@ -1295,7 +1267,7 @@ size_t sb2st_ctl_bytes(int batch)
     return (size_t)batch * sizeof(Sb8Ctl);
 }
 
-int launch_sb2st(int n, int npad, int b, int batch, double *d_AB, double *d_d, double *d_e, hipStream_t st, int *d_status,
+int launch_sb2st(LaunchCtx &cx, int n, int npad, int b, int batch, double *d_AB, double *d_d, double *d_e, hipStream_t st, int *d_status,
                  void *ctl)
 {
     if (b != SB) return BSP_ERR_ARG;
@@ -1315,18 +1287,14 @@ int launch_sb2st(int n, int npad, int b, int batch, double *d_AB, double *d_d, d
         // 7: one workgroup per channel; 8: two (the partner CU runs the two sweeps in between), v6's pairing
         static bool attr7 = false;
         if (!attr7) {
-            BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sb2st_kernel_v7<0>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sb2st_kernel_v7<1>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            BSP_HIP(allow_lds(sb2st_kernel_v7<0>, 160 * 1024));
+            BSP_HIP(allow_lds(sb2st_kernel_v7<1>, 160 * 1024));
             attr7 = true;
         }
-        static int *d_chk = nullptr;
+        int *&d_chk = cx.sb2st_chk;
         const bool chk = opts().sb2st_check != 0;
         if (chk && !d_chk) BSP_HIP(hipMalloc(reinterpret_cast<void **>(&d_chk), sizeof(int)));
         if (chk) BSP_HIP(hipMemsetAsync(d_chk, 0, sizeof(int), st));
-        static Sb8Ctl *s_ctl7 = nullptr;
-        static int cap7 = 0;
         const int ring_env = opts().sb2st_ring;
         Sb8Ctl *d_ctl = nullptr;
         // ring size: as many workgroups per channel as the chip has CUs for (each needs a whole CU), at most 8;
@@ -1339,15 +1307,8 @@ int launch_sb2st(int n, int npad, int b, int batch, double *d_AB, double *d_d, d
                 while (P > 2 && n / SB < 3 * P) P /= 2;       // measured: rings beyond a sweep's length (n/64 items) still
                                                               // help down to about a third of it (n = 2048: 57 -> 46 ms)
             if (P < 2) P = 2;
+            if (!ctl) return BSP_ERR_ARG;                     // the rings' control block is the caller's
             d_ctl = static_cast<Sb8Ctl *>(ctl);
-            if (!d_ctl) {
-                if (cap7 < batch) {
-                    if (s_ctl7) hipFree(s_ctl7);
-                    BSP_HIP(hipMalloc(reinterpret_cast<void **>(&s_ctl7), (size_t)batch * sizeof(Sb8Ctl)));
-                    cap7 = batch;
-                }
-                d_ctl = s_ctl7;
-            }
             BSP_HIP(hipMemsetAsync(d_ctl, 0, (size_t)batch * sizeof(Sb8Ctl), st));
         }
         const int nblk = (ver == 8) ? ((batch + 7) / 8) * 8 * P : batch;

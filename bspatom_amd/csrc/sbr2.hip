@@ -21,6 +21,7 @@
 // Index conventions, the lag of 3 and the working band (<= 127 / <= 31 sub-diagonals) are those of tools/proto_sbr.py.
 // Band storage as everywhere: AB[d + 128 j] = A(j + d, j) (sy2sb.hip::extract_band_kernel).
 #include "common.h"
+#include "wave_ops.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -244,29 +245,6 @@ __global__ __launch_bounds__(256) void sb2sb_kernel(int n, int npad, double *__r
 typedef double d4_t __attribute__((ext_vector_type(4)));
 constexpr int SB2SB2_LDS = (64 * XLD + 4 * 64 * VLD + 16 * VLD + 16) * 8;
 
-template <int CTRL>
-__device__ __forceinline__ double dppm(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-__device__ __forceinline__ double rlane(double x, int l)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
-    return r.d;
-}
-__device__ __forceinline__ double wsum_dpp(double x)          // uniform result: row scans + the four row totals
-{
-    x += dppm<0x111>(x); x += dppm<0x112>(x); x += dppm<0x114>(x); x += dppm<0x118>(x);
-    return (rlane(x, 15) + rlane(x, 31)) + (rlane(x, 47) + rlane(x, 63));
-}
-__device__ __forceinline__ void lds_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double *__restrict__ ABall, int t, int s_lo)
@@ -315,8 +293,8 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
     // operations in the same order as without look-ahead: the band comes out bit-identical.
     auto make_reflector = [&](const int i) {               // by wave i & 3
         const double x = xc[i >> 2];
-        const double nrm2 = wsum_dpp(lane > i ? x * x : 0.0);
-        const double alpha = rlane(x, i);
+        const double nrm2 = wave_sum(lane > i ? x * x : 0.0);
+        const double alpha = read_lane(x, i);
         double tq = 0.0, scale = 0.0, beta = alpha;
         if (nrm2 != 0.0) {
             beta = -copysign(sqrt(alpha * alpha + nrm2), alpha);
@@ -328,23 +306,23 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
         xc[i >> 2] = lane < i ? x : (lane == i ? beta : 0.0);
     };
     if (w == 0) make_reflector(0);
-    lds_bar();
+    lds_barrier();
 #pragma unroll
     for (int i = 0; i < NB1 - 1; ++i) {
         const double v = V[lane * VLD + i], tq = tau[i];
         if (w == ((i + 1) & 3)) {
             const int q1 = (i + 1) >> 2;
-            const double dot = wsum_dpp(v * xc[q1]);
+            const double dot = wave_sum(v * xc[q1]);
             xc[q1] -= tq * dot * v;
             make_reflector(i + 1);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (w + 4 * q > i + 1) {
-                const double dot = wsum_dpp(v * xc[q]);
+                const double dot = wave_sum(v * xc[q]);
                 xc[q] -= tq * dot * v;
             }
-        lds_bar();
+        lds_barrier();
     }
     for (int q = 0; q < 4; ++q) {                          // R (and zeros) back to the band
         const int gc = pc0 + w + 4 * q;
@@ -363,12 +341,12 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
         }
         for (int r = 0; r < 4; ++r) Gp[w * 16 * VLD + (l4 + 4 * r) * VLD + l15] = acc[r];
     }
-    lds_bar();
+    lds_barrier();
     {
         const int i = tid >> 4, j = tid & 15, o = i * VLD + j;
         G[o] = (Gp[o] + Gp[16 * VLD + o]) + (Gp[32 * VLD + o] + Gp[48 * VLD + o]);
     }
-    lds_bar();
+    lds_barrier();
     if (w == 0) {                                         // VT T^-1 = V, row by row
         double vt[16];
 #pragma unroll
@@ -380,7 +358,7 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
             VT[lane * VLD + j] = vt[j];
         }
     }
-    lds_bar();
+    lds_barrier();
 
     // ---- left tile
     if (k > 0) {
@@ -390,7 +368,7 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
             for (int q = 0; q < 16; ++q) acc = MFMA(VT[(4 * q + l4) * VLD + l15], X[cn * XLD + 4 * q + l4], acc);
             for (int r = 0; r < 4; ++r) Yb[(l4 + 4 * r) * XLD + cn] = acc[r];
         }
-        lds_bar();
+        lds_barrier();
         for (int nb = 0; nb < 3; ++nb) {                  // X(:, 16:64) -= V W2, row block w
             const int cn = 16 + 16 * nb + l15;
             d4_t acc;
@@ -398,12 +376,12 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
             for (int q = 0; q < 4; ++q) acc = MFMA(-V[(16 * w + l15) * VLD + 4 * q + l4], Yb[(4 * q + l4) * XLD + cn], acc);
             for (int r = 0; r < 4; ++r) X[cn * XLD + 16 * w + l4 + 4 * r] = acc[r];
         }
-        lds_bar();
+        lds_barrier();
         for (int c = 16 + w; c < 64; c += 4) {
             const int gc = pc0 + c;
             if (gi < n) AB[(size_t)gc * LD + (gi - gc)] = X[c * XLD + lane];
         }
-        lds_bar();
+        lds_barrier();
     }
 
     // ---- diagonal tile
@@ -425,31 +403,31 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
             pf[q] = AB[gi1 < n ? (size_t)gc * LD + (gi1 - gc) : 0];
         }
     }
-    lds_bar();
+    lds_barrier();
     {                                                     // Y = D VT, row block w
         d4_t acc = {0.0, 0.0, 0.0, 0.0};
         for (int q = 0; q < 16; ++q) acc = MFMA(X[(4 * q + l4) * XLD + 16 * w + l15], VT[(4 * q + l4) * VLD + l15], acc);
         for (int r = 0; r < 4; ++r) Yb[(16 * w + l4 + 4 * r) * VLD + l15] = acc[r];
     }
-    lds_bar();
+    lds_barrier();
     {                                                     // M = VT^T Y, split along the rows
         d4_t acc = {0.0, 0.0, 0.0, 0.0};
         for (int q = 4 * w; q < 4 * w + 4; ++q) acc = MFMA(VT[(4 * q + l4) * VLD + l15], Yb[(4 * q + l4) * VLD + l15], acc);
         for (int r = 0; r < 4; ++r) Gp[w * 16 * VLD + (l4 + 4 * r) * VLD + l15] = acc[r];
     }
-    lds_bar();
+    lds_barrier();
     {
         const int i = tid >> 4, j = tid & 15, o = i * VLD + j;
         G[o] = (Gp[o] + Gp[16 * VLD + o]) + (Gp[32 * VLD + o] + Gp[48 * VLD + o]);
     }
-    lds_bar();
+    lds_barrier();
     {                                                     // Z = Y - 1/2 V M, row block w
         d4_t acc;
         for (int r = 0; r < 4; ++r) acc[r] = Yb[(16 * w + l4 + 4 * r) * VLD + l15];
         for (int q = 0; q < 4; ++q) acc = MFMA(-0.5 * V[(16 * w + l15) * VLD + 4 * q + l4], G[(4 * q + l4) * VLD + l15], acc);
         for (int r = 0; r < 4; ++r) Z[(16 * w + l4 + 4 * r) * VLD + l15] = acc[r];
     }
-    lds_bar();
+    lds_barrier();
     for (int bi = w; bi < 10; bi += 4) {                  // D -= V Z^T + Z V^T, the ten 16 x 16 blocks of the lower triangle
         const int mb = bi < 1 ? 0 : (bi < 3 ? 1 : (bi < 6 ? 2 : 3));
         const int nb = bi - (mb * (mb + 1)) / 2;
@@ -461,29 +439,29 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
         }
         for (int r = 0; r < 4; ++r) X[(16 * nb + l15) * XLD + 16 * mb + l4 + 4 * r] = acc[r];
     }
-    lds_bar();
+    lds_barrier();
     for (int c = w; c < 64; c += 4)
         if (lane >= c && gi < n) AB[(size_t)(r0 + c) * LD + (lane - c)] = X[c * XLD + lane];
 
     // ---- next bulge tile
     if (!more) return;
-    lds_bar();
+    lds_barrier();
 #pragma unroll
     for (int q = 0; q < 16; ++q) X[(w + 4 * q) * XLD + lane] = gi1 < n ? pf[q] : 0.0;
-    lds_bar();
+    lds_barrier();
     {                                                     // W1 = X' VT, row block w
         d4_t acc = {0.0, 0.0, 0.0, 0.0};
         for (int q = 0; q < 16; ++q) acc = MFMA(X[(4 * q + l4) * XLD + 16 * w + l15], VT[(4 * q + l4) * VLD + l15], acc);
         for (int r = 0; r < 4; ++r) Yb[(16 * w + l4 + 4 * r) * VLD + l15] = acc[r];
     }
-    lds_bar();
+    lds_barrier();
     for (int nb = 0; nb < 4; ++nb) {                      // X' -= W1 V^T
         d4_t acc;
         for (int r = 0; r < 4; ++r) acc[r] = X[(16 * nb + l15) * XLD + 16 * w + l4 + 4 * r];
         for (int q = 0; q < 4; ++q) acc = MFMA(-Yb[(16 * w + l15) * VLD + 4 * q + l4], V[(16 * nb + l15) * VLD + 4 * q + l4], acc);
         for (int r = 0; r < 4; ++r) X[(16 * nb + l15) * XLD + 16 * w + l4 + 4 * r] = acc[r];
     }
-    lds_bar();
+    lds_barrier();
     for (int c = w; c < 64; c += 4) {
         const int gc = r0 + c;
         if (gi1 < n) AB[(size_t)gc * LD + (gi1 - gc)] = X[c * XLD + lane];
@@ -498,47 +476,7 @@ __global__ __launch_bounds__(256) void sb2sb_mfma_kernel(int n, int npad, double
 constexpr int B2 = 16, NW2 = 8, WCOLS = 512, WROWS = 32;
 constexpr int SB16_LDS = (WCOLS * WROWS + NW2 * 16 + 2) * 8;
 
-template <int CTRL>
-__device__ __forceinline__ double dppd(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-__device__ __forceinline__ double rdlane(double x, int l)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
-    return r.d;
-}
-// Sum over the 16 lanes of a DPP row, the total in every lane (bitwise the same in all of them: each step adds the two
-// halves of a pair, and addition commutes): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror.
-__device__ __forceinline__ double rsum16(double x)
-{
-    x += dppd<0xB1>(x);
-    x += dppd<0x4E>(x);
-    x += dppd<0x141>(x);
-    x += dppd<0x140>(x);
-    return x;
-}
-// four row sums at once: the same four operations per value as rsum16 (the same bits), the four dependent chains interleaved so
-// that the DPP hazard slots and the add latencies of one are filled by the others (back to back the compiler pads them with s_nop)
-__device__ __forceinline__ void rsum16x4(double (&x)[4])
-{
-#pragma unroll
-    for (int q = 0; q < 4; ++q) x[q] += dppd<0xB1>(x[q]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) x[q] += dppd<0x4E>(x[q]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) x[q] += dppd<0x141>(x[q]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) x[q] += dppd<0x140>(x[q]);
-}
-__device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (Row sums: rsum16, rsum16x4, wave_ops.h.)
 
 // Householder parameters from alpha and the squared norm of the rest (> 0), with IEEE sqrt and divisions.  (v_rsq_f64 /
 // v_rcp_f64 + three Newton steps were 2 ms faster per 128-channel step and cost the eigenvalues next to zero their accuracy: C5
@@ -589,7 +527,7 @@ __device__ __forceinline__ void chase_item(double *Lw, double *pS, int r0, int c
         bt[j] = Lw[it[j]];
     }
     const double nrm2 = rsum16(r > 0 ? x * x : 0.0);
-    const double alpha = rdlane(x, 0);
+    const double alpha = read_lane(x, 0);
     double tq = 0.0, scale = 0.0, beta = alpha;
     if (nrm2 != 0.0) house_params(alpha, nrm2, beta, tq, scale);
     const double v = r == 0 ? 1.0 : x * scale;
@@ -621,7 +559,7 @@ __device__ __forceinline__ void chase_item(double *Lw, double *pS, int r0, int c
         part += vc[j] * pc[j];
     }
     if (r < 4) pS[4 * g + r] = r == 0 ? pc[0] : (r == 1 ? pc[1] : (r == 2 ? pc[2] : pc[3]));
-    const double vtp = (rdlane(part, 0) + rdlane(part, 16)) + (rdlane(part, 32) + rdlane(part, 48));
+    const double vtp = (read_lane(part, 0) + read_lane(part, 16)) + (read_lane(part, 32) + read_lane(part, 48));
     const double kk = 0.5 * tq * vtp;
     const double w = pS[r] - kk * v;
     for (int j = 0; j < 4; ++j) {
@@ -817,7 +755,7 @@ __global__ __launch_bounds__(576) void sb16st_kernel(int n, int npad, int batch,
                 else chase_item<false>(Lw, pS, r0, c0, k, r, g, cA, cT, offD);
                 if (diag) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
             }
-            lds_only_barrier();
+            lds_barrier();
             if (diag) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
         }
         __syncthreads();
@@ -897,20 +835,20 @@ struct Rw {
 template <int B>
 __device__ __forceinline__ double rsumB(double x)
 {
-    x += dppd<0xB1>(x);
-    x += dppd<0x4E>(x);
-    x += dppd<0x141>(x);
-    if (B == 16) x += dppd<0x140>(x);
+    x += dpp_mov<0xB1>(x);
+    x += dpp_mov<0x4E>(x);
+    x += dpp_mov<0x141>(x);
+    if (B == 16) x += dpp_mov<0x140>(x);
     return x;
 }
 // two such sums at once (the chains interleaved, same operations per value)
 template <int B>
 __device__ __forceinline__ void rsumBx2(double &a, double &b)
 {
-    a += dppd<0xB1>(a); b += dppd<0xB1>(b);
-    a += dppd<0x4E>(a); b += dppd<0x4E>(b);
-    a += dppd<0x141>(a); b += dppd<0x141>(b);
-    if (B == 16) { a += dppd<0x140>(a); b += dppd<0x140>(b); }
+    a += dpp_mov<0xB1>(a); b += dpp_mov<0xB1>(b);
+    a += dpp_mov<0x4E>(a); b += dpp_mov<0x4E>(b);
+    a += dpp_mov<0x141>(a); b += dpp_mov<0x141>(b);
+    if (B == 16) { a += dpp_mov<0x140>(a); b += dpp_mov<0x140>(b); }
 }
 
 // The reflector of the column whose element j is x0 in lane j of the item: v and tau into the slot xw, beta (lane 0) resp. zeros
@@ -1144,7 +1082,7 @@ __device__ __forceinline__ void mover_pass(double *Lw, double *__restrict__ AB, 
         mover_step<B, PH, MLAG>(Lw, AB, n, npad, LP + B * PH, RP, RPn, RPold, ps, lane, pollp, pubp, pw, ptmp, C, status, DIAG, dacc); \
         if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime(); \
         RP = RPn; \
-        lds_only_barrier(); \
+        lds_barrier(); \
         if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; } \
     }
     for (int t = 0; t < nsteps; t += 4) {
@@ -1339,7 +1277,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                     }
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
                     if (__builtin_amdgcn_ballot_w64(actN) != 0) stores_done_barrier<B>();
-                    else lds_only_barrier();
+                    else lds_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
                 };
                 for (int t = 0; t < tA; ++t) general_step(t);
@@ -1412,7 +1350,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                     }
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
                     if (__builtin_amdgcn_ballot_w64(actN) != 0) stores_done_barrier<B>();
-                    else lds_only_barrier();
+                    else lds_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
                 };
                 for (int t = 0; t < tA; ++t) general_step(t);
@@ -1449,7 +1387,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                     const int k4 = t - LAG * sw, r04 = r04b + B * t;
                     if (k4 > 0 && live && r04 < n) chase4_bulge<B>(Lw, r04, r04 - B, j, xs0 + ((t & 1) << 8), dumpi);
                     if (DIAG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
-                    lds_only_barrier();
+                    lds_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
                 };
                 // steady for this role from tA + 1 (k4 > 0 for all); r04 < n follows from r04 + B < n
@@ -1462,7 +1400,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                         chase4_bulge<B>(Lw, r04, r04 - B, j, xr, dumpi);
                         r04 += B; xr ^= 256;
                         if (DIAG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
-                        lds_only_barrier();
+                        lds_barrier();
                         if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
                     }
                 }
@@ -1521,10 +1459,8 @@ int launch_sb2sb(int n, int npad, int batch, double *d_AB, hipStream_t st)
 {
     static bool attr = false;
     if (!attr) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sb2sb_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    SB2SB_LDS));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sb2sb_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    SB2SB2_LDS));
+        BSP_HIP(allow_lds(sb2sb_kernel, SB2SB_LDS));
+        BSP_HIP(allow_lds(sb2sb_mfma_kernel, SB2SB2_LDS));
         attr = true;
     }
     const int mf = opts().sb2sb_mfma;
@@ -1561,13 +1497,13 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
     static bool attr = false;
     static int wg8 = 1;                                     // workgroups of the B = 8 kernel a CU holds (LDS: 2; registers permitting)
     if (!attr) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sb16st_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    SB16_LDS));
-        const void *const rk16[] = {reinterpret_cast<const void *>(sbr_rows_kernel<16, false>), reinterpret_cast<const void *>(sbr_rows_kernel<16, true>)};
-        const void *const rk8[] = {reinterpret_cast<const void *>(sbr_rows_kernel<8, false>), reinterpret_cast<const void *>(sbr_rows_kernel<8, true>),
-                                   reinterpret_cast<const void *>(sbr_rows_general_kernel<8, false>), reinterpret_cast<const void *>(sbr_rows_general_kernel<8, true>)};
-        for (const void *f : rk16) BSP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, Rw<16>::LDS));
-        for (const void *f : rk8) BSP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, Rw<8>::LDS));
+        BSP_HIP(allow_lds(sb16st_kernel, SB16_LDS));
+        BSP_HIP(allow_lds(sbr_rows_kernel<16, false>, Rw<16>::LDS));
+        BSP_HIP(allow_lds(sbr_rows_kernel<16, true>, Rw<16>::LDS));
+        BSP_HIP(allow_lds(sbr_rows_kernel<8, false>, Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows_kernel<8, true>, Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows_general_kernel<8, false>, Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows_general_kernel<8, true>, Rw<8>::LDS));
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(sbr_rows_kernel<8, false>), SB16R_THREADS,
                                                          Rw<8>::LDS) == hipSuccess && nb >= 1) wg8 = nb > 2 ? 2 : nb;
@@ -1581,11 +1517,7 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
     if (opts().sb2st_ring > 0) P = opts().sb2st_ring;
     else if (hb == 16) P = batch > 128 ? 1 : (batch > 64 ? 2 : (batch > 32 ? 4 : 8));
     else {
-        int cus = 256;
-        hipDeviceProp_t prop;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
+        const int cus = device_cus();
         // one workgroup per CU while that gives a channel four members, two per CU (what the LDS holds) beyond: measured at 128 /
         // 64 channels, chase in ms: four members on one CU each - / 17.7, two per CU 26.1 / 18.9 (eight members), two members 30.8 / -
         const int wgs = opts().sb8_wgs > 0 && opts().sb8_wgs < wg8 ? opts().sb8_wgs : wg8;
@@ -1597,21 +1529,11 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
     }
     if (P > 8) P = 8;
     while (P > 1 && (n - 2) / nsw < 2 * P) P /= 2;         // fewer passes than members: nothing to share
-    static Sb16Ctl *s_ctl = nullptr;
-    static int cap = 0;
     Sb16Ctl *d_ctl = nullptr;
     static_assert(sizeof(Sb16Ctl) <= 112, "the caller's per-problem control block is sized for sb2st.hip's Sb8Ctl (112 bytes per channel)");
-    if (P > 1 && ctl) {                                     // the problem's own control block (capi.hip: PipeBufs::sbctl)
+    if (P > 1) {                                            // the caller's own control block (capi.hip: PipeBufs::sbctl)
+        if (!ctl) return BSP_ERR_ARG;
         d_ctl = static_cast<Sb16Ctl *>(ctl);
-        BSP_HIP(hipMemsetAsync(d_ctl, 0, (size_t)batch * sizeof(Sb16Ctl), st));
-    }
-    else if (P > 1) {
-        if (cap < batch) {
-            if (s_ctl) hipFree(s_ctl);
-            BSP_HIP(hipMalloc(reinterpret_cast<void **>(&s_ctl), (size_t)batch * sizeof(Sb16Ctl)));
-            cap = batch;
-        }
-        d_ctl = s_ctl;
         BSP_HIP(hipMemsetAsync(d_ctl, 0, (size_t)batch * sizeof(Sb16Ctl), st));
     }
     const int nblk = P > 1 ? ((batch + 7) / 8) * 8 * P : batch;

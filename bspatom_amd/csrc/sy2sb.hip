@@ -19,6 +19,7 @@
 // after a sub-panel is factored its block reflector (I - V_s T_s^T V_s^T) is applied to the
 // remaining panel columns CW = 4 at a time, streaming them through registers.
 #include "common.h"
+#include "wave_ops.h"
 #include <vector>
 
 namespace bsp {
@@ -246,41 +247,17 @@ __global__ __launch_bounds__(PQ_THREADS) void panel_qr_kernel(int npad, int r0, 
 // 2 x 4096 doubles = 128 KB of LDS); larger panels use the kernel above.
 constexpr int CW2 = 2;
 
-template <int CTRL>
-__device__ __forceinline__ double pq_dpp(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-__device__ __forceinline__ double pq_lane(double x, int l)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_readlane(u.i[0], l);
-    r.i[1] = __builtin_amdgcn_readlane(u.i[1], l);
-    return r.d;
-}
-__device__ __forceinline__ double pq_wave_sum(double x)
-{
-    x += pq_dpp<0x111>(x); x += pq_dpp<0x112>(x); x += pq_dpp<0x114>(x); x += pq_dpp<0x118>(x);   // row_shr 1, 2, 4, 8
-    return (pq_lane(x, 15) + pq_lane(x, 31)) + (pq_lane(x, 47) + pq_lane(x, 63));
-}
-__device__ __forceinline__ void pq_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <int NV>
 __device__ __forceinline__ void block_allreduce2(double (&v)[NV], double *red, int lane, int wave)
 {
     constexpr int NW = PQ_THREADS / 64;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = pq_wave_sum(v[i]);
+    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) red[wave * NV + i] = v[i];
     }
-    pq_barrier();
+    lds_barrier();
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         double s = 0.0;
@@ -291,7 +268,7 @@ __device__ __forceinline__ void block_allreduce2(double (&v)[NV], double *red, i
         // kernel's register count
         if ((i & 1) == 1) asm volatile("" : "+v"(v[i]), "+v"(v[i - 1])::"memory");
     }
-    pq_barrier();
+    lds_barrier();
 }
 
 template <int RPT>
@@ -452,7 +429,7 @@ __global__ __launch_bounds__(PQ_THREADS) void panel_qr2_kernel(int npad, int r0,
                 // everything this wave issued before those RPT loads -- group gi's LDS-DMA, older stores -- is done
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RPT) : "memory");
             } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            pq_barrier();                                  // ... for every wave: buffer b is complete
+            lds_barrier();                                  // ... for every wave: buffer b is complete
             const double *X = xs + (size_t)b * CW2 * MP;
             double wp[SW * CW2];
 #pragma unroll
@@ -492,7 +469,7 @@ __global__ __launch_bounds__(PQ_THREADS) void panel_qr2_kernel(int npad, int r0,
                     else if (i < m) P[i + (size_t)(cs + cc) * ld] = x;
                 }
             }
-            pq_barrier();                                  // buffer b may be overwritten by the prefetch after next
+            lds_barrier();                                  // buffer b may be overwritten by the prefetch after next
         }
         if (KEEP) {
 #pragma unroll
@@ -594,8 +571,7 @@ static void launch_pq(int npad, int r0, int c0, int batch, double *A, double *bu
         const size_t lds = (size_t)(2 * CW2 * PQ_THREADS * RPT + 128) * sizeof(double);
         static bool attr[17] = {};
         if (!attr[RPT]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(panel_qr2_kernel<RPT>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)allow_lds(panel_qr2_kernel<RPT>, lds);
             attr[RPT] = true;
         }
         hipLaunchKernelGGL((panel_qr2_kernel<RPT>), dim3(batch), dim3(PQ_THREADS), lds, st, npad, r0, c0, A, buf, tau);
@@ -648,10 +624,6 @@ int sy2sb_panel_only(int npad, int c0, int batch, double *d_A, const Sy2sbWork &
 // Look-ahead schedule: after the block column that holds the next panel has been updated (syr2k
 // part 1), QR(p+1), T and W(p+1) run on a side stream while the rest of the HBM-bound update
 // (part 2) proceeds on the main stream; the two [V|Z|V] buffers alternate between panels.
-struct Sy2sbLane {                       // one pipeline: main + high-priority side stream and their events
-    hipStream_t main = nullptr, side = nullptr;
-    hipEvent_t evA = nullptr, evB = nullptr, done = nullptr;
-};
 
 // one panel step of one pipeline (p = -1: the first panel's QR, T, W)
 static int sy2sb_panel(int npad, int batch, double *d_A, const Sy2sbWork &w, hipStream_t st, const Sy2sbLane &ln,
@@ -727,43 +699,39 @@ static int sy2sb_pipeline(int npad, int batch, double *d_A, const Sy2sbWork &w, 
 // panel QR (one workgroup per channel) cannot fill the chip.  The channels are therefore split into groups that run
 // the whole pipeline independently on their own streams: while one group factors a panel the other keeps the
 // chip busy with its GEMMs.  BSP_SY2SB_GROUPS (default 2; 1 = a single pipeline on the caller's stream).
-int sy2sb_run(int npad, int nb, int batch, double *d_A, const Sy2sbWork &w, hipStream_t st)
+int sy2sb_run(LaunchCtx &cx, int npad, int nb, int batch, double *d_A, const Sy2sbWork &w, hipStream_t st)
 {
     if (nb != NB || npad % NB != 0) return BSP_ERR_ARG;
     if (opts().panel_qr < 3 && npad - NB > PQ_THREADS * 16) return BSP_ERR_UNSUPPORTED;   // the one-workgroup panel kernels: n <= 8256
     if (opts().panel_qr >= 3) BSP_HIP(hipMemsetAsync(w.tsqr_cntr, 0, (size_t)batch * tsqr_cntr_ints(npad) * sizeof(int), st));
-    constexpr int MAXG = 4;
-    static Sy2sbLane lanes[MAXG];
-    static hipEvent_t fork = nullptr;
-    static bool lanes_ready = false;
+    Sy2sbLane *const lanes = cx.lanes;
     const int lookahead = opts().sy2sb_lookahead;
-    int groups = opts().sy2sb_groups;
-    if (groups < 1) groups = 1;
-    if (groups > MAXG) groups = MAXG;
-    if (!lanes_ready) {
-        lanes_ready = true;
+    int ng = opts().sy2sb_groups;
+    if (ng < 1) ng = 1;
+    if (ng > SY2SB_MAXG) ng = SY2SB_MAXG;
+    if (batch < 16 * ng) ng = 1;                   // small batches: one pipeline
+    // the ctx's lanes, each at the first run that has it (Sy2sbLane, common.h)
+    for (int g = 0; g < ng; ++g) {
+        if (lanes[g].done) continue;
         int plo = 0, phi = 0;                      // the latency-bound panel work gets the high-priority queue
         BSP_HIP(hipDeviceGetStreamPriorityRange(&plo, &phi));
         // (Giving the panel streams compute units of their own through CU masks -- a panel-QR workgroup needs a whole
         // CU and waits between GEMM workgroups that take half a CU each -- was tried: 32/64/96 reserved CUs cost
         // 20-37 % of the stage; the GEMMs need every CU's memory pipeline.)
-        for (int g = 0; g < MAXG; ++g) {
-            BSP_HIP(hipStreamCreateWithFlags(&lanes[g].main, hipStreamNonBlocking));
-            BSP_HIP(hipStreamCreateWithPriority(&lanes[g].side, hipStreamNonBlocking, phi));
-            BSP_HIP(hipEventCreateWithFlags(&lanes[g].evA, hipEventDisableTiming));
-            BSP_HIP(hipEventCreateWithFlags(&lanes[g].evB, hipEventDisableTiming));
-            BSP_HIP(hipEventCreateWithFlags(&lanes[g].done, hipEventDisableTiming));
-        }
-        BSP_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+        if (!lanes[g].main) BSP_HIP(hipStreamCreateWithFlags(&lanes[g].main, hipStreamNonBlocking));
+        if (!lanes[g].side) BSP_HIP(hipStreamCreateWithPriority(&lanes[g].side, hipStreamNonBlocking, phi));
+        if (!lanes[g].evA) BSP_HIP(hipEventCreateWithFlags(&lanes[g].evA, hipEventDisableTiming));
+        if (!lanes[g].evB) BSP_HIP(hipEventCreateWithFlags(&lanes[g].evB, hipEventDisableTiming));
+        BSP_HIP(hipEventCreateWithFlags(&lanes[g].done, hipEventDisableTiming));
     }
-    int ng = groups;
-    if (batch < 16 * ng) ng = 1;                   // small batches: one pipeline
     if (ng == 1) return sy2sb_pipeline(npad, batch, d_A, w, st, lanes[0], lookahead);
+    if (!cx.sy_fork) BSP_HIP(hipEventCreateWithFlags(&cx.sy_fork, hipEventDisableTiming));
+    hipEvent_t fork = cx.sy_fork;
     BSP_HIP(hipEventRecord(fork, st));
     const size_t bsA = (size_t)npad * npad, bsBuf = (size_t)npad * 3 * NB, bsW = (size_t)npad * NB, bsS = (size_t)NB * NB;
     int rc = BSP_OK, c0 = 0;
-    Sy2sbWork wg[MAXG];
-    int cnt[MAXG], first[MAXG];
+    Sy2sbWork wg[SY2SB_MAXG];
+    int cnt[SY2SB_MAXG], first[SY2SB_MAXG];
     for (int g = 0; g < ng; ++g) {
         cnt[g] = batch / ng + (g < batch % ng ? 1 : 0);
         first[g] = c0;

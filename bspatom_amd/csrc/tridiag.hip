@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <vector>
 #include "common.h"
+#include "wave_ops.h"
 
 namespace bsp {
 
@@ -353,10 +354,6 @@ __device__ __forceinline__ bool bracket_final(double lo, double hi)
 }
 
 // a value that is the same in every lane, moved to scalar registers (bit for bit)
-__device__ __forceinline__ double uniform_double(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
 
 // dynamic LDS of bisect3_kernel<EPT, TPB> for n rows (ng = TPB * EPT evaluation slots)
 static size_t bisect3_lds_bytes(int n, int ng)
@@ -461,8 +458,8 @@ __global__ __launch_bounds__(TPB) void bisect3_kernel(int n, int ldn, const doub
         gu = gu * sc + 2.1 * eps * n + 1e-300;
 
         // the same in every lane, and live through the items: in scalar registers
-        gl = uniform_double(gl); gu = uniform_double(gu);
-        isc = uniform_double(isc_v);
+        gl = read_first_lane(gl); gu = read_first_lane(gu);
+        isc = read_first_lane(isc_v);
     };
     const int nwl = (n + NG - 1) / NG;                 // logical workgroups of a channel
     int side = -1;                                     // DIAG: the workgroup's arrival number on its CU
@@ -893,8 +890,7 @@ int launch_bisect_one(int n, const double *d_d, const double *d_e, int m, double
         if (lds3 > 150 * 1024) return BSP_ERR_UNSUPPORTED;
         static bool attr3 = false;
         if (!attr3) {
-            BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect_one3_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            BSP_HIP(allow_lds(bisect_one3_kernel, 150 * 1024));
             attr3 = true;
         }
         hipLaunchKernelGGL(bisect_one3_kernel, dim3(1), dim3(256), lds3, st, n, d_d, d_e, m, d_out);
@@ -905,8 +901,7 @@ int launch_bisect_one(int n, const double *d_d, const double *d_e, int m, double
     if (lds > 150 * 1024) return BSP_ERR_UNSUPPORTED;
     static bool attr = false;
     if (!attr) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect_one_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(allow_lds(bisect_one_kernel, 150 * 1024));
         attr = true;
     }
     hipLaunchKernelGGL(bisect_one_kernel, dim3(1), dim3(64), lds, st, n, d_d, d_e, m, d_out);
@@ -914,8 +909,7 @@ int launch_bisect_one(int n, const double *d_d, const double *d_e, int m, double
     return BSP_OK;
 }
 
-int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_e, double *d_w, long ldw,
-                  hipStream_t st)
+int launch_bisect(LaunchCtx &cx, int n, int ldn, int batch, const double *d_d, const double *d_e, double *d_w, long ldw, hipStream_t st)
 {
     // ONE workgroup shape for every batch size: 512 threads x 2 eigenvalues = 1024 evaluation slots and 1024 eigenvalues per
     // workgroup.  The bracket sequence of an eigenvalue depends on the first-level grid (its size = the slots) and on which
@@ -935,49 +929,33 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
     while (bisect3_lds_bytes(nl, ng) > 150 * 1024) nl -= HW;
     const size_t lds3 = bisect3_lds_bytes(nl, ng);
     const size_t lds = (size_t)2 * (n + 3 * RS + HW) * sizeof(double);    // variants 1 and 2
-    // rows beyond the LDS (n > 8672): one scratch array PER STREAM (launches of a stream are ordered, so a stream may reuse its
-    // own; two problems bisecting at the same time on their own streams no longer share rows -- round-3 advisor), grown on demand
-    struct Tail { hipStream_t st; double2 *p; size_t cap; };
-    static std::vector<Tail> g_tails;
+    // rows beyond the LDS (n > 8672): one scratch array of the ctx (a ctx bisects on one stream, whose launches are ordered, so it may
+    // reuse its own; two problems bisecting at the same time share no rows), grown on demand
     double2 *gtail = nullptr;
     if (nl < np3) {
         const size_t need = (size_t)batch * (np3 + 1);
-        Tail *tl = nullptr;
-        for (auto &x : g_tails) if (x.st == st) tl = &x;
-        if (!tl) { g_tails.push_back({st, nullptr, 0}); tl = &g_tails.back(); }
-        if (need > tl->cap) {
-            if (tl->p) { BSP_HIP(hipStreamSynchronize(st)); (void)hipFree(tl->p); tl->p = nullptr; tl->cap = 0; }
-            BSP_HIP(hipMalloc(reinterpret_cast<void **>(&tl->p), need * sizeof(double2)));
-            tl->cap = need;
+        if (need > cx.bis_tail_cap) {
+            if (cx.bis_tail) { BSP_HIP(hipStreamSynchronize(st)); (void)hipFree(cx.bis_tail); cx.bis_tail = nullptr; cx.bis_tail_cap = 0; }
+            BSP_HIP(hipMalloc(reinterpret_cast<void **>(&cx.bis_tail), need * sizeof(double2)));
+            cx.bis_tail_cap = need;
         }
-        gtail = tl->p;
+        gtail = cx.bis_tail;
         if (opts().bisect < 3) return BSP_ERR_UNSUPPORTED;                  // the older counting kernels keep the whole matrix in LDS
     }
     static bool attr_set = false;
     const int variant = opts().bisect;
     if (!attr_set) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect2_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<4, 256>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<8, 256>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<4, 512>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 1024>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 256>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bisect3_kernel<2, 512, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BSP_HIP(allow_lds(bisect_kernel, 150 * 1024));
+        BSP_HIP(allow_lds(bisect2_kernel, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<4, 256>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<8, 256>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<4, 512>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<2, 1024>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<2, 256>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<2, 512>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<2, 512, true>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<2, 512, false, true>, 150 * 1024));
+        BSP_HIP(allow_lds(bisect3_kernel<2, 512, true, true>, 150 * 1024));
         attr_set = true;
     }
     const dim3 grid((n + 256 * EPT - 1) / (256 * EPT), batch);
@@ -992,12 +970,7 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
     // CUs anyway, and the dispatcher deals them out so that the slow quarters of the spectra share theirs.  The rule
     // looks at the batch size -- allowed here because the schedule cannot change a bit of the result.
     // BSP_BISECT_PAIR: 1 = by this rule, 0 = never, 2 = always.
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        BSP_HIP(hipGetDevice(&dev));
-        BSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    const int cus = device_cus();
     const int nw = (n + ng - 1) / ng;
     const int pmode = opts().bisect_pair;
     // The item queue (bisect3_kernel, QUEUE): at most two hardware workgroups per CU claim the nw x batch logical workgroups from a list,
@@ -1012,17 +985,12 @@ int launch_bisect(int n, int ldn, int batch, const double *d_d, const double *d_
     int qgrid = (int)std::min(items, 2L * cus);
     if (opts().bisect_queue_grid > 0) qgrid = std::min(qgrid, opts().bisect_queue_grid);
     const dim3 g3 = queue ? dim3(qgrid, 1) : dim3(pair_stride ? pair_stride : nw, batch);
-    // the queue's counters (arrival table, claimed, head, tail): one small array PER STREAM like the rows above, zeroed on the stream in
+    // the queue's counters (arrival table, claimed, head, tail): one small array of the ctx like the rows above, zeroed on the stream in
     // front of every launch
-    struct QCount { hipStream_t st; unsigned *p; };
-    static std::vector<QCount> g_qcounts;
     unsigned *qcnt = nullptr;
     if (queue) {
-        for (auto &x : g_qcounts) if (x.st == st) qcnt = x.p;
-        if (!qcnt) {
-            BSP_HIP(hipMalloc(reinterpret_cast<void **>(&qcnt), BISECT_Q_WORDS * sizeof(unsigned)));
-            g_qcounts.push_back({st, qcnt});
-        }
+        if (!cx.bis_qcnt) BSP_HIP(hipMalloc(reinterpret_cast<void **>(&cx.bis_qcnt), BISECT_Q_WORDS * sizeof(unsigned)));
+        qcnt = cx.bis_qcnt;
         BSP_HIP(hipMemsetAsync(qcnt, 0, BISECT_Q_WORDS * sizeof(unsigned), st));
     }
     // (measured with BSP_BISECT_DIAG, 128 channels of n = 4096: the 256 paired workgroups land on 256 different CUs although two would fit

@@ -26,6 +26,7 @@
 //                     [V | . | V] and W written where sy2sb's products expect them, S' R on top of the panel, zeros below.
 // Results do not depend on the batch size, on which workgroup runs a node, or on timing: bit-identical from run to run.
 #include "common.h"
+#include "wave_ops.h"
 
 namespace bsp {
 namespace {
@@ -53,26 +54,6 @@ struct TsqrArgs {
     TsqrPlan plan;
 };
 
-template <int CTRL>
-__device__ __forceinline__ double tq_dpp(double x)
-{
-    union { double d; int i[2]; } u, r;
-    u.d = x;
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, 0xf, 0xf, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, 0xf, 0xf, true);
-    return r.d;
-}
-// Sum over the 16 lanes of a DPP row, the total in every lane (bitwise the same in all of them: each step adds the two halves of
-// a pair): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror.
-__device__ __forceinline__ double tq_rsum16(double x)
-{
-    x += tq_dpp<0xB1>(x);
-    x += tq_dpp<0x4E>(x);
-    x += tq_dpp<0x141>(x);
-    x += tq_dpp<0x140>(x);
-    return x;
-}
-__device__ __forceinline__ void tq_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- the 256 x 64 block in registers: thread (rg = lane & 15, cg = tid >> 4) holds a[i][jj] = element (rg + 16 i, cg + 16 jj).
 // Column j = 16 JJ + j16 lives in register column JJ of the 16 threads with cg == j16 (one DPP row); rows < 16 JJ are finished.
@@ -85,7 +66,7 @@ __device__ __forceinline__ void tq_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\
         _Pragma("unroll") for (int i = (I0); i < 16; ++i) {                                 \
             if (i & 1) s1_ += v[i] * a[i][JJX]; else s0_ += v[i] * a[i][JJX];               \
         }                                                                                   \
-        const double w_ = (ON) ? tau * tq_rsum16(s0_ + s1_) : 0.0;                          \
+        const double w_ = (ON) ? tau * rsum16(s0_ + s1_) : 0.0;                          \
         _Pragma("unroll") for (int i = (I0); i < 16; ++i) a[i][JJX] -= w_ * v[i];           \
     }
 
@@ -102,8 +83,8 @@ __device__ __forceinline__ void tq_house(double (&a)[16][4], int jn16, double *v
         if (i & 1) s1 += a[i][JN] * a[i][JN]; else s0 += a[i][JN] * a[i][JN];
     }
     const double x0 = a[JN][JN];
-    const double sigma = tq_rsum16((s0 + s1) + (rg > jn16 ? x0 * x0 : 0.0));
-    const double alpha = tq_rsum16(rg == jn16 ? x0 : 0.0);
+    const double sigma = rsum16((s0 + s1) + (rg > jn16 ? x0 * x0 : 0.0));
+    const double alpha = rsum16(rg == jn16 ? x0 : 0.0);
     const double n2 = alpha * alpha + sigma;
     const bool ok = sigma != 0.0 && n2 > 1e-280;
     const double nrm = sqrt(ok ? n2 : 1.0);
@@ -147,7 +128,7 @@ __device__ __forceinline__ void tq_qr_step(double (&a)[16][4], double *vb, doubl
         if (jj == JJ) TQ_UPD(JJ, JJ, onJ)
         else TQ_UPD(JJ, jj, true)
     }
-    tq_bar();
+    lds_barrier();
 }
 
 template <int JJ>
@@ -162,7 +143,7 @@ __device__ __forceinline__ void tq_qr_cols(double (&a)[16][4], double *vb, doubl
 __device__ __forceinline__ void tq_qr(double (&a)[16][4], double *vb, double *taus, int rg, int cg)
 {
     tq_house<0>(a, 0, vb, taus, rg, cg);
-    tq_bar();
+    lds_barrier();
     tq_qr_cols<0>(a, vb, taus, rg, cg);
     tq_qr_cols<1>(a, vb, taus, rg, cg);
     tq_qr_cols<2>(a, vb, taus, rg, cg);
@@ -210,14 +191,14 @@ __device__ __forceinline__ void tq_formq_cols(double (&a)[16][4], double *vb, co
             }
             a[JJ][JJ] = rg > j16 ? -tau * v[JJ] : (rg == j16 ? 1.0 - tau : 0.0);
         }
-        tq_bar();
+        lds_barrier();
     }
 }
 
 __device__ __forceinline__ void tq_formq(double (&a)[16][4], double *vb, const double *taus, int rg, int cg)
 {
     tq_publish<3>(a, 15, vb + TR, rg, cg);                // v_63 -> buffer 63 & 1 (the QR's last read of it is behind a barrier)
-    tq_bar();
+    lds_barrier();
     tq_formq_cols<3>(a, vb, taus, rg, cg);
     tq_formq_cols<2>(a, vb, taus, rg, cg);
     tq_formq_cols<1>(a, vb, taus, rg, cg);
@@ -319,7 +300,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
     // (leaf first).  This workgroup's own factor (the root's) comes from its registers.
     const int top = pl.nlev - 1;
     double *mine = top > 0 ? Y : X;
-    tq_bar();                                        // the last v buffer of the Q formation has been read by everyone
+    lds_barrier();                                        // the last v buffer of the Q formation has been read by everyone
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
@@ -333,7 +314,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
 #pragma unroll
             for (int u = 0; u < 16; ++u) { const int idx = tid + 256 * u; X[(idx & 63) + XS * (idx >> 6)] = tmp[u]; }
         }
-        tq_bar();
+        lds_barrier();
         for (int l = 1; l <= top; ++l) {             // X <- X . (top block of the level-l node 0's Q); the root's is in Y
             const double *Bp = l < top ? Qall + (long)pl.base[l] * (TR * TB) : Y;
             const long sBn = l < top ? TR : XS;
@@ -355,14 +336,14 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
 #pragma unroll
                     for (int y = 0; y < 4; ++y) acc[x][y] += av[x] * bv[y];
             }
-            tq_bar();                                // every thread has read X
+            lds_barrier();                                // every thread has read X
 #pragma unroll
             for (int x = 0; x < 4; ++x)
 #pragma unroll
                 for (int y = 0; y < 4; ++y) X[(r4 + x) + XS * (c4 + y)] = acc[x][y];
-            tq_bar();
+            lds_barrier();
         }
-    } else tq_bar();
+    } else lds_barrier();
 
     // ---- modified LU of X = Q11 - S' (S' chosen on the fly: s_j = -sgn of the partially eliminated diagonal, |pivot| >= 1), then
     // T = -U S' L^-T and U^-1, all in REGISTERS: thread (br = tid & 15, bc = tid >> 4) owns the 4 x 4 block (rows 4 br.., columns
@@ -389,7 +370,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
 #pragma unroll
                 for (int ro = 0; ro < 4; ++ro) Lcol[p + 4 * br + ro] = x[ro][jo];
             }
-            tq_bar();
+            lds_barrier();
             const double d = Urow[p + j];
             const double sj = d >= 0.0 ? -1.0 : 1.0;
             const double piv = d - sj, rp = 1.0 / piv;
@@ -411,7 +392,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
             if (tid == 0) sg[j] = sj;
         }
     }
-    tq_bar();
+    lds_barrier();
     // t = Y = -U S' (upper triangle), ui = I;  then, in one loop of 64 steps: column c = it of T is final and leaves the columns
     // right of it (T L^T = Y), row k = 63 - it of U^-1 is final and leaves the rows above it (U U^-1 = I)
 #pragma unroll
@@ -445,7 +426,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
 #pragma unroll
                 for (int ro = 0; ro < 4; ++ro) Ucol[p + 4 * br + ro] = (4 * br + ro <= k) ? x[ro][kj] : 0.0;   // U(r, k), r <= k
             }
-            tq_bar();
+            lds_barrier();
             {
                 double tc[4], lc[4];
 #pragma unroll
@@ -477,7 +458,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
     }
     // ---- results: U^-1, T (row-major, ld 64) and S' to scratch for tsqr_apply_kernel; L (unit lower) -> X, T -> Y for W_top = L T
     double *Ui = scr + g.offUi, *Tm = scr + g.offT, *Sm = scr + g.offS;
-    tq_bar();
+    lds_barrier();
 #pragma unroll
     for (int ro = 0; ro < 4; ++ro)
 #pragma unroll
@@ -489,7 +470,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_tree_kernel(TsqrArgs g)
             Y[r + XS * c] = r <= c ? t[ro][co] : 0.0;
         }
     if (tid < TB) Sm[tid] = sg[tid];
-    tq_bar();
+    lds_barrier();
     // ---- top 64 rows of V (= L: exact unit lower triangle) and of W = L T
     double *buf = g.buf + (long)ch * g.bsBuf, *Wg = g.W + (long)ch * g.bsW;
     {
@@ -579,7 +560,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_apply_kernel(TsqrArgs g)
         for (int u = 0; u < 16; ++u) tmp[u] = Ui[tid + 256 * u];
 #pragma unroll
         for (int u = 0; u < 16; ++u) { const int idx = tid + 256 * u; M0[(idx >> 6) * BS + (idx & 63)] = tmp[u]; }
-        tq_bar();
+        lds_barrier();
         __syncthreads();
         BV = M0; BW = M1;
     } else {
@@ -594,18 +575,18 @@ __global__ __launch_bounds__(256, MINW) void tsqr_apply_kernel(TsqrArgs g)
 #pragma unroll
             for (int u = 0; u < 16; ++u) { const int e = tid + 256 * u; cur[(e & 63) * BS + (e >> 6)] = tmp[u]; }
         }
-        tq_bar();
+        lds_barrier();
         __syncthreads();
         for (int l = 2; l < pl.nlev; ++l) {
             const int k = idx & 3; idx >>= 2;
             const double *Qp = Qall + (long)(pl.base[l] + idx) * (TR * TB) + TB * k;
             tq_mm64m(cur, Qp, 1, TR, oth, lane, wave);
-            tq_bar();
+            lds_barrier();
             __syncthreads();
             double *t = cur; cur = oth; oth = t;
         }
         tq_mm64m(cur, Ui, TB, 1, oth, lane, wave);
-        tq_bar();
+        lds_barrier();
         __syncthreads();
         BV = oth; BW = cur;
     }
@@ -629,7 +610,7 @@ __global__ __launch_bounds__(256, MINW) void tsqr_apply_kernel(TsqrArgs g)
             }
         }
     }
-    tq_bar();
+    lds_barrier();
     __syncthreads();
     // ---- V = Q_leaf BV, W = Q_leaf BW on the matrix cores: wave w owns rows 64 w .. 64 w + 63 of the block, in two halves of 32;
     // the products are formed transposed (MFMA(b, a)), so that a DPP row of 16 lanes stores 16 consecutive rows of one column
@@ -732,10 +713,10 @@ int tsqr_panel(int npad, int r0, int c0, int batch, double *d_A, double *buf, do
     g.bsCntr = tsqr_cntr_ints(npad);
     static bool attr = false;
     if (!attr) {
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tsqr_tree_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, TQ_LDS_TREE));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tsqr_apply_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, TQ_LDS_APPLY));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tsqr_tree_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, TQ_LDS_TREE));
-        BSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tsqr_apply_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, TQ_LDS_APPLY));
+        BSP_HIP(allow_lds(tsqr_tree_kernel<1>, TQ_LDS_TREE));
+        BSP_HIP(allow_lds(tsqr_apply_kernel<1>, TQ_LDS_APPLY));
+        BSP_HIP(allow_lds(tsqr_tree_kernel<2>, TQ_LDS_TREE));
+        BSP_HIP(allow_lds(tsqr_apply_kernel<2>, TQ_LDS_APPLY));
         attr = true;
     }
     const dim3 grid(g.plan.cnt[0], batch);
