@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_resolvent", "bspatom_resolvent_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_tdse_adaptive", "bspatom_tdse_adaptive_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_resolvent", "bspatom_resolvent_dev", "bspatom_resolvent_chain", "bspatom_resolvent_chain_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_tdse_adaptive", "bspatom_tdse_adaptive_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -76,6 +76,8 @@ def lib():
         L.bspatom_operator_matrix_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.bspatom_resolvent.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.bspatom_resolvent_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.bspatom_resolvent_chain.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.bspatom_resolvent_chain_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.bspatom_write_wf.argtypes = [vp, vp, i32, vp, vp]
         L.bspatom_quadrature.argtypes = [vp, C.POINTER(i32), vp, vp]
         L.bspatom_tabulate.argtypes = [vp, i32, vp, i32, vp, vp, vp]
@@ -363,6 +365,70 @@ class Problem:
         vp = lambda a: None if a is None else C.c_void_p(a)
         _chk(lib().bspatom_resolvent_dev(self._h, nmat, _p(l), _p(z), nabs, vp(W_ptr), _p(w), nrhs, vp(B_ptr), nproj, vp(P_ptr),
                                          vp(X_ptr), vp(R_ptr), _p(info)), "bspatom_resolvent_dev")
+        return info
+
+    @staticmethod
+    def _chain_stages(l, z, w, a, nop):
+        """(nchain, nstage, l int32, z complex128, w int32 or None, a float64 or None), each (nchain, nstage) -- a (nchain, nstage-1,
+        nop) -- and contiguous; l, z, w broadcast from (nstage,) or scalars, a from (nstage-1, nop) or, with one operator, (nstage-1,);
+        a None with one operator means coefficient 1"""
+        l, z = np.asarray(l, dtype=np.int32), np.asarray(z, dtype=np.complex128)
+        w = None if w is None else np.asarray(w, dtype=np.int32)
+        shape = np.broadcast_shapes(l.shape, z.shape, () if w is None else w.shape)
+        assert len(shape) <= 2, shape
+        nchain, nstage = (1,) * (2 - len(shape)) + tuple(shape)
+        assert nstage >= 1, shape
+        if nstage == 1:
+            a = None
+        else:
+            assert nop >= 1, "a chain of more than one stage needs operator bands G"
+            a = np.ones((nstage - 1, nop)) if a is None and nop == 1 else a
+            assert a is not None, "a (nchain, nstage-1, nop) is needed with more than one operator"
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 1 and nop == 1:
+                a = a[:, None]
+            if a.ndim == 3 and nchain == 1:
+                nchain = a.shape[0]
+            a = np.ascontiguousarray(np.broadcast_to(a, (nchain, nstage - 1, nop)))
+        bc = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(v, (nchain, nstage)))
+        return nchain, nstage, bc(l), bc(z), bc(w), a
+
+    def resolvent_chain(self, l, z, B, G=None, a=None, W=None, w=None, P=None, want_x=True):
+        """Chains of resolvents with an operator in between, every chain on the GPU from its first factorisation to its last
+        projection in one call (bspatom_resolvent_chain): x[c, 0, r] = M[c, 0]^-1 B[r], x[c, s, r] = M[c, s]^-1 A[c, s] x[c, s-1, r],
+        M[c, s] = H_l[c, s] - i W_w[c, s] - z[c, s] S, A[c, s] = sum_o a[c, s-1, o] G[o].  l, z, w: (nchain, nstage), broadcast from
+        (nstage,) or scalars; G: full bands (nop, 2k-1, nfun) or (2k-1, nfun) as dipole_bands / operator_bands return them (None
+        with one stage); a: real, (nchain, nstage-1, nop), broadcast from (nstage-1, nop), None with one operator: coefficient 1.
+        B, W, P as in resolvent.  Returns (X, R, info): X (nchain, nrhs, nfun) complex128, the LAST stage's solutions, or None
+        (want_x False); R (nchain, nstage, nrhs, nproj) complex128, sum_i P[q, i] x[c, s, r, i] of EVERY stage (bilinear), or None
+        (P None); info (nchain, nstage) replaced pivots (0).  A chain cut to s+1 stages gives the same R, info of those stages bit
+        for bit and x[c, s] as its X; one stage is resolvent bit for bit."""
+        n = self.nfun
+        B = np.ascontiguousarray(np.asarray(B, dtype=np.complex128).reshape(-1, n))
+        P = None if P is None else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, n))
+        W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
+        G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
+        nabs, nop = 0 if W is None else W.shape[0], 0 if G is None else G.shape[0]
+        nchain, nstage, l, z, w, a = self._chain_stages(l, z, w, a, nop)
+        nrhs, nproj = B.shape[0], 0 if P is None else P.shape[0]
+        X = np.zeros((nchain, nrhs, n), dtype=np.complex128) if want_x else None
+        R = np.zeros((nchain, nstage, nrhs, nproj), dtype=np.complex128) if P is not None else None
+        info = np.zeros((nchain, nstage), dtype=np.int32)
+        _chk(lib().bspatom_resolvent_chain(self._h, nchain, nstage, _p(l), _p(z), nabs, _p(W), _p(w), nop, _p(G), _p(a), nrhs, _p(B),
+                                           nproj, _p(P), _p(X), _p(R), _p(info)), "bspatom_resolvent_chain")
+        return X, R, info
+
+    def resolvent_chain_dev(self, l, z, nrhs, B_ptr, nop=0, G_ptr=None, a=None, nabs=0, W_ptr=None, w=None, nproj=0, P_ptr=None,
+                            X_ptr=None, R_ptr=None):
+        """resolvent_chain with B (nrhs * nfun complex), G (nop * (2k-1) * nfun doubles), W (nabs * (2k-1) * nfun doubles), P (nproj *
+        nfun complex), X (nchain * nrhs * nfun complex) and R (nchain * nstage * nrhs * nproj complex) in device memory of this
+        problem's device, e.g. torch tensors' data_ptr(); X and R are written in place (either pointer may be None).  l, z, w, a are
+        host values as in resolvent_chain.  Returns info (nchain, nstage)."""
+        nchain, nstage, l, z, w, a = self._chain_stages(l, z, w, a, nop)
+        info = np.zeros((nchain, nstage), dtype=np.int32)
+        vp = lambda v: None if v is None else C.c_void_p(v)
+        _chk(lib().bspatom_resolvent_chain_dev(self._h, nchain, nstage, _p(l), _p(z), nabs, vp(W_ptr), _p(w), nop, vp(G_ptr), _p(a), nrhs,
+                                               vp(B_ptr), nproj, vp(P_ptr), vp(X_ptr), vp(R_ptr), _p(info)), "bspatom_resolvent_chain_dev")
         return info
 
     def write_wf(self, c, npts=10000):

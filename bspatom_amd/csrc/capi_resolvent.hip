@@ -1,6 +1,7 @@
 // capi_resolvent.hip -- bspatom_resolvent / bspatom_resolvent_dev (include/bspatom.h): solves with the banded pencil at complex
 // energies, (H_l - i W - z S) x = b, by resolvent.hip's one-wave LU.  The bands are those the problem holds on the device (the
 // last bspatom_solve or bspatom_assemble); all work goes on the problem's stream and the scratch of a call is freed when it returns.
+// bspatom_resolvent_chain / _dev: chains of such solves with an operator in between, one launch for the whole batch.
 #include <algorithm>
 #include "capi_internal.h"
 
@@ -66,6 +67,91 @@ static int resolvent_impl(bspatom_problem *p, int nmat, const int32_t *l, const 
     if (!rc && !dev && R) rc = HIP_RC(hipMemcpyAsync(R, dR.p, r_all * sizeof(double), hipMemcpyDeviceToHost, p->st));
     if (!rc) rc = HIP_RC(hipMemcpyAsync(info, dinfo.p, (size_t)nmat * sizeof(int), hipMemcpyDeviceToHost, p->st));
     return drain(p, rc);
+}
+
+// bspatom_resolvent_chain / _dev: the same plumbing with nchain * nstage matrices, the operator bands and their coefficients beside
+// them, the slots sized by resolvent_chain_kernel (its scratch holds nrhs more vectors), the groups made of whole chains.
+static int resolvent_chain_impl(bspatom_problem *p, int nchain, int nstage, const int32_t *l, const double *z, int nabs, const double *WB,
+                                const int32_t *w, int nop, const double *GB, const double *ac, int nrhs, const double *B, int nproj,
+                                const double *P, double *X, double *R, int32_t *info, bool dev)
+{
+    if (!p || !l || !z || !B || !info || (!X && !R)) return BSP_ERR_ARG;
+    if (nchain < 1 || nstage < 1 || nrhs < 1 || nabs < 0 || nproj < 0 || nop < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
+    if (R && (!P || nproj < 1)) return BSP_ERR_ARG;
+    if (nstage > 1 && (nop < 1 || !GB || !ac)) return BSP_ERR_ARG;
+    if ((long long)nchain * nstage > 0x3fffffffLL) return BSP_ERR_ARG;
+    if (!WB) nabs = 0;
+    const int nmat = nchain * nstage;
+    for (int m = 0; m < nmat; ++m) {
+        if (p->band_nl < 1 || l[m] < p->band_l0 || l[m] >= p->band_l0 + p->band_nl) return BSP_ERR_ARG;
+        if (w && (w[m] < -1 || w[m] >= nabs)) return BSP_ERR_ARG;
+    }
+    const HostSetup &h = p->hs;
+    const int n = h.nfun, k = h.k;
+    const size_t wband = (size_t)(2 * k - 1) * n, stage = opts().resolvent_stage_mb > 0 ? (size_t)opts().resolvent_stage_mb << 20 : RESOLVENT_STAGE_BYTES;
+    BSP_HIP(hipSetDevice(p->device));
+    int rc;
+    int slots = 0;
+    if ((rc = resolvent_chain_slots(k, nchain, &slots))) return rc;
+    if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, nchain);
+    const size_t slot_doubles = resolvent_chain_slot_doubles(n, k, nrhs);
+    slots = (int)std::max<size_t>(1, std::min<size_t>(slots, stage / (slot_doubles * sizeof(double))));
+    // the host variant's groups: the X of one group of chains within the bound, one chain at least
+    const size_t x_chain = (size_t)2 * nrhs * n;                     // doubles of one chain's X
+    int group = nchain;
+    if (!dev && X) group = (int)std::max<size_t>(1, std::min<size_t>(nchain, stage / (x_chain * sizeof(double))));
+    std::vector<int> chan(nmat), wsel(nmat, nabs > 0 && !w ? 0 : -1);
+    for (int m = 0; m < nmat; ++m) { chan[m] = l[m] - p->band_l0; if (w) wsel[m] = w[m]; }
+    const bool ops = nstage > 1;
+    DevArray<double> work, dz, dac, dWB, dGB, dB, dP, dX, dR;
+    DevArray<int> dchan, dw, dinfo;
+    if ((rc = work.alloc((size_t)slots * slot_doubles)) || (rc = dz.put(z, (size_t)2 * nmat)) ||
+        (ops && (rc = dac.put(ac, (size_t)nchain * (nstage - 1) * nop))) ||
+        (rc = dchan.put(chan.data(), nmat)) || (rc = dw.put(wsel.data(), nmat)) || (rc = dinfo.alloc(nmat))) return rc;
+    const size_t r_chain = (size_t)2 * nstage * nrhs * nproj, r_all = r_chain * nchain;
+    if (!dev) {
+        if ((nabs > 0 && (rc = dWB.put(WB, (size_t)nabs * wband))) || (ops && (rc = dGB.put(GB, (size_t)nop * wband))) ||
+            (rc = dB.put(B, (size_t)2 * nrhs * n)) || (R && (rc = dP.put(P, (size_t)2 * nproj * n))) ||
+            (X && (rc = dX.alloc((size_t)group * x_chain))) || (R && (rc = dR.alloc(r_all))))
+            return rc;
+    }
+    ResolventChainArgs a;
+    a.n = n; a.k = k; a.nstage = nstage; a.nop = ops ? nop : 0; a.nrhs = nrhs; a.nproj = R ? nproj : 0;
+    a.SB = p->d_SB; a.HB = p->d_HB;
+    a.WB = nabs > 0 ? (dev ? WB : dWB.p) : nullptr;
+    a.GB = ops ? (dev ? GB : dGB.p) : nullptr;
+    a.B = dev ? B : dB.p;
+    a.P = R ? (dev ? P : dP.p) : nullptr;
+    a.work = work.p;
+    rc = BSP_OK;
+    for (int c0 = 0; !rc && c0 < nchain; c0 += group) {
+        const int g = std::min(group, nchain - c0);
+        const size_t m0 = (size_t)c0 * nstage;
+        a.nchain = g;
+        a.chan = dchan.p + m0; a.z = dz.p + 2 * m0; a.w = dw.p + m0; a.info = dinfo.p + m0;
+        a.acoef = ops ? dac.p + (size_t)c0 * (nstage - 1) * nop : nullptr;
+        a.X = X ? (dev ? X + (size_t)c0 * x_chain : dX.p) : nullptr;
+        a.R = R ? (dev ? R : dR.p) + (size_t)c0 * r_chain : nullptr;
+        rc = launch_resolvent_chain(a, std::min(slots, g), p->st);
+        if (!rc && !dev && X) rc = HIP_RC(hipMemcpyAsync(X + (size_t)c0 * x_chain, dX.p, (size_t)g * x_chain * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc && !dev && R) rc = HIP_RC(hipMemcpyAsync(R, dR.p, r_all * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    if (!rc) rc = HIP_RC(hipMemcpyAsync(info, dinfo.p, (size_t)nmat * sizeof(int), hipMemcpyDeviceToHost, p->st));
+    return drain(p, rc);
+}
+
+extern "C" int bspatom_resolvent_chain(bspatom_problem *p, int nchain, int nstage, const int32_t *l, const double *z, int nabs,
+                                       const double *WB, const int32_t *w, int nop, const double *GB, const double *a, int nrhs,
+                                       const double *B, int nproj, const double *P, double *X, double *R, int32_t *info)
+{
+    return resolvent_chain_impl(p, nchain, nstage, l, z, nabs, WB, w, nop, GB, a, nrhs, B, nproj, P, X, R, info, false);
+}
+extern "C" int bspatom_resolvent_chain_dev(bspatom_problem *p, int nchain, int nstage, const int32_t *l, const double *z, int nabs,
+                                           const double *WB_dev, const int32_t *w, int nop, const double *GB_dev, const double *a,
+                                           int nrhs, const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev,
+                                           int32_t *info)
+{
+    return resolvent_chain_impl(p, nchain, nstage, l, z, nabs, WB_dev, w, nop, GB_dev, a, nrhs, B_dev, nproj, P_dev, X_dev, R_dev, info, true);
 }
 
 extern "C" int bspatom_resolvent(bspatom_problem *p, int nmat, const int32_t *l, const double *z, int nabs, const double *WB,

@@ -347,6 +347,25 @@ struct ResolventArgs {
 size_t resolvent_slot_doubles(int n, int k);
 int resolvent_slots(int k, int nmat, int *slots);
 int launch_resolvent(const ResolventArgs &a, int slots, hipStream_t st);
+// Chains of resolvents (bspatom_resolvent_chain): matrix (c, s) is entry c*nstage + s of chan, z, w, info; x_{c,0,r} = M^-1 B_r,
+// x_{c,s,r} = M_{c,s}^-1 (A_{c,s} x_{c,s-1,r}), A_{c,s} = sum_o acoef[(c*(nstage-1) + s-1)*nop + o] G_o, GB nop full bands
+// [2k-1][n] (nstage == 1: GB, acoef unused).  R[c][s][r][nproj] of every stage, X[c][r][n] of the last (either may be null).
+// work: slots * resolvent_chain_slot_doubles(n, k, nrhs): resolvent_slot_doubles, then the nrhs vectors of the previous stage.
+struct ResolventChainArgs {
+    int n, k, nchain, nstage, nop, nrhs, nproj;
+    const double *SB, *HB;
+    const int *chan;
+    const double *z, *WB;
+    const int *w;
+    const double *GB, *acoef;
+    const double *B, *P;
+    double *X, *R;
+    int *info;
+    double *work;
+};
+size_t resolvent_chain_slot_doubles(int n, int k, int nrhs);
+int resolvent_chain_slots(int k, int nchain, int *slots);
+int launch_resolvent_chain(const ResolventChainArgs &a, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

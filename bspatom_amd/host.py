@@ -861,6 +861,79 @@ def photoabsorption(prob, n_ini, omega, absorber):
     return 4.0 * np.pi * om * polarizability(prob, n_ini, om, absorber).imag / C_RESPONSE
 
 
+def response_chain(prob, l_ini, n_ini, path, z, absorber=None, left=None):
+    """p^T G_s A_s ... G_2 A_2 G_1 A_1 c_i for every row of z: the response of order nstage + 1 of state n_ini (1-based) of channel
+    l_ini, G_j = (H_{l_j} - i W - z_j S)^-1 (Problem.resolvent_chain: every chain on the GPU in one call, no intermediate vector
+    on the host).  path: a list of (l, a3), the channel of each resolvent and the dipole_bands coefficients of the operator in
+    front of it, A = a3[0] R_r + a3[1] R_{1/r} + a3[2] R_{d/dr}; z: (..., nstage), z[..., j] the energy of resolvent j.  left =
+    (l_f, n_f, a3): p = A c_f of a final state (bilinear: for an operator that is not symmetric hand in the coefficients of its
+    transpose); None: p = A_1 c_i, as in response.  A_1 c_i and p are formed as response forms them, so one stage is response
+    bit for bit.  absorber as in response, on every stage.  Every channel must be in the last solve.  Returns complex128 of
+    shape z.shape[:-1]; raises ArithmeticError where response does (a pivot was replaced)."""
+    import numpy as np
+    path = [(int(l), tuple(float(v) for v in a3)) for l, a3 in path]
+    if not path:
+        raise ValueError("path must name at least one (l, a3)")
+    nstage = len(path)
+    zz = np.asarray(z, dtype=np.complex128)
+    if zz.ndim < 1 or zz.shape[-1] != nstage:
+        raise ValueError("z must have shape (..., %d), got %s" % (nstage, zz.shape))
+    RB = prob.dipole_bands()
+    ci = prob.eigvecs(l_ini, n_ini, 1)
+    comb = lambda co: sum(float(co[o]) * RB[o] for o in range(3))
+    b = band_apply(comb(path[0][1]), ci)
+    p = b if left is None else band_apply(comb(left[2]), prob.eigvecs(int(left[0]), int(left[1]), 1))
+    W = _absorber_band(prob, absorber)
+    a = np.array([a3 for _, a3 in path[1:]], dtype=np.float64).reshape(nstage - 1, 3)
+    _, R, info = prob.resolvent_chain([l for l, _ in path], zz.reshape(-1, nstage), b, G=RB if nstage > 1 else None,
+                                      a=a if nstage > 1 else None, W=W, P=p, want_x=False)
+    if np.any(info != 0):
+        s = int(np.argmax(info.max(axis=0)))
+        raise ArithmeticError("response_chain: z on an eigenvalue of channel %d (%d pivots replaced)" % (path[s][0], int(info.max())))
+    return R[:, nstage - 1, 0, 0].reshape(zz.shape[:-1])
+
+
+def two_photon(prob, n_ini, l_mid, final, omega, absorber=None):
+    """The radial two-photon amplitude <f| r G_{l_mid}(E_i + omega) r |i> of the s state n_ini (1-based) to final = (l_f, n_f), for
+    every omega of an array (or one): the sum over every state of l_mid (angular factors are the caller's: 1/3 for s - p - s).
+    Channels 0, l_mid and l_f in the last solve, made by prob.solve.  Returns complex128 of omega's shape."""
+    import numpy as np
+    om = np.asarray(omega, dtype=np.float64)
+    Ei = float(prob.last_E[0 - prob.last_l0, n_ini - 1])
+    r1 = (1.0, 0.0, 0.0)
+    return response_chain(prob, 0, n_ini, [(l_mid, r1)], (Ei + om)[..., None], absorber=absorber, left=(final[0], final[1], r1))
+
+
+def two_photon_ati(prob, n_ini, path2, omega, absorber, left=None):
+    """Two photons above threshold: p^T G_{l2}(E_i + 2 omega) r G_{l1}(E_i + omega) r c_i of the s state n_ini with path2 = (l1, l2),
+    both resolvents in the continuum -- hence the absorber is not optional -- for every omega of an array.  p = r c_i (left None:
+    the diagonal fourth-order response) or r c_f of left = (l_f, n_f).  Returns complex128 of omega's shape."""
+    import numpy as np
+    om = np.asarray(omega, dtype=np.float64)
+    Ei = float(prob.last_E[0 - prob.last_l0, n_ini - 1])
+    r1 = (1.0, 0.0, 0.0)
+    l1, l2 = path2
+    z = np.stack([Ei + om, Ei + 2.0 * om], axis=-1)
+    return response_chain(prob, 0, n_ini, [(l1, r1), (l2, r1)], z, absorber=absorber,
+                          left=None if left is None else (left[0], left[1], r1))
+
+
+def cauchy_moments(prob, n_ini, order):
+    """The moments (2/3) b^T (G S)^(m-1) G b, m = 1 .. order, of the s state n_ini: b = r c_i, G = (H_1 - E_i S)^-1 -- the oscillator
+    strength sums S(-(m+1)) -- from ONE chain of `order` stages with the overlap as the operator in between (R of every stage).
+    G(E_i +- omega) = G +- omega G S G + omega^2 G S G S G ..., so alpha(omega) = sum over odd m of moment_m omega^(m-1): m = 1 is
+    alpha(0), m = 3 the coefficient of omega^2, and so on.  Hydrogen 1s: 9/2, 43/4, 319/12.  Channels 0 and 1 in the last solve, made
+    by prob.solve.  Returns float64 (order,)."""
+    import numpy as np
+    Ei = float(prob.last_E[0 - prob.last_l0, n_ini - 1])
+    b = band_apply(prob.dipole_bands()[0], prob.eigvecs(0, n_ini, 1))
+    SBf = prob.operator_bands(np.ones(prob.quadrature()[0].size), [0])
+    _, R, info = prob.resolvent_chain(np.ones(order, dtype=np.int32), np.full(order, Ei), b, G=SBf, P=b, want_x=False)
+    if np.any(info != 0):
+        raise ArithmeticError("cauchy_moments: E_i on an eigenvalue of channel 1 (%d pivots replaced)" % int(info.max()))
+    return (2.0 / 3.0) * R[0, :, 0, 0].real
+
+
 # ---- KIND_PI = 0 on several GPUs: one process per GPU, channels sharded, spectra gathered (SURVEY 8e) ---------------
 def write_structure_outputs(nfun, lmax, E, l_ini, wf, outdir):
     """Enl.dat, wf_n0.dat and the stdout text of a KIND_PI = 0 run from the spectra E[l][i] and the tabulated initial

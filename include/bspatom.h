@@ -218,6 +218,47 @@ int bspatom_resolvent_dev(bspatom_problem *p, int nmat, const int32_t *l, const 
                           const int32_t *w, int nrhs, const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev,
                           int32_t *info);
 
+/* Chains of resolvents with an operator in between (csrc/resolvent.hip: resolvent_chain_kernel) -- what lies beyond second order:
+ * two-photon amplitudes above threshold, three-photon amplitudes, hyperpolarizabilities, the Cauchy moments of alpha(omega) are
+ *   p^T G_{l2}(z2) A2 G_{l1}(z1) A1 c_i,      G_l(z) = (H_l - i W - z S)^-1,
+ * where the right-hand side of a solve is the solution of the one before and differs for every energy.  For chain c < nchain, stage
+ * s < nstage, right-hand side r < nrhs, with m = c*nstage + s:
+ *   M_{c,s}   = H_{l[m]} - i W_{w[m]} - z_{c,s} S,   z_{c,s} = z[2m] + i z[2m+1]   (w == NULL, w[m] = -1 as in bspatom_resolvent)
+ *   x_{c,0,r} = M_{c,0}^-1 B_r
+ *   x_{c,s,r} = M_{c,s}^-1 (A_{c,s} x_{c,s-1,r}),   s >= 1,   A_{c,s} = sum_o a[(c*(nstage-1) + (s-1))*nop + o] G_o
+ *   R[(((size_t)c*nstage + s)*nrhs + r)*nproj + q] = sum_i P_q(i) x_{c,s,r}(i)      (bilinear, EVERY stage)
+ *   X[((size_t)c*nrhs + r)*nfun + i] = x_{c,nstage-1,r}(i)                          (the LAST stage only)
+ *   info[m] = pivots replaced in M_{c,s}
+ * GB: nop FULL bands in bspatom_operator_bands' layout, both triangles used as given (bspatom_dipole_bands, any
+ * bspatom_operator_bands result, S itself from g = 1).  a is REAL, as in bspatom_operator_matrix: the bands are real and a real
+ * combination keeps A x two independent real products (G3 below survives a chain); a phase factor on an operator is a factor on the
+ * whole amplitude and the caller's business.  nstage = 1 needs neither GB nor a: nop = 0 is then allowed and both may be NULL.
+ * The arithmetic of y = A x is fixed: an entry is formed as t = a_0*G_0(i,i+d), then t = t + a_o*G_o(i,i+d) for o ascending; y_re(i)
+ * starts at +0.0 and adds t * x_re(i+d) for d = -(k-1) .. k-1 ascending, terms with i+d outside 0..nfun-1 skipped; y_im likewise from
+ * x_im; IEEE multiplies and adds, no FMA (bspatom_operator_matrix's rule for A x, applied to the two components).  One wavefront
+ * keeps a chain from its first factorisation to its last projection; a stage's factorisation serves all nrhs right-hand sides.
+ * Guarantees:
+ *   (C1) results are bit-identical from run to run;
+ *   (C2) a chain's results depend on its own (l, z, W, a), on GB, B_r and P_q alone -- not on the other chains, on nchain, nrhs or
+ *        nproj, on the work slots or the grouping, or on the host versus _dev variant;
+ *   (C3) prefix: R and info of stages 0..s equal those of the same chain cut to s+1 stages, and the cut chain's X is x_{c,s}: an
+ *        intermediate vector is obtained this way;
+ *   (C4) nstage = 1 is bspatom_resolvent bit for bit, in X, R and info;
+ *   (C5) composition: stage s equals bspatom_resolvent with nmat = 1 given A x_{s-1}, formed by the arithmetic above, as its
+ *        right-hand side, bit for bit;
+ *   (C6) with every Im z = 0, no absorber and real B every imaginary part of X is +-0.0 exactly.
+ * The host variant processes the chains in groups under the bound of bspatom_resolvent ("resolvent_stage_mb"; the X of one group, one
+ * chain at least); the kernel's scratch per resident wave is bspatom_resolvent's plus nrhs complex vectors, nfun*(6k-1 + 2 nrhs)
+ * doubles, within the same bound; "resolvent_slots" applies as there.  BSPATOM_ERR_ARG: what bspatom_resolvent names, for every
+ * stage; nchain < 1, nstage < 1; nop < 0; nstage > 1 with nop < 1 or GB or a NULL.  The _dev variant: WB, GB, B, P, X, R in device
+ * memory of the problem's device, written in place; l, z, w, a, info stay host pointers. */
+int bspatom_resolvent_chain(bspatom_problem *p, int nchain, int nstage, const int32_t *l, const double *z, int nabs, const double *WB,
+                            const int32_t *w, int nop, const double *GB, const double *a, int nrhs, const double *B, int nproj,
+                            const double *P, double *X, double *R, int32_t *info);
+int bspatom_resolvent_chain_dev(bspatom_problem *p, int nchain, int nstage, const int32_t *l, const double *z, int nabs,
+                                const double *WB_dev, const int32_t *w, int nop, const double *GB_dev, const double *a, int nrhs,
+                                const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev, int32_t *info);
+
 /* WRITE_WF (Bsp_Atom.f90:118-146): u(r_i) = sum_j c_j B_j(r_i), r_i = ra + i*(rb-ra)/npts,
  * i = 0..npts.  Returns BSPATOM_ERR_BSPLVB where the reference STOPs. r[npts+1], u[npts+1]. */
 int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u);
