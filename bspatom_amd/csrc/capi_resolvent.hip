@@ -2,6 +2,7 @@
 // energies, (H_l - i W - z S) x = b, by resolvent.hip's one-wave LU.  The bands are those the problem holds on the device (the
 // last bspatom_solve or bspatom_assemble); all work goes on the problem's stream and the scratch of a call is freed when it returns.
 // bspatom_resolvent_chain / _dev: chains of such solves with an operator in between, one launch for the whole batch.
+// bspatom_resolvent_coupled / _dev: several channels coupled to all orders in one banded LU (resolvent_coupled.hip).
 #include <algorithm>
 #include "capi_internal.h"
 
@@ -138,6 +139,105 @@ static int resolvent_chain_impl(bspatom_problem *p, int nchain, int nstage, cons
     if (!rc && !dev && R) rc = HIP_RC(hipMemcpyAsync(R, dR.p, r_all * sizeof(double), hipMemcpyDeviceToHost, p->st));
     if (!rc) rc = HIP_RC(hipMemcpyAsync(info, dinfo.p, (size_t)nmat * sizeof(int), hipMemcpyDeviceToHost, p->st));
     return drain(p, rc);
+}
+
+// bspatom_resolvent_coupled / _dev: nmat matrices of nch coupled channels each, one workgroup per matrix (resolvent_coupled.hip); the
+// plumbing of resolvent_impl with nmat * nch channel records, the coupling topology and its complex coefficients beside them.
+static int resolvent_coupled_impl(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs, const double *WB,
+                                  const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop,
+                                  const double *GB, const double *ac, int nrhs, const double *B, int nproj, const double *P, double *X,
+                                  double *R, int32_t *info, bool dev)
+{
+    if (!p || !l || !z || !B || !info || (!X && !R)) return BSP_ERR_ARG;
+    if (nmat < 1 || nch < 1 || nrhs < 1 || nabs < 0 || nproj < 0 || ncoup < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
+    if (R && (!P || nproj < 1)) return BSP_ERR_ARG;
+    if (ncoup > 0 && (nop < 1 || !cr || !cc || !ctr || !GB || !ac)) return BSP_ERR_ARG;
+    if ((long long)nmat * nch > 0x3fffffffLL) return BSP_ERR_ARG;
+    if (!WB) nabs = 0;
+    const int nrec = nmat * nch;
+    for (int m = 0; m < nrec; ++m) {
+        if (p->band_nl < 1 || l[m] < p->band_l0 || l[m] >= p->band_l0 + p->band_nl) return BSP_ERR_ARG;
+        if (w && (w[m] < -1 || w[m] >= nabs)) return BSP_ERR_ARG;
+    }
+    for (int q = 0; q < ncoup; ++q)
+        if (cr[q] < 0 || cr[q] >= nch || cc[q] < 0 || cc[q] >= nch || ctr[q] < 0 || ctr[q] > 1) return BSP_ERR_ARG;
+    const HostSetup &h = p->hs;
+    const int n = h.nfun, k = h.k;
+    if ((long long)nch * k - 1 > resolvent_coupled_max_band()) {
+        fprintf(stderr, "bspatom_resolvent_coupled: half-width nch*k - 1 = %lld exceeds BSPATOM_COUPLED_MAX_BAND = %d\n",
+                (long long)nch * k - 1, resolvent_coupled_max_band());
+        return BSP_ERR_UNSUPPORTED;
+    }
+    if ((long long)nch * n > 0x3fffffffLL) return BSP_ERR_ARG;
+    const size_t N = (size_t)nch * n;
+    const size_t wband = (size_t)(2 * k - 1) * n, stage = opts().resolvent_stage_mb > 0 ? (size_t)opts().resolvent_stage_mb << 20 : RESOLVENT_STAGE_BYTES;
+    BSP_HIP(hipSetDevice(p->device));
+    int rc;
+    int slots = 0;
+    if ((rc = resolvent_coupled_slots(k, nch, nmat, &slots))) return rc;
+    if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, nmat);
+    const size_t slot_doubles = resolvent_coupled_slot_doubles(n, k, nch);
+    slots = (int)std::max<size_t>(1, std::min<size_t>(slots, stage / (slot_doubles * sizeof(double))));
+    // the host variant's groups: the X of one group within the bound, one matrix at least
+    const size_t x_mat = (size_t)2 * nrhs * N;                       // doubles of one matrix's X
+    int group = nmat;
+    if (!dev && X) group = (int)std::max<size_t>(1, std::min<size_t>(nmat, stage / (x_mat * sizeof(double))));
+    std::vector<int> chan(nrec), wsel(nrec, nabs > 0 && !w ? 0 : -1);
+    for (int m = 0; m < nrec; ++m) { chan[m] = l[m] - p->band_l0; if (w) wsel[m] = w[m]; }
+    const bool ops = ncoup > 0;
+    DevArray<double> work, dz, dac, dWB, dGB, dB, dP, dX, dR;
+    DevArray<int> dchan, dw, dinfo, dcr, dcc, dctr;
+    if ((rc = work.alloc((size_t)slots * slot_doubles)) || (rc = dz.put(z, (size_t)2 * nrec)) ||
+        (ops && ((rc = dac.put(ac, (size_t)2 * nmat * ncoup * nop)) || (rc = dcr.put(cr, ncoup)) || (rc = dcc.put(cc, ncoup)) ||
+                 (rc = dctr.put(ctr, ncoup)))) ||
+        (rc = dchan.put(chan.data(), nrec)) || (rc = dw.put(wsel.data(), nrec)) || (rc = dinfo.alloc(nmat))) return rc;
+    const size_t r_all = (size_t)2 * nmat * nrhs * nproj;
+    if (!dev) {
+        if ((nabs > 0 && (rc = dWB.put(WB, (size_t)nabs * wband))) || (ops && (rc = dGB.put(GB, (size_t)nop * wband))) ||
+            (rc = dB.put(B, (size_t)2 * nrhs * N)) || (R && (rc = dP.put(P, (size_t)2 * nproj * N))) ||
+            (X && (rc = dX.alloc((size_t)group * x_mat))) || (R && (rc = dR.alloc(r_all))))
+            return rc;
+    }
+    ResolventCoupledArgs a;
+    a.n = n; a.k = k; a.nch = nch; a.nrhs = nrhs; a.nproj = R ? nproj : 0; a.ncoup = ncoup; a.nop = ops ? nop : 0;
+    a.SB = p->d_SB; a.HB = p->d_HB;
+    a.WB = nabs > 0 ? (dev ? WB : dWB.p) : nullptr;
+    a.cr = ops ? dcr.p : nullptr; a.cc = ops ? dcc.p : nullptr; a.ctr = ops ? dctr.p : nullptr;
+    a.GB = ops ? (dev ? GB : dGB.p) : nullptr;
+    a.B = dev ? B : dB.p;
+    a.P = R ? (dev ? P : dP.p) : nullptr;
+    a.work = work.p;
+    rc = BSP_OK;
+    for (int m0 = 0; !rc && m0 < nmat; m0 += group) {
+        const int g = std::min(group, nmat - m0);
+        a.nmat = g;
+        a.chan = dchan.p + (size_t)m0 * nch; a.z = dz.p + (size_t)2 * m0 * nch; a.w = dw.p + (size_t)m0 * nch; a.info = dinfo.p + m0;
+        a.acoef = ops ? dac.p + (size_t)2 * m0 * ncoup * nop : nullptr;
+        a.X = X ? (dev ? X + (size_t)m0 * x_mat : dX.p) : nullptr;
+        a.R = R ? (dev ? R : dR.p) + (size_t)2 * m0 * nrhs * nproj : nullptr;
+        rc = launch_resolvent_coupled(a, std::min(slots, g), p->st);
+        if (!rc && !dev && X) rc = HIP_RC(hipMemcpyAsync(X + (size_t)m0 * x_mat, dX.p, (size_t)g * x_mat * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc && !dev && R) rc = HIP_RC(hipMemcpyAsync(R, dR.p, r_all * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    if (!rc) rc = HIP_RC(hipMemcpyAsync(info, dinfo.p, (size_t)nmat * sizeof(int), hipMemcpyDeviceToHost, p->st));
+    return drain(p, rc);
+}
+
+extern "C" int bspatom_resolvent_coupled(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,
+                                         const double *WB, const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc,
+                                         const int32_t *ctr, int nop, const double *GB, const double *a, int nrhs, const double *B,
+                                         int nproj, const double *P, double *X, double *R, int32_t *info)
+{
+    return resolvent_coupled_impl(p, nmat, nch, l, z, nabs, WB, w, ncoup, cr, cc, ctr, nop, GB, a, nrhs, B, nproj, P, X, R, info, false);
+}
+extern "C" int bspatom_resolvent_coupled_dev(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,
+                                             const double *WB_dev, const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc,
+                                             const int32_t *ctr, int nop, const double *GB_dev, const double *a, int nrhs,
+                                             const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev,
+                                             int32_t *info)
+{
+    return resolvent_coupled_impl(p, nmat, nch, l, z, nabs, WB_dev, w, ncoup, cr, cc, ctr, nop, GB_dev, a, nrhs, B_dev, nproj, P_dev,
+                                  X_dev, R_dev, info, true);
 }
 
 extern "C" int bspatom_resolvent_chain(bspatom_problem *p, int nchain, int nstage, const int32_t *l, const double *z, int nabs,

@@ -366,6 +366,28 @@ struct ResolventChainArgs {
 size_t resolvent_chain_slot_doubles(int n, int k, int nrhs);
 int resolvent_chain_slots(int k, int nchain, int *slots);
 int launch_resolvent_chain(const ResolventChainArgs &a, int slots, hipStream_t st);
+// resolvent_coupled.hip: nch channels coupled in one banded LU (bspatom_resolvent_coupled).  Matrix m: channel c is entry m*nch + c
+// of chan, z (complex) and w (-1: no absorber; never null here); coupling entry p adds sum_o acoef[(m*ncoup + p)*nop + o] (complex)
+// G_o, or its transpose where ctr[p], to block (cr[p], cc[p]).  B: nrhs, P: nproj vectors of nch*n complex, channel-major;
+// X[m][r][nch][n], R[m][r][nproj] complex (either may be null).  Every pointer is device memory.
+// work: slots * resolvent_coupled_slot_doubles (16-byte aligned), slots at most resolvent_coupled_slots.
+struct ResolventCoupledArgs {
+    int n, k, nch, nmat, nrhs, nproj, ncoup, nop;
+    const double *SB, *HB;
+    const int *chan;
+    const double *z, *WB;
+    const int *w;
+    const int *cr, *cc, *ctr;
+    const double *GB, *acoef;
+    const double *B, *P;
+    double *X, *R;
+    int *info;
+    double *work;
+};
+int resolvent_coupled_max_band();              // half-width limit of the coupled matrix, nch*k - 1 (BSPATOM_COUPLED_MAX_BAND)
+size_t resolvent_coupled_slot_doubles(int n, int k, int nch);
+int resolvent_coupled_slots(int k, int nch, int nmat, int *slots);
+int launch_resolvent_coupled(const ResolventCoupledArgs &a, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

@@ -1,0 +1,431 @@
+// resolvent_coupled.hip -- the coupled-channel resolvent: (sum_c (H_{l_c} - i W_c - z_c S) + V) x = b across nch channels in ONE
+// banded LU (include/bspatom.h: bspatom_resolvent_coupled).
+//
+// resolvent.hip answers for one channel at a time and its chains multiply such answers: perturbation theory.  A coupling to all
+// orders -- a static field, a Floquet block matrix, any potential that mixes l -- is one linear system whose matrix, with the
+// unknowns ordered basis index first and channel second (unknown (i, c) at position i nch + c), is banded again: half-width
+// bw = nch k - 1.  That is too wide for the one-wave register window of resolvent.hip (bw <= 15), so here a WORKGROUP factors a
+// matrix, the row window in LDS:
+//
+//   rows j .. j + bw of the columns j .. j + 2 bw, (bw + 1) x (2 bw + 1) complex, as a ring in both directions (row r in slot
+//   r mod (bw + 1), column c in slot c mod (2 bw + 1)): nothing is ever shifted, the slot of the row that leaves takes the row that
+//   enters, the slot of the column that was eliminated is the column that comes into reach, zero but in the entering row.
+//
+// A step (one column; RC_PANEL below): wave 0 finds the pivot among the at most bw + 1 <= 64 candidates -- one per lane --, forms the
+// reciprocal and the multipliers, copies the pivot row out (U, and a broadcast copy in LDS) and puts row j where the pivot row
+// was; after a barrier all waves update the window, a wave per row, a lane per column, while the last two waves store the entering
+// row, which they requested two steps ahead; a second barrier ends the step.  U rows, L multipliers and pivot indices stream
+// to the slot's scratch; the solves run from there on wave 0 (forward: resolvent.hip's register window, bw + 1 lanes; backward: the
+// last 2 bw unknowns in an LDS ring, two per lane), one right-hand side after the other.
+//
+// The matrix is first ASSEMBLED, by all threads, into the rows of U itself -- row r of the band, columns r - bw .. r + bw, lies where
+// U's row r will be written at step r, bw + 1 steps after the window has taken it -- so the entering row is one coalesced load and
+// the generalisation of rs_entry (rc_entry: the diagonal-block formula or the sum over the block's coupling entries) runs once per
+// entry, outside the dependent steps.
+//
+// Arithmetic, fixed (K1 - K4 of include/bspatom.h): pivot by |Re| + |Im|, ties to the smallest row; complex products in the plain
+// four-product form; one reciprocal per pivot, resolvent.hip's; every sum in an order that depends on the matrix alone (no atomics;
+// the workgroup's shape is a constant).  With Im z = 0, no absorber, real coefficients and real B every imaginary part is a sum of
+// products with a zero factor.
+#include "common.h"
+#include "wave_ops.h"
+#include "../../include/bspatom.h"
+
+namespace bsp {
+namespace {
+constexpr int RC_BMAX = 63;                // BSPATOM_COUPLED_MAX_BAND: the pivot candidates of a column fit one wavefront
+constexpr int RC_NT = 512;                 // threads of the workgroup
+constexpr int RC_NW = RC_NT / 64;
+constexpr int RC_PANEL = 1;                // columns per panel
+constexpr int RC_PF = 8;                   // steps per prefetch block of the solves' forward pass
+constexpr int RC_PFB = 4;                  // the same of the backward pass (two U entries per lane and step)
+static_assert(RC_PANEL == 1, "the step below is one column");
+static_assert(RC_BMAX == BSPATOM_COUPLED_MAX_BAND, "the limit the header states");
+
+__host__ __device__ inline size_t rc_slot_doubles(int N, int bw)
+{
+    const size_t piv = ((size_t)N + 1) / 2;
+    return 2 * ((size_t)N * (2 * bw + 1) + (size_t)N * bw + (size_t)N) + piv + (piv & 1);
+}
+// LDS of a workgroup: the window, the pivot row's copy (128), the multipliers (64), the reductions' words (16), complex each
+__host__ __device__ inline size_t rc_lds_bytes(int bw) { return ((size_t)(bw + 1) * (2 * bw + 1) + 128 + 64 + 16) * sizeof(double2); }
+
+// The maximum over the 64 lanes of values that are >= 0 in lane 0 (wave_sum's scan with fmax: zeros shift in and change nothing)
+__device__ __forceinline__ double rc_wave_max(double x)
+{
+    x = fmax(x, dpp_mov<0x111>(x)); x = fmax(x, dpp_mov<0x112>(x)); x = fmax(x, dpp_mov<0x114>(x)); x = fmax(x, dpp_mov<0x118>(x));
+    return fmax(fmax(read_lane(x, 15), read_lane(x, 31)), fmax(read_lane(x, 47), read_lane(x, 63)));
+}
+// *p where ok, else zero: a guarded load, never a load through a selected address (that one is a FLAT load, whose wait drains the
+// global loads and stores in flight as well)
+__device__ __forceinline__ double2 rc_load(const double2 *p, bool ok)
+{
+    double2 v = make_double2(0.0, 0.0);
+    if (ok) v = *p;
+    return v;
+}
+__device__ __forceinline__ void rc_sync() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// M(R, C) of item `it`, R = i nch + c, C = j nch + c2.  fl: the sum of the magnitudes of the terms (the pivot threshold's floor).
+__device__ __forceinline__ void rc_entry(const ResolventCoupledArgs &a, int it, int R, int C, double &re, double &im, double &fl)
+{
+    re = 0.0; im = 0.0; fl = 0.0;
+    const int n = a.n, b = a.k - 1, nch = a.nch;
+    if (C < 0 || C >= n * nch) return;
+    const int i = R / nch, c = R - i * nch, j = C / nch, c2 = C - j * nch;
+    const int d = (i > j) ? (i - j) : (j - i);
+    if (d > b) return;
+    if (c == c2) {
+        const int lo = (i > j) ? j : i, mc = it * nch + c;
+        const double zr = a.z[2 * mc], zi = a.z[2 * mc + 1];
+        const double s = a.SB[(size_t)d * n + lo], h = a.HB[((size_t)a.chan[mc] * a.k + d) * n + lo];
+        re = h - zr * s;
+        im = -(zi * s);
+        fl = (fabs(h) + fabs(zr * s)) + fabs(zi * s);
+        const int ws = a.w[mc];
+        if (a.WB && ws >= 0) {
+            const double wv = a.WB[((size_t)ws * (2 * b + 1) + (j - i + b)) * n + i];
+            im -= wv;
+            fl += fabs(wv);
+        }
+    }
+    const size_t cs = (size_t)(2 * b + 1) * n;
+    for (int p = 0; p < a.ncoup; ++p) {
+        if (a.cr[p] != c || a.cc[p] != c2) continue;
+        const size_t at = a.ctr[p] ? (size_t)(i - j + b) * n + j : (size_t)(j - i + b) * n + i;   // G(i, j), or G(j, i) for the transpose
+        const double *co = a.acoef + ((size_t)it * a.ncoup + p) * a.nop * 2;
+        for (int o = 0; o < a.nop; ++o) {
+            const double g = a.GB[(size_t)o * cs + at];
+            re += co[2 * o] * g;
+            im += co[2 * o + 1] * g;
+            fl += (fabs(co[2 * o]) + fabs(co[2 * o + 1])) * fabs(g);
+        }
+    }
+}
+
+// The factorisation P M = L U of the assembled band in U.  U: [N][2bw+1] complex, on entry row r = M(r, r-bw .. r+bw), on return
+// row j = (1 / pivot, U(j, j+1 .. j+2bw)); Lm: [N][bw] multipliers; piv: [N] pivot rows.  Returns (in wave 0) the replaced pivots.
+__device__ __forceinline__ int rc_factor(const int N, const int bw, const double pertol, double2 *U, double2 *Lm, int *piv, double2 *win,
+                                         double2 *prow, double2 *mult, const int tid)
+{
+    const int W = 2 * bw + 1, RS = bw + 1, lane = tid & 63, wv = tid >> 6;
+    // the window at step 0: rows 0 .. bw, columns 0 .. 2 bw
+    for (int e = tid; e < RS * W; e += RC_NT) {
+        const int r = e / W, C = e - r * W;
+        win[e] = rc_load(U + (size_t)r * W + (C - r + bw), r < N && C <= r + bw);
+    }
+    // the loaders: thread lc of the last two waves holds entry lc of the rows that enter at an even step (ent0) and at an odd one
+    // (ent1); a register is loaded again right after the window has taken it, two steps ahead of its next use, and never copied
+    // (a copy would wait for the load)
+    const int lc = tid - (RC_NT - 128);
+    const bool loader = lc >= 0 && lc < W;
+    double2 ent0 = rc_load(U + (size_t)(bw + 1) * W + lc, loader && bw + 1 < N);
+    double2 ent1 = rc_load(U + (size_t)(bw + 2) * W + lc, loader && bw + 2 < N);
+    lds_barrier();
+    int nper = 0, rbase = 0, cb = 0;                               // j mod RS, j mod W
+    auto step = [&](const int j, double2 &ent) {
+        const int nrow = (N - 1 - j < bw) ? (N - 1 - j) : bw;
+        if (wv == 0) {
+            // pivot search: lane t holds M(j + t, j); ties go to the smallest row
+            int s = rbase + (lane <= bw ? lane : 0);
+            s = (s >= RS) ? s - RS : s;
+            const double2 v = rc_load(win + s * W + cb, lane <= nrow);
+            const double mag = (lane <= nrow) ? fabs(v.x) + fabs(v.y) : -1.0;
+            const double mx = rc_wave_max(mag);
+            const unsigned long long hit = __ballot(mag == mx);
+            const int dp = __builtin_amdgcn_readfirstlane(hit ? __ffsll((long long)hit) - 1 : 0);
+            double pr = read_lane(v.x, dp), pi = read_lane(v.y, dp);
+            const double v0r = read_lane(v.x, 0), v0i = read_lane(v.y, 0);
+            if (fabs(pr) + fabs(pi) < pertol) { pr = (pr < 0.0) ? -pertol : pertol; pi = 0.0; ++nper; }
+            // 1 / pivot, once per column (resolvent.hip's form)
+            const double sc = 1.0 / (fabs(pr) + fabs(pi));
+            const double qr = pr * sc, qi = pi * sc;
+            const double rd = 1.0 / (qr * qr + qi * qi);
+            const double rr = (qr * rd) * sc, ri = -((qi * rd) * sc);
+            // rows j and j + dp change places: the row now at j + t, t >= 1, is the old row j where t == dp
+            const double xr = (lane == dp) ? v0r : v.x, xi = (lane == dp) ? v0i : v.y;
+            const bool below = lane >= 1 && lane <= nrow;
+            const double2 lm = make_double2(below ? xr * rr - xi * ri : 0.0, below ? xr * ri + xi * rr : 0.0);
+            mult[lane] = lm;
+            if (lane >= 1 && lane <= bw) Lm[(size_t)j * bw + lane - 1] = lm;
+            if (lane == 0) piv[j] = j + dp;
+            int sp = rbase + dp;
+            sp = (sp >= RS) ? sp - RS : sp;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int c = lane + 64 * h;
+                if (c < W) {
+                    int ci = cb + c;
+                    ci = (ci >= W) ? ci - W : ci;
+                    const double2 pv = win[sp * W + ci];
+                    if (dp != 0) win[sp * W + ci] = win[rbase * W + ci];
+                    prow[c] = pv;
+                    U[(size_t)j * W + c] = make_double2((c == 0) ? rr : pv.x, (c == 0) ? ri : pv.y);
+                }
+            }
+        }
+        lds_barrier();
+        // the trailing update: a wave per row, a lane per column; column j is eliminated and becomes column j + 2 bw + 1
+        for (int t = 1 + wv; t <= nrow; t += RC_NW) {
+            int s = rbase + t;
+            s = (s >= RS) ? s - RS : s;
+            const double2 lm = mult[t];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int c = lane + 64 * h;
+                if (c < W) {
+                    int ci = cb + c;
+                    ci = (ci >= W) ? ci - W : ci;
+                    const double2 av = win[s * W + ci];
+                    const double2 pv = prow[c];
+                    const double ur = lm.x * pv.x - lm.y * pv.y, ui = lm.x * pv.y + lm.y * pv.x;
+                    win[s * W + ci] = make_double2((c == 0) ? 0.0 : av.x - ur, (c == 0) ? 0.0 : av.y - ui);
+                }
+            }
+        }
+        // row j + bw + 1 enters the slot row j has left: its columns j + 1 .. j + 2 bw + 1
+        if (loader && j + bw + 1 < N) {
+            int ci = cb + lc + 1;
+            ci = (ci >= W) ? ci - W : ci;
+            win[rbase * W + ci] = ent;
+        }
+        ent = rc_load(U + (size_t)(j + bw + 3) * W + lc, loader && j + bw + 3 < N);
+        lds_barrier();
+        rbase = (rbase + 1 == RS) ? 0 : rbase + 1;
+        cb = (cb + 1 == W) ? 0 : cb + 1;
+    };
+    for (int j = 0; j < N; j += 2) {
+        step(j, ent0);
+        if (j + 1 < N) step(j + 1, ent1);                          // uniform
+    }
+    return nper;
+}
+
+// y <- U^-1 L^-1 P y in place on ONE wave (y: N complex in global memory, visible to the wave; xs: an LDS ring of 128 complex).
+// Forward: resolvent.hip::rs_solve's pass, lane i holds y[j + i], i <= bw <= 63.  Backward: x_j = (y_j - sum_{c=1..2bw} U[j][c]
+// x_{j+c}) / pivot_j, the 2 bw unknowns behind j in the ring, lane l takes c = l and c = 64 + l, then the wave's fixed tree.
+__device__ __forceinline__ void rc_solve(const int N, const int bw, const double2 *U, const double2 *Lm, const int *piv, double2 *y,
+                                         double2 *xs, const int lane)
+{
+    {
+        constexpr int PF = RC_PF;
+        double wr = 0.0, wi = 0.0;
+        if (lane <= bw && lane < N) { const double2 v = y[lane]; wr = v.x; wi = v.y; }
+        double2 lvn[PF]; int pvn[PF];
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            lvn[u] = (u < N && lane >= 1 && lane <= bw) ? Lm[(size_t)u * bw + lane - 1] : make_double2(0.0, 0.0);
+            pvn[u] = (u < N) ? piv[u] : 0;
+        }
+        double2 yln = (lane < PF && lane + bw + 1 < N) ? y[lane + bw + 1] : make_double2(0.0, 0.0);
+        for (int j0 = 0; j0 < N; j0 += PF) {
+            double2 lv[PF]; int pvv[PF];
+            const double2 yl = yln;
+            yln = (lane < PF && j0 + PF + lane + bw + 1 < N) ? y[j0 + PF + lane + bw + 1] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int jn = j0 + u + PF;
+                lv[u] = lvn[u]; pvv[u] = pvn[u];
+                lvn[u] = (jn < N && lane >= 1 && lane <= bw) ? Lm[(size_t)jn * bw + lane - 1] : make_double2(0.0, 0.0);
+                pvn[u] = (jn < N) ? piv[jn] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int j = j0 + u;
+                if (j < N) {
+                    const int p = __builtin_amdgcn_readfirstlane(pvv[u]);
+                    if (p != j) {                                    // uniform: rows j and p change places (p - j <= bw: inside the window)
+                        const double t0r = read_lane(wr, 0), t0i = read_lane(wi, 0);
+                        const double tqr = read_lane(wr, p - j), tqi = read_lane(wi, p - j);
+                        wr = lane == 0 ? tqr : (lane == p - j ? t0r : wr);
+                        wi = lane == 0 ? tqi : (lane == p - j ? t0i : wi);
+                    }
+                    const double yr = read_lane(wr, 0), yi = read_lane(wi, 0);
+                    const int nrow = (N - 1 - j < bw) ? (N - 1 - j) : bw;
+                    if (lane >= 1 && lane <= nrow) {
+                        wr -= lv[u].x * yr - lv[u].y * yi;
+                        wi -= lv[u].x * yi + lv[u].y * yr;
+                    }
+                    if (lane == 0) y[j] = make_double2(yr, yi);
+                    wr = dpp_mov<0x130>(wr); wi = dpp_mov<0x130>(wi);  // wave_shl:1 -- lane i takes lane i + 1
+                    const double er = read_lane(yl.x, u), ei = read_lane(yl.y, u);
+                    if (lane == bw) { wr = er; wi = ei; }
+                }
+            }
+        }
+        rc_sync();
+    }
+    {
+        constexpr int PF = RC_PFB;
+        const int W = 2 * bw + 1;
+        xs[lane] = make_double2(0.0, 0.0); xs[lane + 64] = make_double2(0.0, 0.0);
+        const bool in1 = lane >= 1 && lane <= 2 * bw, in2 = lane + 64 <= 2 * bw;
+        double2 u1n[PF], u2n[PF], udn[PF];
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int j = N - 1 - u;
+            u1n[u] = (j >= 0 && in1) ? U[(size_t)j * W + lane] : make_double2(0.0, 0.0);
+            u2n[u] = (j >= 0 && in2) ? U[(size_t)j * W + lane + 64] : make_double2(0.0, 0.0);
+            udn[u] = (j >= 0) ? U[(size_t)j * W] : make_double2(0.0, 0.0);
+        }
+        double2 ybn = (lane < PF && N - 1 - lane >= 0) ? y[N - 1 - lane] : make_double2(0.0, 0.0);
+        for (int j0 = N - 1; j0 >= 0; j0 -= PF) {
+            double2 u1[PF], u2[PF], ru[PF];
+            const double2 yb = ybn;
+            ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int jn = j0 - u - PF;
+                u1[u] = u1n[u]; u2[u] = u2n[u]; ru[u] = udn[u];
+                u1n[u] = (jn >= 0 && in1) ? U[(size_t)jn * W + lane] : make_double2(0.0, 0.0);
+                u2n[u] = (jn >= 0 && in2) ? U[(size_t)jn * W + lane + 64] : make_double2(0.0, 0.0);
+                udn[u] = (jn >= 0) ? U[(size_t)jn * W] : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                const int j = j0 - u;
+                if (j >= 0) {
+                    double sr = 0.0, si = 0.0;
+                    if (in1 && j + lane < N) {
+                        const double2 x = xs[(j + lane) & 127];
+                        sr = u1[u].x * x.x - u1[u].y * x.y;
+                        si = u1[u].x * x.y + u1[u].y * x.x;
+                    }
+                    if (in2 && j + lane + 64 < N) {
+                        const double2 x = xs[(j + lane + 64) & 127];
+                        sr += u2[u].x * x.x - u2[u].y * x.y;
+                        si += u2[u].x * x.y + u2[u].y * x.x;
+                    }
+                    sr = wave_sum(sr); si = wave_sum(si);
+                    const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
+                    const double2 x = make_double2(dr * ru[u].x - di * ru[u].y, dr * ru[u].y + di * ru[u].x);
+                    if (lane == 0) { xs[j & 127] = x; y[j] = x; }
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+        rc_sync();
+    }
+}
+}  // namespace
+
+// A PERSISTENT grid of workgroups, one per work slot, takes the matrices by resolvent_kernel's static stride.
+// Slot scratch: U [N][2bw+1], L [N][bw], y [N] complex, then piv [N] ints (rc_slot_doubles); N = nch n, bw = nch k - 1.
+__global__ __launch_bounds__(RC_NT) void resolvent_coupled_kernel(const ResolventCoupledArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double2 rc_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = a.n, nch = a.nch, N = n * nch, bw = nch * a.k - 1, W = 2 * bw + 1;
+    double2 *win = rc_lds, *prow = win + (size_t)(bw + 1) * W, *mult = prow + 128, *red = mult + 64;
+    double *work = a.work + (size_t)blockIdx.x * rc_slot_doubles(N, bw);
+    double2 *U = reinterpret_cast<double2 *>(work), *Lm = U + (size_t)N * W, *y = Lm + (size_t)N * bw;
+    int *piv = reinterpret_cast<int *>(y + N);
+    for (int it = blockIdx.x; it < a.nmat; it += gridDim.x) {
+        // the band, row by row, into U's rows; the scale of the zero-pivot perturbation from its diagonal (resolvent.hip's rule)
+        double dmax = 0.0, dflo = 0.0;
+        for (int r = wv; r < N; r += RC_NW)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int c = lane + 64 * h;
+                if (c < W) {
+                    double re, im, fl;
+                    rc_entry(a, it, r, r - bw + c, re, im, fl);
+                    U[(size_t)r * W + c] = make_double2(re, im);
+                    if (c == bw) { dmax = fmax(dmax, fabs(re) + fabs(im)); dflo = fmax(dflo, fl); }
+                }
+            }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { dmax = fmax(dmax, __shfl_xor(dmax, off)); dflo = fmax(dflo, __shfl_xor(dflo, off)); }
+        if (lane == 0) red[wv] = make_double2(dmax, dflo);
+        __syncthreads();                                             // the band is in memory (vmcnt(0) and the barrier), red is written
+#pragma unroll
+        for (int q = 0; q < RC_NW; ++q) { dmax = fmax(dmax, red[q].x); dflo = fmax(dflo, red[q].y); }
+        const double pertol = 2.220446049250313e-16 * fmax(fmax(dmax, 2.220446049250313e-16 * dflo), 1e-280);
+        const int nper = rc_factor(N, bw, pertol, U, Lm, piv, win, prow, mult, tid);
+        if (tid == 0) a.info[it] = nper;
+        for (int r = 0; r < a.nrhs; ++r) {
+            // B_r, channel-major, into the ordering of the matrix (read and written as doubles: the ABI promises no more alignment)
+            const double *B = a.B + (size_t)2 * r * N;
+            for (int e = tid; e < N; e += RC_NT) {
+                const int c = e / n, i = e - c * n;
+                y[i * nch + c] = make_double2(B[2 * e], B[2 * e + 1]);
+            }
+            __syncthreads();                                         // y, and with the first right-hand side U, L, piv, are in memory
+            if (wv == 0) rc_solve(N, bw, U, Lm, piv, y, prow, lane);
+            __syncthreads();
+            const size_t mr = (size_t)it * a.nrhs + r;
+            if (a.X) {
+                double *X = a.X + 2 * mr * N;
+                for (int e = tid; e < N; e += RC_NT) {
+                    const int c = e / n, i = e - c * n;
+                    const double2 v = y[i * nch + c];
+                    X[2 * e] = v.x; X[2 * e + 1] = v.y;
+                }
+            }
+            if (a.R)
+                for (int q = 0; q < a.nproj; ++q) {
+                    // bilinear, no conjugate, over all channels: thread-strided partial sums in the caller's order, each wave's
+                    // fixed tree, then the waves in ascending order
+                    const double *P = a.P + (size_t)2 * q * N;
+                    double sr = 0.0, si = 0.0;
+                    for (int e = tid; e < N; e += RC_NT) {
+                        const int c = e / n, i = e - c * n;
+                        const double2 xv = y[i * nch + c];
+                        const double pr = P[2 * e], pi = P[2 * e + 1];
+                        sr += pr * xv.x - pi * xv.y;
+                        si += pr * xv.y + pi * xv.x;
+                    }
+                    sr = wave_sum(sr); si = wave_sum(si);
+                    if (lane == 0) red[wv] = make_double2(sr, si);
+                    lds_barrier();
+                    if (tid == 0) {
+                        double tr = red[0].x, ti = red[0].y;
+#pragma unroll
+                        for (int u = 1; u < RC_NW; ++u) { tr += red[u].x; ti += red[u].y; }
+                        a.R[2 * (mr * a.nproj + q)] = tr; a.R[2 * (mr * a.nproj + q) + 1] = ti;
+                    }
+                    lds_barrier();
+                }
+            __syncthreads();                                         // every load of y is back before the next right-hand side overwrites it
+        }
+    }
+}
+
+int resolvent_coupled_max_band() { return RC_BMAX; }
+size_t resolvent_coupled_slot_doubles(int n, int k, int nch) { return rc_slot_doubles(n * nch, nch * k - 1); }
+
+static int rc_allow_lds()
+{
+    static bool done = false;
+    if (!done) {
+        BSP_HIP(allow_lds(resolvent_coupled_kernel, rc_lds_bytes(RC_BMAX)));
+        done = true;
+    }
+    return BSP_OK;
+}
+
+int resolvent_coupled_slots(int k, int nch, int nmat, int *slots)
+{
+    if (k < 2 || nch < 1 || nmat < 1 || (long)nch * k - 1 > RC_BMAX) return BSP_ERR_ARG;
+    int rc = rc_allow_lds();
+    if (rc) return rc;
+    int per_cu = 0;
+    const int cus = device_cus();
+    BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_coupled_kernel, RC_NT, rc_lds_bytes(nch * k - 1)));
+    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+    *slots = (int)(r < nmat ? r : nmat);
+    return BSP_OK;
+}
+
+int launch_resolvent_coupled(const ResolventCoupledArgs &a, int slots, hipStream_t st)
+{
+    if (a.k < 2 || a.n < 1 || a.nch < 1 || a.nmat < 1 || a.nrhs < 1 || slots < 1 || (long)a.nch * a.k - 1 > RC_BMAX) return BSP_ERR_ARG;
+    if (a.ncoup > 0 && (a.nop < 1 || !a.cr || !a.cc || !a.ctr || !a.GB || !a.acoef)) return BSP_ERR_ARG;
+    int rc = rc_allow_lds();
+    if (rc) return rc;
+    hipLaunchKernelGGL(resolvent_coupled_kernel, dim3(slots), dim3(RC_NT), rc_lds_bytes(a.nch * a.k - 1), st, a);
+    BSP_HIP(hipGetLastError());
+    return BSP_OK;
+}
+
+}  // namespace bsp

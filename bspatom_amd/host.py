@@ -934,6 +934,139 @@ def cauchy_moments(prob, n_ini, order):
     return (2.0 / 3.0) * R[0, :, 0, 0].real
 
 
+# ---- channels coupled to all orders: one banded LU across the channels (Problem.resolvent_coupled) --------------------------
+def band_transpose(G):
+    """The full band(s) of the transposed operator(s): T[..., d + k - 1, i] = G^T(i, i + d) = G[..., -d + k - 1, i + d], zero where
+    i + d is outside 0 .. n-1.  An index shuffle, no arithmetic: resolvent_coupled with an entry (cr, cc, 1) on G equals the entry
+    (cr, cc, 0) on band_transpose(G) bit for bit."""
+    import numpy as np
+    G = np.asarray(G)
+    k, n = (G.shape[-2] + 1) // 2, G.shape[-1]
+    T = np.zeros_like(G)
+    for d in range(-(k - 1), k):
+        lo, hi = max(0, -d), min(n, n - d)                     # rows i with 0 <= i + d < n
+        T[..., d + k - 1, lo:hi] = G[..., -d + k - 1, lo + d:hi + d]
+    return T
+
+
+def _full_to_dense(FB, dtype):
+    import numpy as np
+    k, n = (FB.shape[0] + 1) // 2, FB.shape[1]
+    A = np.zeros((n, n), dtype=dtype)
+    for d in range(-(k - 1), k):
+        i = np.arange(max(0, -d), min(n, n - d))
+        A[i, i + d] = FB[d + k - 1, i]
+    return A
+
+
+def coupled_dense(SB, HB, l, z, couplings, G, a, W=None, w=None, dtype=None):
+    """The dense matrix of ONE coupled system in channel-major order (block (c, c') in rows c n .. and columns c' n ..), for small
+    checks: diagonal block c = H_l[c] - i W_w[c] - z[c] S, and entry p of `couplings` = (cr, cc, ctr) adds sum_o a[p, o] G[o] (its
+    transpose where ctr) to block (cr, cc).  SB (k, n), HB (nl, k, n) upper bands with HB[l] the channel l (Problem.assemble(0, nl));
+    G (nop, 2k-1, n) or (2k-1, n); a (ncoup, nop) or (ncoup,) complex; W (nabs, 2k-1, n) or (2k-1, n) full bands, w (nch,) with -1 =
+    no absorber, None = W[0] on every channel.  dtype: complex128, or clongdouble for a matrix formed in extended precision."""
+    import numpy as np
+    dtype = np.complex128 if dtype is None else dtype
+    real = np.longdouble if dtype == np.clongdouble else np.float64
+    SB, HB = np.asarray(SB), np.asarray(HB)
+    k, n = SB.shape
+    l = [int(v) for v in np.atleast_1d(l)]
+    nch = len(l)
+    z = np.broadcast_to(np.asarray(z, dtype=np.complex128), (nch,))
+    def sym(UB):                                               # the symmetric matrix of an upper band UB[d, i] = A(i, i + d)
+        A = np.zeros((n, n), dtype=real)
+        for d in range(k):
+            i = np.arange(n - d)
+            A[i, i + d] = UB[d, :n - d]
+            A[i + d, i] = UB[d, :n - d]
+        return A
+    M = np.zeros((nch * n, nch * n), dtype=dtype)
+    S = sym(SB).astype(dtype)
+    if W is not None:
+        W = np.asarray(W, dtype=np.float64).reshape(-1, 2 * k - 1, n)
+    for c in range(nch):
+        D = sym(HB[l[c]]).astype(dtype) - dtype(z[c]) * S
+        wc = (0 if W is not None else -1) if w is None else int(np.atleast_1d(w)[c])
+        if wc >= 0:
+            D = D - dtype(1j) * _full_to_dense(W[wc], real).astype(dtype)
+        M[c * n:(c + 1) * n, c * n:(c + 1) * n] = D
+    if couplings:
+        G = np.asarray(G, dtype=np.float64).reshape(-1, 2 * k - 1, n)
+        a = np.asarray(a, dtype=np.complex128).reshape(len(couplings), G.shape[0])
+        Gd = [_full_to_dense(g, real).astype(dtype) for g in G]
+        for p, (cr, cc, ctr) in enumerate(couplings):
+            for o, g in enumerate(Gd):
+                M[cr * n:(cr + 1) * n, cc * n:(cc + 1) * n] += dtype(a[p, o]) * (g.T if ctr else g)
+    return M
+
+
+def stark_system(channels, F):
+    """The static field F z between `channels` (a list of (l, m)): (couplings, a) for resolvent_coupled with G = dipole_bands()[0],
+    the band of r.  For every block of dipole_blocks(channels, kind_pi=1) -- bra position a_ <= ket position b_ -- BOTH directions
+    are generated: (a_, b_, 0) and (b_, a_, 1), the second as the transpose, with the same real coefficient F <lf m| cos theta |l0 m>,
+    (l+1) / sqrt((2l+1)(2l+3)) between l and l+1 at m = 0.  That is dipole_blocks' angular factor c0 c1 without the reference's phase
+    (-1)^(lf + l0), which is -1 on every dipole block (a field of the other direction: the levels do not see it, the vectors do)."""
+    import numpy as np
+    couplings, a = [], []
+    for a_, b_, _l0, _lf, c0, coef in dipole_blocks(channels, kind_pi=1):
+        couplings += [(a_, b_, 0), (b_, a_, 1)]
+        a += [-float(F) * c0 * coef[0]] * 2
+    return couplings, np.asarray(a, dtype=np.complex128)
+
+
+def floquet_system(channels, nphot, omega, F):
+    """A monochromatic field F z cos(omega t) in the Floquet picture: the blocks (channel, n), n = -nphot .. nphot ascending, of the
+    parity class that block (channels[0], 0) belongs to (l - l_0 - n even), block c with the energy z - n omega, and the coupling
+    (F / 2) z between dipole-coupled channels whose n differ by one.  Returns (blocks, zoff, couplings, a): blocks a list of
+    ((l, m), n) -- l of block c is blocks[c][0][0] --, zoff[c] = -n omega to be added to the quasi-energy, couplings and a as
+    stark_system returns them (both directions, the second as the transpose)."""
+    import numpy as np
+    l_0 = channels[0][0]
+    blocks = [(ch, nn) for nn in range(-nphot, nphot + 1) for ch in channels if (ch[0] - l_0 - nn) % 2 == 0]
+    zoff = np.array([-nn * float(omega) for _, nn in blocks])
+    couplings, a = [], []
+    for a_, b_, _l0, _lf, c0, coef in dipole_blocks([ch for ch, _ in blocks], kind_pi=1):
+        if abs(blocks[a_][1] - blocks[b_][1]) != 1:
+            continue
+        couplings += [(a_, b_, 0), (b_, a_, 1)]
+        a += [-0.5 * float(F) * c0 * coef[0]] * 2             # stark_system's sign
+    return blocks, zoff, couplings, np.asarray(a, dtype=np.complex128)
+
+
+def coupled_eigenpair(prob, l, couplings, G, a, shift, x0, zoff=None, W=None, w=None, iters=3, solver=None):
+    """Inverse iteration on the coupled pencil: the eigenvalue lambda next to `shift` of
+        (sum_c (H_l[c] - i W_w[c] - (lambda + zoff[c]) S) + V) x = 0,
+    every solve one Problem.resolvent_coupled call at z[c] = shift + zoff[c] (a dressed energy in a static field: stark_system; a
+    quasi-energy: floquet_system and its zoff).  x0: (nch, nfun), e.g. (c_1s, 0, ..).  Per iteration b = S x (band_apply on every
+    channel), y = M(shift)^-1 b, and the Rayleigh quotient of y, lambda = shift + y^T b / y^T S y -- BILINEAR, no conjugate, so it
+    is complex when an absorber is present (a width) --, x = y / sqrt(y^T S y).  solver: a callable (l, z, B) -> y (nch, nfun) that
+    stands in for the GPU call (a dense solve in the CPU tests); prob then only needs the attribute SB_full, the overlap's full
+    band (2k-1, nfun).  Returns (lambda, x, history): history the lambda of every iteration."""
+    import numpy as np
+    x = np.asarray(x0, dtype=np.complex128)
+    nch = x.shape[0]
+    SBf = getattr(prob, "SB_full", None)
+    if SBf is None:
+        SBf = prob.operator_bands(np.ones(prob.quadrature()[0].size), [0])[0]
+    zoff = np.zeros(nch) if zoff is None else np.asarray(zoff)
+    z = complex(shift) + zoff
+    if solver is None:
+        def solver(l_, z_, B_):
+            X, _, info = prob.resolvent_coupled(l_, z_, B_, couplings=couplings, G=G, a=a, W=W, w=w)
+            if np.any(info != 0):
+                raise ArithmeticError("coupled_eigenpair: the shift is on an eigenvalue (%d pivots replaced)" % int(info.max()))
+            return X[0, 0]
+    lam, history = complex(shift), []
+    for _ in range(iters):
+        b = band_apply(SBf, x)
+        y = np.asarray(solver(l, z, b), dtype=np.complex128).reshape(nch, -1)
+        ysy = np.sum(y * band_apply(SBf, y))
+        lam = complex(shift) + np.sum(y * b) / ysy
+        x = y / np.sqrt(ysy)
+        history.append(lam)
+    return lam, x, history
+
+
 # ---- KIND_PI = 0 on several GPUs: one process per GPU, channels sharded, spectra gathered (SURVEY 8e) ---------------
 def write_structure_outputs(nfun, lmax, E, l_ini, wf, outdir):
     """Enl.dat, wf_n0.dat and the stdout text of a KIND_PI = 0 run from the spectra E[l][i] and the tabulated initial

@@ -259,6 +259,58 @@ int bspatom_resolvent_chain_dev(bspatom_problem *p, int nchain, int nstage, cons
                                 const double *WB_dev, const int32_t *w, int nop, const double *GB_dev, const double *a, int nrhs,
                                 const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev, int32_t *info);
 
+/* Channels coupled to ALL orders in one banded LU (csrc/resolvent_coupled.hip).  bspatom_resolvent answers for one channel, a chain
+ * multiplies such answers with one operator in between -- perturbation theory.  A static field (Stark shifts and widths), a
+ * monochromatic field in the Floquet picture (dressed states, multiphoton rates without a time propagation), any potential that mixes
+ * l is ONE linear system:  (sum_c (H_{l_c} - i W_c - z_c S) + V) x = b.  Matrix m < nmat acts on nch blocks of nfun coefficients:
+ *   diagonal block c:  H_{l[m*nch+c]} - i W_{w[m*nch+c]} - z_{m,c} S,   z_{m,c} = z[2(m*nch+c)] + i z[2(m*nch+c)+1]
+ *     -- every channel of every matrix has its own energy (a Floquet block carries z - n omega); l may repeat within a matrix; w as in
+ *     bspatom_resolvent per (m, c): w[..] = -1: no absorber for that block; w == NULL: absorber 0 for every block if WB is given,
+ *     none otherwise; WB: nabs FULL bands;
+ *   coupling entry p < ncoup:  block (row channel cr[p], column channel cc[p]) gains sum_o alpha_{m,p,o} G_o, or G_o^T where
+ *     ctr[p] = 1;  alpha_{m,p,o} = a[((m*ncoup+p)*nop+o)*2] + i a[((m*ncoup+p)*nop+o)*2 + 1] is COMPLEX;  GB: nop FULL bands in
+ *     bspatom_operator_bands' layout, both triangles as given.  The topology (cr, cc, ctr) is shared by all matrices of the call, the
+ *     coefficients are per matrix.  NO partner is added: a Hermitian coupling is two entries, the second with ctr = 1 and the
+ *     conjugate coefficient (bspatom_tdse_static's convention).  cr[p] == cc[p] is allowed (an in-channel perturbation); entries on
+ *     the same block add in ascending p, after the diagonal-block formula, each as re += Re alpha * G, im += Im alpha * G for o
+ *     ascending.  ncoup = 0 needs neither cr, cc, ctr, GB nor a.
+ * Right-hand sides, shared by all matrices, and projections are channel-major, nch*nfun complex each:
+ *   B[(r*nch+c)*nfun+i],   P[(q*nch+c)*nfun+i];   X[((((size_t)m*nrhs+r)*nch+c)*nfun+i] = x_{m,r}(i, c);
+ *   R[((size_t)m*nrhs+r)*nproj+q] = sum_c sum_i P_q(i, c) x_{m,r}(i, c)   (bilinear, no conjugate, over ALL channels);
+ *   info[m] = number of pivots replaced, with bspatom_resolvent's meaning and threshold (eps * max |M_jj| over the whole diagonal).
+ * At least one of X and R must be given; P may be NULL when R is.
+ * Ordering: the matrix that is factored has unknown (i, c) at position i*nch + c; it is banded with half-width bw = nch*k - 1 (this
+ *   build does not narrow bw from the topology).  The matrix is the one in that ordering: a dense solve of the same system meets the
+ *   same band and, with the same pivot rule, the same growth.
+ * Factorisation: one workgroup per matrix, LU with partial pivoting by |Re| + |Im|, ties to the smallest row; complex products in the
+ *   plain four-product form; one reciprocal per pivot (bspatom_resolvent's).  The row window, (bw+1) x (2bw+1) complex, lives in LDS.
+ * Limit: bw <= BSPATOM_COUPLED_MAX_BAND = 63: the pivot candidates of a column, at most bw + 1, then fit one wavefront, and the window,
+ *   at most 64 x 127 complex = 130 KB, fits the 160 KiB of LDS.  That covers k = 9 with seven channels and k = 16 with four.  Beyond it:
+ *   BSPATOM_ERR_UNSUPPORTED, the limit printed on stderr.
+ * Guarantees:
+ *   (K1) results are bit-identical from run to run;
+ *   (K2) the results of matrix m depend on its own l, z, w, a, on the shared topology and on WB, GB, B_r, P_q alone -- not on the other
+ *        matrices, on nmat, nrhs or nproj, on the work slots, on the grouping below, or on the host versus _dev variant;
+ *   (K3) with every Im z = 0, no absorber, real coefficients and real B every imaginary part of X is +-0.0 exactly;
+ *   (K4) an entry given with ctr = 1 equals, bit for bit, the same entry with ctr = 0 and the transposed band.
+ * NOT promised: nch = 1 is not bspatom_resolvent bit for bit -- another kernel, another order of summation; it satisfies the same
+ * system to the same backward error.
+ * The host variant processes the matrices in groups under bspatom_resolvent's bound ("resolvent_stage_mb": the X of one group, one
+ * matrix at least); "resolvent_slots" applies.  Scratch per work slot (resident workgroup), within the same bound: U, L and one
+ * vector, N*(3bw+2) complex with N = nch*nfun, plus N pivot indices -- nch*nfun*(6*nch*k - 2) doubles and nch*nfun 32-bit integers.
+ * BSPATOM_ERR_ARG: what bspatom_resolvent names, per (m, c); nch < 1; ncoup < 0; a channel index outside 0..nch-1; ctr outside {0, 1};
+ * ncoup > 0 with nop < 1 or with any of cr, cc, ctr, GB, a NULL.  The _dev variant: WB, GB, B, P, X, R in device memory of the problem's
+ * device, written in place; l, z, w, cr, cc, ctr, a, info stay host pointers. */
+#define BSPATOM_COUPLED_MAX_BAND 63
+int bspatom_resolvent_coupled(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs, const double *WB,
+                              const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop,
+                              const double *GB, const double *a, int nrhs, const double *B, int nproj, const double *P, double *X,
+                              double *R, int32_t *info);
+int bspatom_resolvent_coupled_dev(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,
+                                  const double *WB_dev, const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc,
+                                  const int32_t *ctr, int nop, const double *GB_dev, const double *a, int nrhs, const double *B_dev,
+                                  int nproj, const double *P_dev, double *X_dev, double *R_dev, int32_t *info);
+
 /* WRITE_WF (Bsp_Atom.f90:118-146): u(r_i) = sum_j c_j B_j(r_i), r_i = ra + i*(rb-ra)/npts,
  * i = 0..npts.  Returns BSPATOM_ERR_BSPLVB where the reference STOPs. r[npts+1], u[npts+1]. */
 int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u);
