@@ -34,7 +34,7 @@ class Sizes(C.Structure):
 EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup", "bspatom_problem_create", "bspatom_problem_destroy",
            "bspatom_problem_sizes", "bspatom_problem_grid", "bspatom_problem_route", "bspatom_assemble", "bspatom_solve", "bspatom_solve_dev",
            "bspatom_eigvec", "bspatom_eigvecs", "bspatom_eigvecs_batch", "bspatom_eigvecs_batch_dev", "bspatom_dipole_bands", "bspatom_dipole_elements", "bspatom_dipole_matrix", "bspatom_dipole_matrix_dev",
-           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_resolvent", "bspatom_resolvent_dev", "bspatom_resolvent_chain", "bspatom_resolvent_chain_dev", "bspatom_resolvent_coupled", "bspatom_resolvent_coupled_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_tdse_adaptive", "bspatom_tdse_adaptive_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
+           "bspatom_operator_bands", "bspatom_operator_bands_dev", "bspatom_operator_matrix", "bspatom_operator_matrix_dev", "bspatom_resolvent", "bspatom_resolvent_dev", "bspatom_resolvent_chain", "bspatom_resolvent_chain_dev", "bspatom_resolvent_coupled", "bspatom_resolvent_coupled_dev", "bspatom_resolvent_coupled_wide", "bspatom_resolvent_coupled_wide_dev", "bspatom_write_wf", "bspatom_quadrature", "bspatom_tabulate", "bspatom_tabulate_dev", "bspatom_wavefunctions", "bspatom_wavefunctions_dev", "bspatom_tdse_propagate", "bspatom_tdse_propagate_dev", "bspatom_tdse_observe", "bspatom_tdse_observe_dev", "bspatom_tdse_lawson", "bspatom_tdse_lawson_dev", "bspatom_tdse_static", "bspatom_tdse_static_dev", "bspatom_tdse_fields", "bspatom_tdse_fields_dev", "bspatom_tdse_adaptive", "bspatom_tdse_adaptive_dev", "bspatom_last_timing", "bspatom_early_vector_state", "bsp_dsygv_", "bspatom_stage_gemm",
            "bspatom_stage_standard_form", "bspatom_stage_sy2sb", "bspatom_stage_panel", "bspatom_stage_sb2st", "bspatom_stage_sb2sb", "bspatom_stage_bisect", "bspatom_stage_crawford", "bspatom_stage_band_eigenvalue",
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
@@ -80,6 +80,8 @@ def lib():
         L.bspatom_resolvent_chain_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.bspatom_resolvent_coupled.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.bspatom_resolvent_coupled_dev.argtypes = list(L.bspatom_resolvent_coupled.argtypes)
+        L.bspatom_resolvent_coupled_wide.argtypes = list(L.bspatom_resolvent_coupled.argtypes)
+        L.bspatom_resolvent_coupled_wide_dev.argtypes = list(L.bspatom_resolvent_coupled.argtypes)
         L.bspatom_write_wf.argtypes = [vp, vp, i32, vp, vp]
         L.bspatom_quadrature.argtypes = [vp, C.POINTER(i32), vp, vp]
         L.bspatom_tabulate.argtypes = [vp, i32, vp, i32, vp, vp, vp]
@@ -462,16 +464,8 @@ class Problem:
         bc = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(v, (nmat, nch)))
         return nmat, nch, bc(l), bc(z), bc(w), cr, cc, ctr, a
 
-    def resolvent_coupled(self, l, z, B, couplings=None, G=None, a=None, W=None, w=None, P=None, want_x=True):
-        """Several channels coupled to ALL orders, one banded LU per matrix on the GPU (bspatom_resolvent_coupled): matrix m acts on
-        nch blocks of nfun coefficients, diagonal block c = H_l[m, c] - i W_w[m, c] - z[m, c] S, and every entry (cr, cc, ctr) of
-        `couplings` adds sum_o a[m, p, o] G[o] -- its transpose where ctr = 1 -- to block (cr, cc); no partner is added, a Hermitian
-        coupling is two entries.  l, z, w: (nmat, nch), broadcast from (nch,); every channel has its own energy (a Floquet block
-        carries z - n omega); G: full bands (nop, 2k-1, nfun) or (2k-1, nfun) as dipole_bands / operator_bands return them; a: COMPLEX,
-        (nmat, ncoup, nop), broadcast from (ncoup, nop) or, with one operator, (ncoup,); None with one operator: coefficient 1.
-        B: (nrhs, nch, nfun) or (nch, nfun), P: (nproj, nch, nfun), (nch, nfun) or None; W, w as in resolvent.  Returns (X, R, info):
-        X (nmat, nrhs, nch, nfun) complex128 or None (want_x False), R (nmat, nrhs, nproj) = sum over all channels of P x (bilinear)
-        or None (P None), info (nmat,) replaced pivots (0).  nch * k - 1 <= 63, else BspAtomError(-5)."""
+    def _resolvent_coupled_host(self, entry, l, z, B, couplings, G, a, W, w, P, want_x):
+        """resolvent_coupled / resolvent_coupled_wide: the host arrays of one call to the entry point `entry`"""
         n = self.nfun
         W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
         G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
@@ -483,9 +477,37 @@ class Problem:
         X = np.zeros((nmat, nrhs, nch, n), dtype=np.complex128) if want_x else None
         R = np.zeros((nmat, nrhs, nproj), dtype=np.complex128) if P is not None else None
         info = np.zeros(nmat, dtype=np.int32)
-        _chk(lib().bspatom_resolvent_coupled(self._h, nmat, nch, _p(l), _p(z), nabs, _p(W), _p(w), ncoup, _p(cr), _p(cc), _p(ctr), nop,
-                                             _p(G), _p(a), nrhs, _p(B), nproj, _p(P), _p(X), _p(R), _p(info)), "bspatom_resolvent_coupled")
+        _chk(getattr(lib(), entry)(self._h, nmat, nch, _p(l), _p(z), nabs, _p(W), _p(w), ncoup, _p(cr), _p(cc), _p(ctr), nop,
+                                    _p(G), _p(a), nrhs, _p(B), nproj, _p(P), _p(X), _p(R), _p(info)), entry)
         return X, R, info
+
+    def resolvent_coupled(self, l, z, B, couplings=None, G=None, a=None, W=None, w=None, P=None, want_x=True):
+        """Several channels coupled to ALL orders, one banded LU per matrix on the GPU (bspatom_resolvent_coupled): matrix m acts on
+        nch blocks of nfun coefficients, diagonal block c = H_l[m, c] - i W_w[m, c] - z[m, c] S, and every entry (cr, cc, ctr) of
+        `couplings` adds sum_o a[m, p, o] G[o] -- its transpose where ctr = 1 -- to block (cr, cc); no partner is added, a Hermitian
+        coupling is two entries.  l, z, w: (nmat, nch), broadcast from (nch,); every channel has its own energy (a Floquet block
+        carries z - n omega); G: full bands (nop, 2k-1, nfun) or (2k-1, nfun) as dipole_bands / operator_bands return them; a: COMPLEX,
+        (nmat, ncoup, nop), broadcast from (ncoup, nop) or, with one operator, (ncoup,); None with one operator: coefficient 1.
+        B: (nrhs, nch, nfun) or (nch, nfun), P: (nproj, nch, nfun), (nch, nfun) or None; W, w as in resolvent.  Returns (X, R, info):
+        X (nmat, nrhs, nch, nfun) complex128 or None (want_x False), R (nmat, nrhs, nproj) = sum over all channels of P x (bilinear)
+        or None (P None), info (nmat,) replaced pivots (0).  nch * k - 1 <= 63, else BspAtomError(-5)."""
+        return self._resolvent_coupled_host("bspatom_resolvent_coupled", l, z, B, couplings, G, a, W, w, P, want_x)
+
+    def resolvent_coupled_wide(self, l, z, B, couplings=None, G=None, a=None, W=None, w=None, P=None, want_x=True):
+        """resolvent_coupled for WIDE bands (bspatom_resolvent_coupled_wide, csrc/resolvent_wide.hip): the same arguments and results,
+        a blocked LU on the matrix cores, nch * k - 1 <= BSPATOM_COUPLED_WIDE_MAX_BAND = 255 (any half-width from 1 on), else
+        BspAtomError(-5).  Not bit-identical to resolvent_coupled where both apply: another order of summation."""
+        return self._resolvent_coupled_host("bspatom_resolvent_coupled_wide", l, z, B, couplings, G, a, W, w, P, want_x)
+
+    def _resolvent_coupled_device(self, entry, l, z, nrhs, B_ptr, couplings, nop, G_ptr, a, nabs, W_ptr, w, nproj, P_ptr, X_ptr, R_ptr):
+        """resolvent_coupled_dev / resolvent_coupled_wide_dev: one call to the entry point `entry` on device pointers"""
+        nmat, nch, l, z, w, cr, cc, ctr, a = self._coupled_system(l, z, w, couplings, a, nop)
+        info = np.zeros(nmat, dtype=np.int32)
+        vp = lambda v: None if v is None else C.c_void_p(v)
+        _chk(getattr(lib(), entry)(self._h, nmat, nch, _p(l), _p(z), nabs, vp(W_ptr), _p(w), 0 if cr is None else cr.size,
+                                    _p(cr), _p(cc), _p(ctr), nop, vp(G_ptr), _p(a), nrhs, vp(B_ptr), nproj, vp(P_ptr),
+                                    vp(X_ptr), vp(R_ptr), _p(info)), entry)
+        return info
 
     def resolvent_coupled_dev(self, l, z, nrhs, B_ptr, couplings=None, nop=0, G_ptr=None, a=None, nabs=0, W_ptr=None, w=None, nproj=0,
                               P_ptr=None, X_ptr=None, R_ptr=None):
@@ -493,13 +515,14 @@ class Problem:
         (nproj * nch * nfun complex), X (nmat * nrhs * nch * nfun complex) and R (nmat * nrhs * nproj complex) in device memory of this
         problem's device, e.g. torch tensors' data_ptr(); X and R are written in place (either pointer may be None).  l, z, w,
         couplings, a are host values as in resolvent_coupled.  Returns info (nmat,)."""
-        nmat, nch, l, z, w, cr, cc, ctr, a = self._coupled_system(l, z, w, couplings, a, nop)
-        info = np.zeros(nmat, dtype=np.int32)
-        vp = lambda v: None if v is None else C.c_void_p(v)
-        _chk(lib().bspatom_resolvent_coupled_dev(self._h, nmat, nch, _p(l), _p(z), nabs, vp(W_ptr), _p(w), 0 if cr is None else cr.size,
-                                                 _p(cr), _p(cc), _p(ctr), nop, vp(G_ptr), _p(a), nrhs, vp(B_ptr), nproj, vp(P_ptr),
-                                                 vp(X_ptr), vp(R_ptr), _p(info)), "bspatom_resolvent_coupled_dev")
-        return info
+        return self._resolvent_coupled_device("bspatom_resolvent_coupled_dev", l, z, nrhs, B_ptr, couplings, nop, G_ptr, a, nabs, W_ptr, w,
+                                              nproj, P_ptr, X_ptr, R_ptr)
+
+    def resolvent_coupled_wide_dev(self, l, z, nrhs, B_ptr, couplings=None, nop=0, G_ptr=None, a=None, nabs=0, W_ptr=None, w=None, nproj=0,
+                                   P_ptr=None, X_ptr=None, R_ptr=None):
+        """resolvent_coupled_dev for wide bands (bspatom_resolvent_coupled_wide_dev): the same arguments, nch * k - 1 <= 255"""
+        return self._resolvent_coupled_device("bspatom_resolvent_coupled_wide_dev", l, z, nrhs, B_ptr, couplings, nop, G_ptr, a, nabs, W_ptr,
+                                              w, nproj, P_ptr, X_ptr, R_ptr)
 
     def write_wf(self, c, npts=10000):
         c = np.ascontiguousarray(c, dtype=np.float64)

@@ -3,6 +3,7 @@
 // last bspatom_solve or bspatom_assemble); all work goes on the problem's stream and the scratch of a call is freed when it returns.
 // bspatom_resolvent_chain / _dev: chains of such solves with an operator in between, one launch for the whole batch.
 // bspatom_resolvent_coupled / _dev: several channels coupled to all orders in one banded LU (resolvent_coupled.hip).
+// bspatom_resolvent_coupled_wide / _dev: the same call on the blocked LU for wide bands (resolvent_wide.hip).
 #include <algorithm>
 #include "capi_internal.h"
 
@@ -143,10 +144,11 @@ static int resolvent_chain_impl(bspatom_problem *p, int nchain, int nstage, cons
 
 // bspatom_resolvent_coupled / _dev: nmat matrices of nch coupled channels each, one workgroup per matrix (resolvent_coupled.hip); the
 // plumbing of resolvent_impl with nmat * nch channel records, the coupling topology and its complex coefficients beside them.
+// wide: the same arguments to resolvent_wide.hip, its limit, its slots and its scratch.
 static int resolvent_coupled_impl(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs, const double *WB,
                                   const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop,
                                   const double *GB, const double *ac, int nrhs, const double *B, int nproj, const double *P, double *X,
-                                  double *R, int32_t *info, bool dev)
+                                  double *R, int32_t *info, bool dev, bool wide)
 {
     if (!p || !l || !z || !B || !info || (!X && !R)) return BSP_ERR_ARG;
     if (nmat < 1 || nch < 1 || nrhs < 1 || nabs < 0 || nproj < 0 || ncoup < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
@@ -163,9 +165,10 @@ static int resolvent_coupled_impl(bspatom_problem *p, int nmat, int nch, const i
         if (cr[q] < 0 || cr[q] >= nch || cc[q] < 0 || cc[q] >= nch || ctr[q] < 0 || ctr[q] > 1) return BSP_ERR_ARG;
     const HostSetup &h = p->hs;
     const int n = h.nfun, k = h.k;
-    if ((long long)nch * k - 1 > resolvent_coupled_max_band()) {
-        fprintf(stderr, "bspatom_resolvent_coupled: half-width nch*k - 1 = %lld exceeds BSPATOM_COUPLED_MAX_BAND = %d\n",
-                (long long)nch * k - 1, resolvent_coupled_max_band());
+    const int max_band = wide ? resolvent_wide_max_band() : resolvent_coupled_max_band();
+    if ((long long)nch * k - 1 > max_band) {
+        fprintf(stderr, "bspatom_resolvent_coupled%s: half-width nch*k - 1 = %lld exceeds BSPATOM_COUPLED%s_MAX_BAND = %d\n",
+                wide ? "_wide" : "", (long long)nch * k - 1, wide ? "_WIDE" : "", max_band);
         return BSP_ERR_UNSUPPORTED;
     }
     if ((long long)nch * n > 0x3fffffffLL) return BSP_ERR_ARG;
@@ -174,9 +177,9 @@ static int resolvent_coupled_impl(bspatom_problem *p, int nmat, int nch, const i
     BSP_HIP(hipSetDevice(p->device));
     int rc;
     int slots = 0;
-    if ((rc = resolvent_coupled_slots(k, nch, nmat, &slots))) return rc;
+    if ((rc = wide ? resolvent_wide_slots(k, nch, nmat, &slots) : resolvent_coupled_slots(k, nch, nmat, &slots))) return rc;
     if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, nmat);
-    const size_t slot_doubles = resolvent_coupled_slot_doubles(n, k, nch);
+    const size_t slot_doubles = wide ? resolvent_wide_slot_doubles(n, k, nch, nrhs) : resolvent_coupled_slot_doubles(n, k, nch);
     slots = (int)std::max<size_t>(1, std::min<size_t>(slots, stage / (slot_doubles * sizeof(double))));
     // the host variant's groups: the X of one group within the bound, one matrix at least
     const size_t x_mat = (size_t)2 * nrhs * N;                       // doubles of one matrix's X
@@ -215,7 +218,7 @@ static int resolvent_coupled_impl(bspatom_problem *p, int nmat, int nch, const i
         a.acoef = ops ? dac.p + (size_t)2 * m0 * ncoup * nop : nullptr;
         a.X = X ? (dev ? X + (size_t)m0 * x_mat : dX.p) : nullptr;
         a.R = R ? (dev ? R : dR.p) + (size_t)2 * m0 * nrhs * nproj : nullptr;
-        rc = launch_resolvent_coupled(a, std::min(slots, g), p->st);
+        rc = wide ? launch_resolvent_wide(a, std::min(slots, g), p->st) : launch_resolvent_coupled(a, std::min(slots, g), p->st);
         if (!rc && !dev && X) rc = HIP_RC(hipMemcpyAsync(X + (size_t)m0 * x_mat, dX.p, (size_t)g * x_mat * sizeof(double), hipMemcpyDeviceToHost, p->st));
     }
     if (!rc && !dev && R) rc = HIP_RC(hipMemcpyAsync(R, dR.p, r_all * sizeof(double), hipMemcpyDeviceToHost, p->st));
@@ -228,7 +231,7 @@ extern "C" int bspatom_resolvent_coupled(bspatom_problem *p, int nmat, int nch, 
                                          const int32_t *ctr, int nop, const double *GB, const double *a, int nrhs, const double *B,
                                          int nproj, const double *P, double *X, double *R, int32_t *info)
 {
-    return resolvent_coupled_impl(p, nmat, nch, l, z, nabs, WB, w, ncoup, cr, cc, ctr, nop, GB, a, nrhs, B, nproj, P, X, R, info, false);
+    return resolvent_coupled_impl(p, nmat, nch, l, z, nabs, WB, w, ncoup, cr, cc, ctr, nop, GB, a, nrhs, B, nproj, P, X, R, info, false, false);
 }
 extern "C" int bspatom_resolvent_coupled_dev(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,
                                              const double *WB_dev, const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc,
@@ -237,7 +240,23 @@ extern "C" int bspatom_resolvent_coupled_dev(bspatom_problem *p, int nmat, int n
                                              int32_t *info)
 {
     return resolvent_coupled_impl(p, nmat, nch, l, z, nabs, WB_dev, w, ncoup, cr, cc, ctr, nop, GB_dev, a, nrhs, B_dev, nproj, P_dev,
-                                  X_dev, R_dev, info, true);
+                                  X_dev, R_dev, info, true, false);
+}
+extern "C" int bspatom_resolvent_coupled_wide(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,
+                                              const double *WB, const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc,
+                                              const int32_t *ctr, int nop, const double *GB, const double *a, int nrhs, const double *B,
+                                              int nproj, const double *P, double *X, double *R, int32_t *info)
+{
+    return resolvent_coupled_impl(p, nmat, nch, l, z, nabs, WB, w, ncoup, cr, cc, ctr, nop, GB, a, nrhs, B, nproj, P, X, R, info, false, true);
+}
+extern "C" int bspatom_resolvent_coupled_wide_dev(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,
+                                                  const double *WB_dev, const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc,
+                                                  const int32_t *ctr, int nop, const double *GB_dev, const double *a, int nrhs,
+                                                  const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev,
+                                                  int32_t *info)
+{
+    return resolvent_coupled_impl(p, nmat, nch, l, z, nabs, WB_dev, w, ncoup, cr, cc, ctr, nop, GB_dev, a, nrhs, B_dev, nproj, P_dev,
+                                  X_dev, R_dev, info, true, true);
 }
 
 extern "C" int bspatom_resolvent_chain(bspatom_problem *p, int nchain, int nstage, const int32_t *l, const double *z, int nabs,

@@ -388,6 +388,12 @@ int resolvent_coupled_max_band();              // half-width limit of the couple
 size_t resolvent_coupled_slot_doubles(int n, int k, int nch);
 int resolvent_coupled_slots(int k, int nch, int nmat, int *slots);
 int launch_resolvent_coupled(const ResolventCoupledArgs &a, int slots, hipStream_t st);
+// resolvent_wide.hip: the same system and arguments in a blocked LU for half-widths up to BSPATOM_COUPLED_WIDE_MAX_BAND
+// (bspatom_resolvent_coupled_wide); work: slots * resolvent_wide_slot_doubles, which counts the nrhs vectors of a slot too
+int resolvent_wide_max_band();
+size_t resolvent_wide_slot_doubles(int n, int k, int nch, int nrhs);
+int resolvent_wide_slots(int k, int nch, int nmat, int *slots);
+int launch_resolvent_wide(const ResolventCoupledArgs &a, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

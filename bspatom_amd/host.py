@@ -935,6 +935,9 @@ def cauchy_moments(prob, n_ini, order):
 
 
 # ---- channels coupled to all orders: one banded LU across the channels (Problem.resolvent_coupled) --------------------------
+COUPLED_MAX_BAND = 63                      # BSPATOM_COUPLED_MAX_BAND of include/bspatom.h: resolvent_coupled's half-width limit
+
+
 def band_transpose(G):
     """The full band(s) of the transposed operator(s): T[..., d + k - 1, i] = G^T(i, i + d) = G[..., -d + k - 1, i + d], zero where
     i + d is outside 0 .. n-1.  An index shuffle, no arithmetic: resolvent_coupled with an entry (cr, cc, 1) on G equals the entry
@@ -1036,8 +1039,8 @@ def floquet_system(channels, nphot, omega, F):
 def coupled_eigenpair(prob, l, couplings, G, a, shift, x0, zoff=None, W=None, w=None, iters=3, solver=None):
     """Inverse iteration on the coupled pencil: the eigenvalue lambda next to `shift` of
         (sum_c (H_l[c] - i W_w[c] - (lambda + zoff[c]) S) + V) x = 0,
-    every solve one Problem.resolvent_coupled call at z[c] = shift + zoff[c] (a dressed energy in a static field: stark_system; a
-    quasi-energy: floquet_system and its zoff).  x0: (nch, nfun), e.g. (c_1s, 0, ..).  Per iteration b = S x (band_apply on every
+    every solve one Problem.resolvent_coupled call -- resolvent_coupled_wide where nch k - 1 > 63 -- at z[c] = shift + zoff[c] (a
+    dressed energy in a static field: stark_system; a quasi-energy: floquet_system and its zoff).  x0: (nch, nfun), e.g. (c_1s, 0, ..).  Per iteration b = S x (band_apply on every
     channel), y = M(shift)^-1 b, and the Rayleigh quotient of y, lambda = shift + y^T b / y^T S y -- BILINEAR, no conjugate, so it
     is complex when an absorber is present (a width) --, x = y / sqrt(y^T S y).  solver: a callable (l, z, B) -> y (nch, nfun) that
     stands in for the GPU call (a dense solve in the CPU tests); prob then only needs the attribute SB_full, the overlap's full
@@ -1051,8 +1054,11 @@ def coupled_eigenpair(prob, l, couplings, G, a, shift, x0, zoff=None, W=None, w=
     zoff = np.zeros(nch) if zoff is None else np.asarray(zoff)
     z = complex(shift) + zoff
     if solver is None:
+        # beyond bspatom_resolvent_coupled's half-width (BSPATOM_COUPLED_MAX_BAND) the blocked LU for wide bands answers
+        call = prob.resolvent_coupled_wide if nch * prob.k - 1 > COUPLED_MAX_BAND else prob.resolvent_coupled
+
         def solver(l_, z_, B_):
-            X, _, info = prob.resolvent_coupled(l_, z_, B_, couplings=couplings, G=G, a=a, W=W, w=w)
+            X, _, info = call(l_, z_, B_, couplings=couplings, G=G, a=a, W=W, w=w)
             if np.any(info != 0):
                 raise ArithmeticError("coupled_eigenpair: the shift is on an eigenvalue (%d pivots replaced)" % int(info.max()))
             return X[0, 0]

@@ -311,6 +311,44 @@ int bspatom_resolvent_coupled_dev(bspatom_problem *p, int nmat, int nch, const i
                                   const int32_t *ctr, int nop, const double *GB_dev, const double *a, int nrhs, const double *B_dev,
                                   int nproj, const double *P_dev, double *X_dev, double *R_dev, int32_t *info);
 
+/* The coupled system beyond half-width 63: a BLOCKED banded LU (csrc/resolvent_wide.hip).  Four l with two photons either side are
+ * ten Floquet blocks, bw = 89 at k = 9; a strong static field needs l well beyond 6: bspatom_resolvent_coupled answers those with
+ * BSPATOM_ERR_UNSUPPORTED.  bspatom_resolvent_coupled_wide takes the SAME arguments with the SAME meaning -- B, P, X, R channel-major
+ * in the same layouts; w == NULL and w = -1; cr, cc, ctr and the complex a; info[m] = number of pivots replaced, the same threshold;
+ * the ordering i*nch + c with bw = nch*k - 1, not narrowed from the topology; the same BSPATOM_ERR_ARG list -- for any bw from 1 to
+ * BSPATOM_COUPLED_WIDE_MAX_BAND = 255 (bw <= 63 included): k = 9 with 28 blocks, k = 16 with 16.  Beyond it: BSPATOM_ERR_UNSUPPORTED,
+ * the limit printed on stderr.  bspatom_resolvent_coupled itself is unchanged: its limit, its kernel, its bits.
+ * Factorisation: one workgroup per matrix, no workgroup waits on another.  The band lies in the slot's scratch in LAPACK ZGBTRF's
+ *   column layout (column c holds the rows c - 2bw .. c + bw); the workgroup factors it in panels of 16 columns.  A panel, at most
+ *   bw + 16 rows, is factored in LDS column by column with bspatom_resolvent_coupled's pivot rule exactly: the largest |Re| + |Im|
+ *   over ALL candidates of the column (up to 256: four wavefronts, combined in ascending order), ties to the smallest row; a pivot
+ *   below the threshold is replaced and counted; one reciprocal per pivot.  Then the panel's interchanges go to the columns on its
+ *   right, U12 = L11^-1 A12 on plain FMAs, and A22 -= L21 U12 on v_mfma_f64_16x16x4_f64, the complex product as four real ones, the
+ *   contraction over the panel's 16 columns in ascending order.  The right-hand sides are eliminated with each panel (L is not
+ *   kept); the backward pass runs over the same blocks of 16 columns.  Tiles, chunks and blocks depend on (nch*nfun, bw) alone.
+ * Guarantees:
+ *   (K1) results are bit-identical from run to run;
+ *   (K2) the results of matrix m depend on its own l, z, w, a, on the shared topology and on WB, GB, B_r, P_q alone -- not on the other
+ *        matrices, on nmat, nrhs or nproj, on the work slots, on the grouping below, or on the host versus _dev variant;
+ *   (K3) with every Im z = 0, no absorber, real coefficients and real B every imaginary part of X is +-0.0 exactly (on the matrix
+ *        cores too: every imaginary accumulator only ever sums products with a zero factor);
+ *   (K4) an entry given with ctr = 1 equals, bit for bit, the same entry with ctr = 0 and the transposed band.
+ * NOT promised: equality with bspatom_resolvent_coupled at bw <= 63 -- another kernel, another order of summation; both satisfy the
+ * same system to the same backward error.
+ * The host variant processes the matrices in groups under bspatom_resolvent's bound ("resolvent_stage_mb": the X of one group, one
+ * matrix at least); "resolvent_slots" applies.  Scratch per work slot, within the same bound (one slot at least): the band with the
+ * room of the fill and the nrhs vectors, N*(3bw + 1 + nrhs) complex with N = nch*nfun -- 2*nch*nfun*(3*nch*k - 2 + nrhs) doubles.
+ * The _dev variant as bspatom_resolvent_coupled_dev. */
+#define BSPATOM_COUPLED_WIDE_MAX_BAND 255
+int bspatom_resolvent_coupled_wide(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs, const double *WB,
+                                   const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop,
+                                   const double *GB, const double *a, int nrhs, const double *B, int nproj, const double *P, double *X,
+                                   double *R, int32_t *info);
+int bspatom_resolvent_coupled_wide_dev(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,
+                                       const double *WB_dev, const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc,
+                                       const int32_t *ctr, int nop, const double *GB_dev, const double *a, int nrhs,
+                                       const double *B_dev, int nproj, const double *P_dev, double *X_dev, double *R_dev, int32_t *info);
+
 /* WRITE_WF (Bsp_Atom.f90:118-146): u(r_i) = sum_j c_j B_j(r_i), r_i = ra + i*(rb-ra)/npts,
  * i = 0..npts.  Returns BSPATOM_ERR_BSPLVB where the reference STOPs. r[npts+1], u[npts+1]. */
 int bspatom_write_wf(bspatom_problem *p, const double *c, int npts, double *r, double *u);
