@@ -132,6 +132,18 @@ inline hipError_t allow_lds(K kernel, size_t bytes)
 {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
+// The work slots of a persistent grid: the workgroups of `kernel` (threads, bytes of dynamic LDS) the current device keeps resident
+// (the occupancy query x CUs, one each if a query fails), at most `items`.  A wrong estimate costs speed, never progress.
+template <class K>
+inline int persistent_slots(K kernel, int threads, size_t lds_bytes, int items, int *slots)
+{
+    int per_cu = 0;
+    const int cus = device_cus();
+    BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds_bytes));
+    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+    *slots = (int)(r < items ? r : items);
+    return BSP_OK;
+}
 
 // ---- launch-side state: the streams, events and small device blocks the launchers need besides the caller's buffers --------
 // One per problem handle (capi_internal.h), one local to every stage-level entry point and to bsp_dsygv_.  Every member is created at

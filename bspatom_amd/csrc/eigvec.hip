@@ -446,13 +446,8 @@ size_t invit_batch_slot_doubles(int n, int k) { return invit_work_doubles(n, k) 
 int invit_batch_slots(int k, int items, int *slots)
 {
     if (k - 1 > EB_MAX || k < 2 || items < 1) return BSP_ERR_ARG;
-    int per_cu = 0;
-    const int cus = device_cus();
-    if (k - 1 <= 8) BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, invit_batch_kernel<8>, 64, 0));
-    else BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, invit_batch_kernel<EB_MAX>, 64, 0));
-    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-    *slots = (int)(r < items ? r : items);
-    return BSP_OK;
+    if (k - 1 <= 8) return persistent_slots(invit_batch_kernel<8>, 64, 0, items, slots);
+    return persistent_slots(invit_batch_kernel<EB_MAX>, 64, 0, items, slots);
 }
 
 // items = nl * count inverse iterations on `slots` workgroups (d_work: slots * invit_batch_slot_doubles); see invit_batch_kernel

@@ -19,14 +19,15 @@
 // Beyond second order the amplitudes are PRODUCTS of resolvents with an operator in between, p^T G(z2) A2 G(z1) A1 c: the second
 // solve's right-hand side is the first one's solution.  resolvent_chain_kernel keeps such a chain on its wave: the same rs_factor
 // and rs_solve per stage, and between the stages rs_band_apply, y = (sum_o a_o G_o) x in fixed no-FMA arithmetic (C1 - C6 of
-// include/bspatom.h: a stage is bit for bit what resolvent_kernel gives for that right-hand side).
+// include/bspatom.h: a stage is bit for bit what resolvent_kernel gives for that right-hand side).  What this file shares with
+// resolvent_coupled.hip and resolvent_wide.hip -- the pivot rule, the reciprocal, the forward substitution -- is in resolvent_shared.h.
 #include "common.h"
 #include "wave_ops.h"
+#include "resolvent_shared.h"
 
 namespace bsp {
 namespace {
 constexpr int RS_BMAX = 15;                // half-bandwidth limit (k <= 16)
-constexpr int RS_PF = 8;                   // steps per prefetch block
 // (sums of wave_ops.h: wave_sum32 over lanes 0 .. 31 -- the callers' terms are zero beyond lane 2 b <= 30 --, wave_sum over all)
 // doubles of one slot's scratch, even (a slot starts on a 16-byte boundary)
 __host__ __device__ inline size_t rs_slot_doubles(int n, int k)
@@ -34,8 +35,6 @@ __host__ __device__ inline size_t rs_slot_doubles(int n, int k)
     const size_t b = (size_t)k - 1, piv = ((size_t)n + 1) / 2;
     return 2 * ((size_t)n * (2 * b + 1) + (size_t)n * b + (size_t)n) + piv + (piv & 1);
 }
-// a wave's own global stores are complete before the pass that reads them through other lanes (eigvec.hip: y_sync<true>)
-__device__ __forceinline__ void rs_sync() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // M(r, c); SB, HB upper bands [k][n] used symmetrically (eigvec.hip::pencil_entry), WB the absorber's FULL band [2k-1][n] with
 // WB[d + b][i] = W(i, i + d), both triangles as given, or null
@@ -60,7 +59,7 @@ __device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict_
                                          int *piv, const int lane)
 {
     constexpr int PF = RS_PF;
-    // scale of the zero-pivot perturbation, invit_body's with |M_jj| measured by cabs1
+    // scale of the zero-pivot perturbation (rs_pertol)
     double dmax = 0.0, dflo = 0.0;
     for (int j = lane; j < n; j += 64) {
         const double s = SB[j], h = HB[j], wv = WB ? WB[(size_t)b * n + j] : 0.0;
@@ -69,7 +68,7 @@ __device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict_
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) { dmax = fmax(dmax, __shfl_xor(dmax, off)); dflo = fmax(dflo, __shfl_xor(dflo, off)); }
-    const double pertol = 2.220446049250313e-16 * fmax(fmax(dmax, 2.220446049250313e-16 * dflo), 1e-280);
+    const double pertol = rs_pertol(dmax, dflo);
 
     // lane c (0 .. 2 b) holds column j + c of the rows j .. j + b: a[t] = M(j + t, j + c)
     double ar[BT + 1], ai[BT + 1];
@@ -113,13 +112,8 @@ __device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict_
                     ar[0] = ar[t]; ai[0] = ai[t]; ar[t] = t1; ai[t] = t2;
                 }
         }
-        double pr = read_lane(ar[0], 0), pi = read_lane(ai[0], 0);
-        if (fabs(pr) + fabs(pi) < pertol) { pr = (pr < 0.0) ? -pertol : pertol; pi = 0.0; ++nper; }
-        // 1 / pivot, once per column
-        const double sc = 1.0 / (fabs(pr) + fabs(pi));
-        const double qr = pr * sc, qi = pi * sc;
-        const double rd = 1.0 / (qr * qr + qi * qi);
-        const double rr = (qr * rd) * sc, ri = -((qi * rd) * sc);
+        const double2 rcp = rs_pivot_recip(read_lane(ar[0], 0), read_lane(ai[0], 0), pertol, nper);
+        const double rr = rcp.x, ri = rcp.y;
         double lmr = 0.0, lmi = 0.0;                                 // this lane's multiplier (row j + lane), for the store
 #pragma unroll
         for (int t = 1; t <= BT; ++t) {
@@ -157,99 +151,52 @@ __device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict_
 // (rs_sync); on return the solution is visible to every lane.
 __device__ __forceinline__ void rs_solve(int n, int b, const double2 *U, const double2 *Lm, const int *piv, double2 *y, const int lane)
 {
-    constexpr int PF = RS_PF;
-    // forward: y <- L^-1 P y; lane i holds y[j + i]
-    {
-        double wr = 0.0, wi = 0.0;
-        if (lane <= b && lane < n) { const double2 v = y[lane]; wr = v.x; wi = v.y; }
-        double2 lvn[PF]; int pvn[PF];
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            lvn[u] = (u < n && lane >= 1 && lane <= b) ? Lm[(size_t)u * b + lane - 1] : make_double2(0.0, 0.0);
-            pvn[u] = (u < n) ? piv[u] : 0;
-        }
-        // the entering entries: one per lane (lane u: step u's), a block ahead; above every index this pass has written
-        double2 yln = (lane < PF && lane + b + 1 < n) ? y[lane + b + 1] : make_double2(0.0, 0.0);
-        for (int j0 = 0; j0 < n; j0 += PF) {
-            double2 lv[PF]; int pvv[PF];
-            const double2 yl = yln;
-            yln = (lane < PF && j0 + PF + lane + b + 1 < n) ? y[j0 + PF + lane + b + 1] : make_double2(0.0, 0.0);
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int jn = j0 + u + PF;
-                lv[u] = lvn[u]; pvv[u] = pvn[u];
-                lvn[u] = (jn < n && lane >= 1 && lane <= b) ? Lm[(size_t)jn * b + lane - 1] : make_double2(0.0, 0.0);
-                pvn[u] = (jn < n) ? piv[jn] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int j = j0 + u;
-                if (j < n) {
-                    const int p = __builtin_amdgcn_readfirstlane(pvv[u]);
-                    if (p != j) {                                    // uniform: rows j and p change places (p - j <= b: inside the window)
-                        const double t0r = read_lane(wr, 0), t0i = read_lane(wi, 0);
-                        const double tqr = read_lane(wr, p - j), tqi = read_lane(wi, p - j);
-                        wr = lane == 0 ? tqr : (lane == p - j ? t0r : wr);
-                        wi = lane == 0 ? tqi : (lane == p - j ? t0i : wi);
-                    }
-                    const double yr = read_lane(wr, 0), yi = read_lane(wi, 0);
-                    const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;
-                    if (lane >= 1 && lane <= nrow) {
-                        wr -= lv[u].x * yr - lv[u].y * yi;
-                        wi -= lv[u].x * yi + lv[u].y * yr;
-                    }
-                    if (lane == 0) y[j] = make_double2(yr, yi);
-                    wr = dpp_mov<0x130>(wr); wi = dpp_mov<0x130>(wi);  // wave_shl:1 -- lane i takes lane i + 1
-                    const double er = read_lane(yl.x, u), ei = read_lane(yl.y, u);
-                    if (lane == b) { wr = er; wi = ei; }
-                }
-            }
-        }
-        rs_sync();
-    }
+    rs_forward(n, b, Lm, piv, y, lane);
     // backward: x_j = (y_j - sum_{c=1..2b} U[j][c] x_{j+c}) / pivot_j; lane c holds x[j + c] (zero beyond the matrix)
-    {
-        const int w = 2 * b + 1;
-        double wr = 0.0, wi = 0.0;
-        double2 uvn[PF], udn[PF];
+    constexpr int PF = RS_PF;
+    const int w = 2 * b + 1;
+    double wr = 0.0, wi = 0.0;
+    double2 uvn[PF], udn[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        const int j = n - 1 - u;
+        uvn[u] = (j >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)j * w + lane] : make_double2(0.0, 0.0);
+        udn[u] = (j >= 0) ? U[(size_t)j * w] : make_double2(0.0, 0.0);
+    }
+    double2 ybn = (lane < PF && n - 1 - lane >= 0) ? y[n - 1 - lane] : make_double2(0.0, 0.0);
+    for (int j0 = n - 1; j0 >= 0; j0 -= PF) {
+        double2 uv[PF], ru[PF];
+        const double2 yb = ybn;
+        ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
-            const int j = n - 1 - u;
-            uvn[u] = (j >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)j * w + lane] : make_double2(0.0, 0.0);
-            udn[u] = (j >= 0) ? U[(size_t)j * w] : make_double2(0.0, 0.0);
+            const int jn = j0 - u - PF;
+            uv[u] = uvn[u]; ru[u] = udn[u];
+            uvn[u] = (jn >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)jn * w + lane] : make_double2(0.0, 0.0);
+            udn[u] = (jn >= 0) ? U[(size_t)jn * w] : make_double2(0.0, 0.0);
         }
-        double2 ybn = (lane < PF && n - 1 - lane >= 0) ? y[n - 1 - lane] : make_double2(0.0, 0.0);
-        for (int j0 = n - 1; j0 >= 0; j0 -= PF) {
-            double2 uv[PF], ru[PF];
-            const double2 yb = ybn;
-            ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
 #pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int jn = j0 - u - PF;
-                uv[u] = uvn[u]; ru[u] = udn[u];
-                uvn[u] = (jn >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)jn * w + lane] : make_double2(0.0, 0.0);
-                udn[u] = (jn >= 0) ? U[(size_t)jn * w] : make_double2(0.0, 0.0);
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int j = j0 - u;
-                if (j >= 0) {
-                    double sr = 0.0, si = 0.0;
-                    if (lane >= 1 && lane <= 2 * b && j + lane < n) {
-                        sr = uv[u].x * wr - uv[u].y * wi;
-                        si = uv[u].x * wi + uv[u].y * wr;
-                    }
-                    sr = wave_sum32(sr); si = wave_sum32(si);
-                    const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
-                    const double xr = dr * ru[u].x - di * ru[u].y, xi = dr * ru[u].y + di * ru[u].x;
-                    if (lane == 0) y[j] = make_double2(xr, xi);
-                    wr = dpp_mov<0x138>(wr); wi = dpp_mov<0x138>(wi);  // wave_shr:1 -- lane i takes lane i - 1
-                    if (lane == 1) { wr = xr; wi = xi; }
+        for (int u = 0; u < PF; ++u) {
+            const int j = j0 - u;
+            if (j >= 0) {
+                double sr = 0.0, si = 0.0;
+                if (lane >= 1 && lane <= 2 * b && j + lane < n) {
+                    sr = uv[u].x * wr - uv[u].y * wi;
+                    // The fused form of x wi + y wr is written out.  Left to the compiler, which of the two products it fuses depends
+                    // on the code around this loop, not on this line, and the results of the call with it.  These are
+                    // the forms the kernel computes since it exists: the first step of a block differs from the other seven.
+                    si = (u == 0) ? __builtin_fma(uv[u].x, wi, uv[u].y * wr) : __builtin_fma(uv[u].y, wr, uv[u].x * wi);
                 }
+                sr = wave_sum32(sr); si = wave_sum32(si);
+                const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
+                const double xr = dr * ru[u].x - di * ru[u].y, xi = dr * ru[u].y + di * ru[u].x;
+                if (lane == 0) y[j] = make_double2(xr, xi);
+                wr = dpp_mov<0x138>(wr); wi = dpp_mov<0x138>(wi);  // wave_shr:1 -- lane i takes lane i - 1
+                if (lane == 1) { wr = xr; wi = xi; }
             }
         }
-        rs_sync();
     }
+    rs_sync();
 }
 
 // y <- A x, A = sum_o ac[o] G_o: the right-hand side of a chain's next stage (include/bspatom.h: bspatom_resolvent_chain).  GB: nop
@@ -423,13 +370,8 @@ size_t resolvent_chain_slot_doubles(int n, int k, int nrhs) { return rs_slot_dou
 int resolvent_chain_slots(int k, int nchain, int *slots)
 {
     if (k - 1 > RS_BMAX || k < 2 || nchain < 1) return BSP_ERR_ARG;
-    int per_cu = 0;
-    const int cus = device_cus();
-    if (k - 1 <= 8) BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_chain_kernel<8>, 64, 0));
-    else BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_chain_kernel<RS_BMAX>, 64, 0));
-    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-    *slots = (int)(r < nchain ? r : nchain);
-    return BSP_OK;
+    if (k - 1 <= 8) return persistent_slots(resolvent_chain_kernel<8>, 64, 0, nchain, slots);
+    return persistent_slots(resolvent_chain_kernel<RS_BMAX>, 64, 0, nchain, slots);
 }
 
 int launch_resolvent_chain(const ResolventChainArgs &a, int slots, hipStream_t st)
@@ -445,13 +387,8 @@ int launch_resolvent_chain(const ResolventChainArgs &a, int slots, hipStream_t s
 int resolvent_slots(int k, int nmat, int *slots)
 {
     if (k - 1 > RS_BMAX || k < 2 || nmat < 1) return BSP_ERR_ARG;
-    int per_cu = 0;
-    const int cus = device_cus();
-    if (k - 1 <= 8) BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_kernel<8>, 64, 0));
-    else BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_kernel<RS_BMAX>, 64, 0));
-    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-    *slots = (int)(r < nmat ? r : nmat);
-    return BSP_OK;
+    if (k - 1 <= 8) return persistent_slots(resolvent_kernel<8>, 64, 0, nmat, slots);
+    return persistent_slots(resolvent_kernel<RS_BMAX>, 64, 0, nmat, slots);
 }
 
 int launch_resolvent(const ResolventArgs &a, int slots, hipStream_t st)

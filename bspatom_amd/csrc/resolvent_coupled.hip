@@ -15,7 +15,7 @@
 // reciprocal and the multipliers, copies the pivot row out (U, and a broadcast copy in LDS) and puts row j where the pivot row
 // was; after a barrier all waves update the window, a wave per row, a lane per column, while the last two waves store the entering
 // row, which they requested two steps ahead; a second barrier ends the step.  U rows, L multipliers and pivot indices stream
-// to the slot's scratch; the solves run from there on wave 0 (forward: resolvent.hip's register window, bw + 1 lanes; backward: the
+// to the slot's scratch; the solves run from there on wave 0 (forward: rs_forward of resolvent_shared.h, resolvent.hip's register window on bw + 1 lanes; backward: the
 // last 2 bw unknowns in an LDS ring, two per lane), one right-hand side after the other.
 //
 // The matrix is first ASSEMBLED, by all threads, into the rows of U itself -- row r of the band, columns r - bw .. r + bw, lies where
@@ -24,12 +24,12 @@
 // entry, outside the dependent steps.
 //
 // Arithmetic, fixed (K1 - K4 of include/bspatom.h): pivot by |Re| + |Im|, ties to the smallest row; complex products in the plain
-// four-product form; one reciprocal per pivot, resolvent.hip's; every sum in an order that depends on the matrix alone (no atomics;
+// four-product form; one reciprocal per pivot (rs_pivot_recip, resolvent.hip's); every sum in an order that depends on the matrix alone (no atomics;
 // the workgroup's shape is a constant).  With Im z = 0, no absorber, real coefficients and real B every imaginary part is a sum of
 // products with a zero factor.
 #include "common.h"
 #include "wave_ops.h"
-#include "resolvent_entry.h"
+#include "resolvent_shared.h"
 #include "../../include/bspatom.h"
 
 namespace bsp {
@@ -38,8 +38,7 @@ constexpr int RC_BMAX = 63;                // BSPATOM_COUPLED_MAX_BAND: the pivo
 constexpr int RC_NT = 512;                 // threads of the workgroup
 constexpr int RC_NW = RC_NT / 64;
 constexpr int RC_PANEL = 1;                // columns per panel
-constexpr int RC_PF = 8;                   // steps per prefetch block of the solves' forward pass
-constexpr int RC_PFB = 4;                  // the same of the backward pass (two U entries per lane and step)
+constexpr int RC_PFB = 4;                  // steps per prefetch block of the solves' backward pass (two U entries per lane and step)
 static_assert(RC_PANEL == 1, "the step below is one column");
 static_assert(RC_BMAX == BSPATOM_COUPLED_MAX_BAND, "the limit the header states");
 
@@ -50,8 +49,6 @@ __host__ __device__ inline size_t rc_slot_doubles(int N, int bw)
 }
 // LDS of a workgroup: the window, the pivot row's copy (128), the multipliers (64), the reductions' words (16), complex each
 __host__ __device__ inline size_t rc_lds_bytes(int bw) { return ((size_t)(bw + 1) * (2 * bw + 1) + 128 + 64 + 16) * sizeof(double2); }
-
-__device__ __forceinline__ void rc_sync() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // The factorisation P M = L U of the assembled band in U.  U: [N][2bw+1] complex, on entry row r = M(r, r-bw .. r+bw), on return
 // row j = (1 / pivot, U(j, j+1 .. j+2bw)); Lm: [N][bw] multipliers; piv: [N] pivot rows.  Returns (in wave 0) the replaced pivots.
@@ -84,14 +81,9 @@ __device__ __forceinline__ int rc_factor(const int N, const int bw, const double
             const double mx = rc_wave_max(mag);
             const unsigned long long hit = __ballot(mag == mx);
             const int dp = __builtin_amdgcn_readfirstlane(hit ? __ffsll((long long)hit) - 1 : 0);
-            double pr = read_lane(v.x, dp), pi = read_lane(v.y, dp);
             const double v0r = read_lane(v.x, 0), v0i = read_lane(v.y, 0);
-            if (fabs(pr) + fabs(pi) < pertol) { pr = (pr < 0.0) ? -pertol : pertol; pi = 0.0; ++nper; }
-            // 1 / pivot, once per column (resolvent.hip's form)
-            const double sc = 1.0 / (fabs(pr) + fabs(pi));
-            const double qr = pr * sc, qi = pi * sc;
-            const double rd = 1.0 / (qr * qr + qi * qi);
-            const double rr = (qr * rd) * sc, ri = -((qi * rd) * sc);
+            const double2 rcp = rs_pivot_recip(read_lane(v.x, dp), read_lane(v.y, dp), pertol, nper);
+            const double rr = rcp.x, ri = rcp.y;
             // rows j and j + dp change places: the row now at j + t, t >= 1, is the old row j where t == dp
             const double xr = (lane == dp) ? v0r : v.x, xi = (lane == dp) ? v0i : v.y;
             const bool below = lane >= 1 && lane <= nrow;
@@ -152,110 +144,61 @@ __device__ __forceinline__ int rc_factor(const int N, const int bw, const double
 }
 
 // y <- U^-1 L^-1 P y in place on ONE wave (y: N complex in global memory, visible to the wave; xs: an LDS ring of 128 complex).
-// Forward: resolvent.hip::rs_solve's pass, lane i holds y[j + i], i <= bw <= 63.  Backward: x_j = (y_j - sum_{c=1..2bw} U[j][c]
+// Forward: rs_forward, the pass of resolvent.hip::rs_solve, lane i holds y[j + i], i <= bw <= 63.  Backward: x_j = (y_j - sum_{c=1..2bw} U[j][c]
 // x_{j+c}) / pivot_j, the 2 bw unknowns behind j in the ring, lane l takes c = l and c = 64 + l, then the wave's fixed tree.
 __device__ __forceinline__ void rc_solve(const int N, const int bw, const double2 *U, const double2 *Lm, const int *piv, double2 *y,
                                          double2 *xs, const int lane)
 {
-    {
-        constexpr int PF = RC_PF;
-        double wr = 0.0, wi = 0.0;
-        if (lane <= bw && lane < N) { const double2 v = y[lane]; wr = v.x; wi = v.y; }
-        double2 lvn[PF]; int pvn[PF];
+    rs_forward(N, bw, Lm, piv, y, lane);
+    constexpr int PF = RC_PFB;
+    const int W = 2 * bw + 1;
+    xs[lane] = make_double2(0.0, 0.0); xs[lane + 64] = make_double2(0.0, 0.0);
+    const bool in1 = lane >= 1 && lane <= 2 * bw, in2 = lane + 64 <= 2 * bw;
+    double2 u1n[PF], u2n[PF], udn[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        const int j = N - 1 - u;
+        u1n[u] = (j >= 0 && in1) ? U[(size_t)j * W + lane] : make_double2(0.0, 0.0);
+        u2n[u] = (j >= 0 && in2) ? U[(size_t)j * W + lane + 64] : make_double2(0.0, 0.0);
+        udn[u] = (j >= 0) ? U[(size_t)j * W] : make_double2(0.0, 0.0);
+    }
+    double2 ybn = (lane < PF && N - 1 - lane >= 0) ? y[N - 1 - lane] : make_double2(0.0, 0.0);
+    for (int j0 = N - 1; j0 >= 0; j0 -= PF) {
+        double2 u1[PF], u2[PF], ru[PF];
+        const double2 yb = ybn;
+        ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
-            lvn[u] = (u < N && lane >= 1 && lane <= bw) ? Lm[(size_t)u * bw + lane - 1] : make_double2(0.0, 0.0);
-            pvn[u] = (u < N) ? piv[u] : 0;
+            const int jn = j0 - u - PF;
+            u1[u] = u1n[u]; u2[u] = u2n[u]; ru[u] = udn[u];
+            u1n[u] = (jn >= 0 && in1) ? U[(size_t)jn * W + lane] : make_double2(0.0, 0.0);
+            u2n[u] = (jn >= 0 && in2) ? U[(size_t)jn * W + lane + 64] : make_double2(0.0, 0.0);
+            udn[u] = (jn >= 0) ? U[(size_t)jn * W] : make_double2(0.0, 0.0);
         }
-        double2 yln = (lane < PF && lane + bw + 1 < N) ? y[lane + bw + 1] : make_double2(0.0, 0.0);
-        for (int j0 = 0; j0 < N; j0 += PF) {
-            double2 lv[PF]; int pvv[PF];
-            const double2 yl = yln;
-            yln = (lane < PF && j0 + PF + lane + bw + 1 < N) ? y[j0 + PF + lane + bw + 1] : make_double2(0.0, 0.0);
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int jn = j0 + u + PF;
-                lv[u] = lvn[u]; pvv[u] = pvn[u];
-                lvn[u] = (jn < N && lane >= 1 && lane <= bw) ? Lm[(size_t)jn * bw + lane - 1] : make_double2(0.0, 0.0);
-                pvn[u] = (jn < N) ? piv[jn] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int j = j0 + u;
-                if (j < N) {
-                    const int p = __builtin_amdgcn_readfirstlane(pvv[u]);
-                    if (p != j) {                                    // uniform: rows j and p change places (p - j <= bw: inside the window)
-                        const double t0r = read_lane(wr, 0), t0i = read_lane(wi, 0);
-                        const double tqr = read_lane(wr, p - j), tqi = read_lane(wi, p - j);
-                        wr = lane == 0 ? tqr : (lane == p - j ? t0r : wr);
-                        wi = lane == 0 ? tqi : (lane == p - j ? t0i : wi);
-                    }
-                    const double yr = read_lane(wr, 0), yi = read_lane(wi, 0);
-                    const int nrow = (N - 1 - j < bw) ? (N - 1 - j) : bw;
-                    if (lane >= 1 && lane <= nrow) {
-                        wr -= lv[u].x * yr - lv[u].y * yi;
-                        wi -= lv[u].x * yi + lv[u].y * yr;
-                    }
-                    if (lane == 0) y[j] = make_double2(yr, yi);
-                    wr = dpp_mov<0x130>(wr); wi = dpp_mov<0x130>(wi);  // wave_shl:1 -- lane i takes lane i + 1
-                    const double er = read_lane(yl.x, u), ei = read_lane(yl.y, u);
-                    if (lane == bw) { wr = er; wi = ei; }
-                }
-            }
-        }
-        rc_sync();
-    }
-    {
-        constexpr int PF = RC_PFB;
-        const int W = 2 * bw + 1;
-        xs[lane] = make_double2(0.0, 0.0); xs[lane + 64] = make_double2(0.0, 0.0);
-        const bool in1 = lane >= 1 && lane <= 2 * bw, in2 = lane + 64 <= 2 * bw;
-        double2 u1n[PF], u2n[PF], udn[PF];
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
-            const int j = N - 1 - u;
-            u1n[u] = (j >= 0 && in1) ? U[(size_t)j * W + lane] : make_double2(0.0, 0.0);
-            u2n[u] = (j >= 0 && in2) ? U[(size_t)j * W + lane + 64] : make_double2(0.0, 0.0);
-            udn[u] = (j >= 0) ? U[(size_t)j * W] : make_double2(0.0, 0.0);
-        }
-        double2 ybn = (lane < PF && N - 1 - lane >= 0) ? y[N - 1 - lane] : make_double2(0.0, 0.0);
-        for (int j0 = N - 1; j0 >= 0; j0 -= PF) {
-            double2 u1[PF], u2[PF], ru[PF];
-            const double2 yb = ybn;
-            ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int jn = j0 - u - PF;
-                u1[u] = u1n[u]; u2[u] = u2n[u]; ru[u] = udn[u];
-                u1n[u] = (jn >= 0 && in1) ? U[(size_t)jn * W + lane] : make_double2(0.0, 0.0);
-                u2n[u] = (jn >= 0 && in2) ? U[(size_t)jn * W + lane + 64] : make_double2(0.0, 0.0);
-                udn[u] = (jn >= 0) ? U[(size_t)jn * W] : make_double2(0.0, 0.0);
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int j = j0 - u;
-                if (j >= 0) {
-                    double sr = 0.0, si = 0.0;
-                    if (in1 && j + lane < N) {
-                        const double2 x = xs[(j + lane) & 127];
-                        sr = u1[u].x * x.x - u1[u].y * x.y;
-                        si = u1[u].x * x.y + u1[u].y * x.x;
-                    }
-                    if (in2 && j + lane + 64 < N) {
-                        const double2 x = xs[(j + lane + 64) & 127];
-                        sr += u2[u].x * x.x - u2[u].y * x.y;
-                        si += u2[u].x * x.y + u2[u].y * x.x;
-                    }
-                    sr = wave_sum(sr); si = wave_sum(si);
-                    const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
-                    const double2 x = make_double2(dr * ru[u].x - di * ru[u].y, dr * ru[u].y + di * ru[u].x);
-                    if (lane == 0) { xs[j & 127] = x; y[j] = x; }
-                    __builtin_amdgcn_wave_barrier();
+            const int j = j0 - u;
+            if (j >= 0) {
+                double sr = 0.0, si = 0.0;
+                if (in1 && j + lane < N) {
+                    const double2 x = xs[(j + lane) & 127];
+                    sr = u1[u].x * x.x - u1[u].y * x.y;
+                    si = u1[u].x * x.y + u1[u].y * x.x;
                 }
+                if (in2 && j + lane + 64 < N) {
+                    const double2 x = xs[(j + lane + 64) & 127];
+                    sr += u2[u].x * x.x - u2[u].y * x.y;
+                    si += u2[u].x * x.y + u2[u].y * x.x;
+                }
+                sr = wave_sum(sr); si = wave_sum(si);
+                const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
+                const double2 x = make_double2(dr * ru[u].x - di * ru[u].y, dr * ru[u].y + di * ru[u].x);
+                if (lane == 0) { xs[j & 127] = x; y[j] = x; }
+                __builtin_amdgcn_wave_barrier();
             }
         }
-        rc_sync();
     }
+    rs_sync();
 }
 }  // namespace
 
@@ -271,7 +214,7 @@ __global__ __launch_bounds__(RC_NT) void resolvent_coupled_kernel(const Resolven
     double2 *U = reinterpret_cast<double2 *>(work), *Lm = U + (size_t)N * W, *y = Lm + (size_t)N * bw;
     int *piv = reinterpret_cast<int *>(y + N);
     for (int it = blockIdx.x; it < a.nmat; it += gridDim.x) {
-        // the band, row by row, into U's rows; the scale of the zero-pivot perturbation from its diagonal (resolvent.hip's rule)
+        // the band, row by row, into U's rows; the scale of the zero-pivot perturbation from its diagonal (rs_pertol)
         double dmax = 0.0, dflo = 0.0;
         for (int r = wv; r < N; r += RC_NW)
 #pragma unroll
@@ -290,52 +233,17 @@ __global__ __launch_bounds__(RC_NT) void resolvent_coupled_kernel(const Resolven
         __syncthreads();                                             // the band is in memory (vmcnt(0) and the barrier), red is written
 #pragma unroll
         for (int q = 0; q < RC_NW; ++q) { dmax = fmax(dmax, red[q].x); dflo = fmax(dflo, red[q].y); }
-        const double pertol = 2.220446049250313e-16 * fmax(fmax(dmax, 2.220446049250313e-16 * dflo), 1e-280);
+        const double pertol = rs_pertol(dmax, dflo);
         const int nper = rc_factor(N, bw, pertol, U, Lm, piv, win, prow, mult, tid);
         if (tid == 0) a.info[it] = nper;
         for (int r = 0; r < a.nrhs; ++r) {
-            // B_r, channel-major, into the ordering of the matrix (read and written as doubles: the ABI promises no more alignment)
-            const double *B = a.B + (size_t)2 * r * N;
-            for (int e = tid; e < N; e += RC_NT) {
-                const int c = e / n, i = e - c * n;
-                y[i * nch + c] = make_double2(B[2 * e], B[2 * e + 1]);
-            }
+            rc_load_rhs<RC_NT>(n, nch, a.B + (size_t)2 * r * N, y, tid);
             __syncthreads();                                         // y, and with the first right-hand side U, L, piv, are in memory
             if (wv == 0) rc_solve(N, bw, U, Lm, piv, y, prow, lane);
             __syncthreads();
             const size_t mr = (size_t)it * a.nrhs + r;
-            if (a.X) {
-                double *X = a.X + 2 * mr * N;
-                for (int e = tid; e < N; e += RC_NT) {
-                    const int c = e / n, i = e - c * n;
-                    const double2 v = y[i * nch + c];
-                    X[2 * e] = v.x; X[2 * e + 1] = v.y;
-                }
-            }
-            if (a.R)
-                for (int q = 0; q < a.nproj; ++q) {
-                    // bilinear, no conjugate, over all channels: thread-strided partial sums in the caller's order, each wave's
-                    // fixed tree, then the waves in ascending order
-                    const double *P = a.P + (size_t)2 * q * N;
-                    double sr = 0.0, si = 0.0;
-                    for (int e = tid; e < N; e += RC_NT) {
-                        const int c = e / n, i = e - c * n;
-                        const double2 xv = y[i * nch + c];
-                        const double pr = P[2 * e], pi = P[2 * e + 1];
-                        sr += pr * xv.x - pi * xv.y;
-                        si += pr * xv.y + pi * xv.x;
-                    }
-                    sr = wave_sum(sr); si = wave_sum(si);
-                    if (lane == 0) red[wv] = make_double2(sr, si);
-                    lds_barrier();
-                    if (tid == 0) {
-                        double tr = red[0].x, ti = red[0].y;
-#pragma unroll
-                        for (int u = 1; u < RC_NW; ++u) { tr += red[u].x; ti += red[u].y; }
-                        a.R[2 * (mr * a.nproj + q)] = tr; a.R[2 * (mr * a.nproj + q) + 1] = ti;
-                    }
-                    lds_barrier();
-                }
+            if (a.X) rc_store_x<RC_NT>(n, nch, y, a.X + 2 * mr * N, tid);
+            if (a.R) rc_project<RC_NT>(n, nch, a.nproj, a.P, y, a.R + 2 * mr * a.nproj, red, tid);
             __syncthreads();                                         // every load of y is back before the next right-hand side overwrites it
         }
     }
@@ -359,12 +267,7 @@ int resolvent_coupled_slots(int k, int nch, int nmat, int *slots)
     if (k < 2 || nch < 1 || nmat < 1 || (long)nch * k - 1 > RC_BMAX) return BSP_ERR_ARG;
     int rc = rc_allow_lds();
     if (rc) return rc;
-    int per_cu = 0;
-    const int cus = device_cus();
-    BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_coupled_kernel, RC_NT, rc_lds_bytes(nch * k - 1)));
-    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-    *slots = (int)(r < nmat ? r : nmat);
-    return BSP_OK;
+    return persistent_slots(resolvent_coupled_kernel, RC_NT, rc_lds_bytes(nch * k - 1), nmat, slots);
 }
 
 int launch_resolvent_coupled(const ResolventCoupledArgs &a, int slots, hipStream_t st)

@@ -11,7 +11,7 @@
 //             read).  Factored there column by column: the pivot of a column is the largest |Re| + |Im| over ALL of its at most
 //             bw + 1 <= 256 candidates, ties to the smallest row -- waves 0 .. 3 take 64 candidates each (the DPP maximum and a
 //             ballot, resolvent_coupled.hip's), leave (maximum, row, value) in LDS, and every thread combines the four in ascending
-//             order; one reciprocal per pivot (resolvent.hip's form); the rows change places across the WHOLE panel, so that
+//             order; one reciprocal per pivot (rs_pivot_recip, resolvent.hip's); the rows change places across the WHOLE panel, so that
 //             P A = L U holds for the panel as a block; a thread per row scales its multiplier and updates its row of the panel.
 //   right     the interchanges of the panel as ONE gather per column (a thread per column of the at most 2 bw to the right):
 //             U12 = L11^-1 A12 on plain FMAs in registers, written back and staged in LDS; then A22 -= L21 U12 on
@@ -27,7 +27,7 @@
 // real coefficients and real B every imaginary accumulator, on the matrix cores too, sums products with a zero factor.
 #include "common.h"
 #include "wave_ops.h"
-#include "resolvent_entry.h"
+#include "resolvent_shared.h"
 #include "../../include/bspatom.h"
 
 namespace bsp {
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(RW_NT) void resolvent_wide_kernel(const ResolventCo
     // M(i, c), c - 2 bw <= i <= c + bw
     auto at = [&](int i, int c) -> double2 * { return AB + (size_t)c * LD + (i - c + 2 * bw); };
     for (int it = blockIdx.x; it < a.nmat; it += gridDim.x) {
-        // the band, column by column; the scale of the zero-pivot perturbation from its diagonal (resolvent.hip's rule)
+        // the band, column by column; the scale of the zero-pivot perturbation from its diagonal (rs_pertol)
         double dmax = 0.0, dflo = 0.0;
         for (int c = wv; c < N; c += RW_NW)
             for (int o = lane; o < LD; o += 64) {
@@ -82,21 +82,15 @@ __global__ __launch_bounds__(RW_NT) void resolvent_wide_kernel(const ResolventCo
                     if (o == 2 * bw) { dmax = fmax(dmax, fabs(re) + fabs(im)); dflo = fmax(dflo, fl); }
                 }
             }
-        // B_r, channel-major, into the ordering of the matrix (read and written as doubles: the ABI promises no more alignment)
-        for (int r = 0; r < a.nrhs; ++r) {
-            const double *B = a.B + (size_t)2 * r * N;
-            for (int e = tid; e < N; e += RW_NT) {
-                const int c = e / n, i = e - c * n;
-                y[(size_t)r * N + i * nch + c] = make_double2(B[2 * e], B[2 * e + 1]);
-            }
-        }
+        // the right-hand sides, into the ordering of the matrix
+        for (int r = 0; r < a.nrhs; ++r) rc_load_rhs<RW_NT>(n, nch, a.B + (size_t)2 * r * N, y + (size_t)r * N, tid);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) { dmax = fmax(dmax, __shfl_xor(dmax, off)); dflo = fmax(dflo, __shfl_xor(dflo, off)); }
         if (lane == 0) pred[wv] = make_double2(dmax, dflo);
         __syncthreads();                                             // the band and the vectors are in memory, pred is written
 #pragma unroll
         for (int q = 0; q < RW_NW; ++q) { dmax = fmax(dmax, pred[q].x); dflo = fmax(dflo, pred[q].y); }
-        const double pertol = 2.220446049250313e-16 * fmax(fmax(dmax, 2.220446049250313e-16 * dflo), 1e-280);
+        const double pertol = rs_pertol(dmax, dflo);
         int nper = 0;
         for (int j0 = 0; j0 < N; j0 += NB) {
             const int nb = (N - j0 < NB) ? N - j0 : NB;
@@ -139,12 +133,8 @@ __global__ __launch_bounds__(RW_NT) void resolvent_wide_kernel(const ResolventCo
                     const double m = red[4 * w];
                     if (m > best) { best = m; p = (int)red[4 * w + 1]; pr = red[4 * w + 2]; pi = red[4 * w + 3]; }
                 }
-                if (fabs(pr) + fabs(pi) < pertol) { pr = (pr < 0.0) ? -pertol : pertol; pi = 0.0; ++nper; }
-                // 1 / pivot, once per column (resolvent.hip's form)
-                const double sc = 1.0 / (fabs(pr) + fabs(pi));
-                const double qr = pr * sc, qi = pi * sc;
-                const double rd = 1.0 / (qr * qr + qi * qi);
-                const double rr = (qr * rd) * sc, ri = -((qi * rd) * sc);
+                const double2 rcp = rs_pivot_recip(pr, pi, pertol, nper);
+                const double rr = rcp.x, ri = rcp.y;
                 // rows t and t + p change places in every column of the panel, L's among them
                 if (p != 0 && tid < NB) {
                     const int e0 = tid * PS + t, e1 = e0 + p;
@@ -376,38 +366,8 @@ __global__ __launch_bounds__(RW_NT) void resolvent_wide_kernel(const ResolventCo
         for (int r = 0; r < a.nrhs; ++r) {
             const double2 *yy = y + (size_t)r * N;
             const size_t mr = (size_t)it * a.nrhs + r;
-            if (a.X) {
-                double *X = a.X + 2 * mr * N;
-                for (int e = tid; e < N; e += RW_NT) {
-                    const int c = e / n, i = e - c * n;
-                    const double2 v = yy[i * nch + c];
-                    X[2 * e] = v.x; X[2 * e + 1] = v.y;
-                }
-            }
-            if (a.R)
-                for (int q = 0; q < a.nproj; ++q) {
-                    // bilinear, no conjugate, over all channels: thread-strided partial sums in the caller's order, each wave's
-                    // fixed tree, then the waves in ascending order
-                    const double *P = a.P + (size_t)2 * q * N;
-                    double sr = 0.0, si = 0.0;
-                    for (int e = tid; e < N; e += RW_NT) {
-                        const int c = e / n, i = e - c * n;
-                        const double2 xv = yy[i * nch + c];
-                        const double pr = P[2 * e], pi = P[2 * e + 1];
-                        sr += pr * xv.x - pi * xv.y;
-                        si += pr * xv.y + pi * xv.x;
-                    }
-                    sr = wave_sum(sr); si = wave_sum(si);
-                    if (lane == 0) pred[wv] = make_double2(sr, si);
-                    lds_barrier();
-                    if (tid == 0) {
-                        double tr = pred[0].x, ti = pred[0].y;
-#pragma unroll
-                        for (int u = 1; u < RW_NW; ++u) { tr += pred[u].x; ti += pred[u].y; }
-                        a.R[2 * (mr * a.nproj + q)] = tr; a.R[2 * (mr * a.nproj + q) + 1] = ti;
-                    }
-                    lds_barrier();
-                }
+            if (a.X) rc_store_x<RW_NT>(n, nch, yy, a.X + 2 * mr * N, tid);
+            if (a.R) rc_project<RW_NT>(n, nch, a.nproj, a.P, yy, a.R + 2 * mr * a.nproj, pred, tid);
         }
         __syncthreads();                                             // every load of the band and of y is back before the next matrix
     }
@@ -431,12 +391,7 @@ int resolvent_wide_slots(int k, int nch, int nmat, int *slots)
     if (k < 2 || nch < 1 || nmat < 1 || (long)nch * k - 1 > RW_BMAX) return BSP_ERR_ARG;
     int rc = rw_allow_lds();
     if (rc) return rc;
-    int per_cu = 0;
-    const int cus = device_cus();
-    BSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resolvent_wide_kernel, RW_NT, RW_LDS_BYTES));
-    const long r = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-    *slots = (int)(r < nmat ? r : nmat);
-    return BSP_OK;
+    return persistent_slots(resolvent_wide_kernel, RW_NT, RW_LDS_BYTES, nmat, slots);
 }
 
 int launch_resolvent_wide(const ResolventCoupledArgs &a, int slots, hipStream_t st)
