@@ -39,6 +39,9 @@ EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup
            "bspatom_release_scratch", "bspatom_run_token", "bspatom_comm_create", "bspatom_comm_allgather", "bspatom_comm_collectives", "bspatom_comm_destroy",
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
 
+# what include/bspatom_tdse_spline.h, the part of the header for the spline-basis TDSE, declares (EXPORTS is include/bspatom.h's own text)
+SPLINE_EXPORTS = ["bspatom_tdse_spline", "bspatom_tdse_spline_dev"]
+
 _lib = None
 
 
@@ -96,6 +99,8 @@ def lib():
                             ("adaptive", t24 + [i32, dbl, i32, i32, vp, i32, vp, vp, vp])):
             getattr(L, "bspatom_tdse_" + name).argtypes = list(types)
             getattr(L, "bspatom_tdse_" + name + "_dev").argtypes = list(types)
+        L.bspatom_tdse_spline.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, dbl, vp, vp, i32, vp, i32, i32, vp, vp, vp]
+        L.bspatom_tdse_spline_dev.argtypes = list(L.bspatom_tdse_spline.argtypes)
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -843,6 +848,73 @@ class Problem:
                                            *self._tdse_static_args(scheme, si, sf, skind, W_ptr), int(nfield), _p(fidx) if len(ci) else None),
              "bspatom_tdse_fields_dev")
         return err
+
+    @staticmethod
+    def _spline_system(l, w, couplings, coef, nscan, nsteps, nop):
+        """(nch, l int32 (nch,), w int32 (nch,) or None, cr, cc, ctr int32 (ncoup,) or None, coef complex128 (nsteps, nscan, ncoup, nop)
+        or None, broadcast from (nsteps, ncoup, nop) -- every scan the same pulse), contiguous"""
+        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
+        w = None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), l.shape))
+        ncoup = 0 if couplings is None else len(couplings)
+        cr = cc = ctr = None
+        if ncoup == 0:
+            coef = None
+        else:
+            assert nop >= 1, "couplings need operator bands G"
+            top = np.asarray(couplings, dtype=np.int32).reshape(ncoup, 3)
+            cr, cc, ctr = (np.ascontiguousarray(top[:, q]) for q in range(3))
+            if nsteps == 0:
+                coef = None
+            else:
+                assert coef is not None, "coef (nsteps, nscan, ncoup, nop) is needed with couplings"
+                coef = np.asarray(coef, dtype=np.complex128)
+                if coef.ndim == 3:
+                    coef = coef[:, None]
+                assert coef.ndim == 4 and coef.shape[0] == nsteps, (coef.shape, nsteps)
+                coef = np.ascontiguousarray(np.broadcast_to(coef, (nsteps, nscan, ncoup, nop)))
+        return l.size, l, w, cr, cc, ctr, coef
+
+    def tdse_spline(self, l, c0, dt, nsteps, couplings=None, G=None, coef=None, W=None, w=None, P=None, obs_every=0, snap_every=0):
+        """nsteps Crank-Nicolson steps dt of i S dc/dt = (sum_c (H_l[c] - i W_w[c]) + V(t)) c in the B-spline basis itself
+        (bspatom_tdse_spline): the whole continuum of the box, any absorber, any coupling, one banded LU per step and packet, the
+        matrix resolvent_coupled's at z = 2i/dt.  l, w: (nch,); couplings [(cr, cc, ctr)], G, W as in resolvent_coupled; coef: COMPLEX
+        (nsteps, nscan, ncoup, nop), the coefficient of entry p and operator o during step n of scan q -- the field at the step's
+        MIDPOINT times the angular factor (host.spline_coefficients) --, broadcast from (nsteps, ncoup, nop).  c0: complex (nscan, nch,
+        nfun) or (nch, nfun).  Returns (c, info), then obs if obs_every >= 1 -- (nobs, nscan, nch + 2 nproj): N_ch = Re c_ch^H S c_ch
+        per channel, then Re, Im of sum P_r (S c) for the projections P (nproj, nch, nfun), for the steps 0, obs_every, .. < nsteps
+        and the final state (tdse_nobs) --, then snaps (nsteps // snap_every, nscan, nch, nfun) if snap_every >= 1.  info (nscan,):
+        replaced pivots, 0.  nsteps = 0 with obs_every >= 1 only measures.  nch * k - 1 <= 63, else BspAtomError(-5)."""
+        n = self.nfun
+        W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
+        G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
+        nabs, nop = 0 if W is None else W.shape[0], 0 if G is None else G.shape[0]
+        c = np.array(c0, dtype=np.complex128, order="C")
+        one = c.ndim == 2
+        nch = np.asarray(l).size
+        c = np.ascontiguousarray(c.reshape(-1, nch, n))
+        nscan = c.shape[0]
+        nch, l, w, cr, cc, ctr, coef = self._spline_system(l, w, couplings, coef, nscan, nsteps, nop)
+        P = None if P is None or obs_every < 1 else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, nch, n))
+        nproj = 0 if P is None else P.shape[0]
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, n), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj)) if obs_every > 0 else None
+        info = np.zeros(nscan, dtype=np.int32)
+        _chk(lib().bspatom_tdse_spline(self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), 0 if cr is None else cr.size, _p(cr), _p(cc), _p(ctr),
+                                       nop, _p(G), nsteps, float(dt), _p(coef), _p(c), snap_every, _p(snaps), obs_every, nproj, _p(P),
+                                       _p(obs), _p(info)), "bspatom_tdse_spline")
+        return (c[0] if one else c, info) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+
+    def tdse_spline_dev(self, l, nscan, nsteps, dt, c_ptr, couplings=None, nop=0, G_ptr=None, coef_ptr=None, nabs=0, W_ptr=None, w=None,
+                        nproj=0, P_ptr=None, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None):
+        """tdse_spline with the packets (nscan * nch * nfun complex at c_ptr, advanced in place), G, W, the coefficient table (nsteps *
+        nscan * ncoup * nop complex), P, the rows and the snapshots in device memory of this problem's device, e.g. torch tensors'
+        data_ptr(); l, w and couplings are host values.  Returns info (nscan,) when the result is there."""
+        nch, l, w, cr, cc, ctr, _ = self._spline_system(l, w, couplings, None, nscan, 0, nop)
+        info = np.zeros(nscan, dtype=np.int32)
+        _chk(lib().bspatom_tdse_spline_dev(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), 0 if cr is None else cr.size, _p(cr),
+                                           _p(cc), _p(ctr), nop, _ptr(G_ptr), nsteps, float(dt), _ptr(coef_ptr), _ptr(c_ptr), snap_every,
+                                           _ptr(snap_ptr), obs_every, nproj, _ptr(P_ptr), _ptr(obs_ptr), _p(info)), "bspatom_tdse_spline_dev")
+        return info
 
     def early_vector_state(self):
         """0: the last solve computed no early vector; 1: computed and kept; -1: computed, failed its check, dropped (include/bspatom.h)."""

@@ -116,6 +116,7 @@ const OptName OPT_TABLE[] = {
     {"wf_stage_mb", "BSP_WF_STAGE_MB", &Options::wf_stage_mb},
     {"tdse_stage_mb", "BSP_TDSE_STAGE_MB", &Options::tdse_stage_mb},
     {"tdse_adapt_group", "BSP_TDSE_ADAPT_GROUP", &Options::tdse_adapt_group},
+    {"tdse_spline_group", "BSP_TDSE_SPLINE_GROUP", &Options::tdse_spline_group},
 };
 }  // namespace
 

@@ -5,14 +5,19 @@
 //   bspatom_resolvent_chain / _dev: chains of such solves with an operator in between, one launch for the whole batch.
 //   bspatom_resolvent_coupled / _dev: several channels coupled to all orders in one banded LU (resolvent_coupled.hip).
 //   bspatom_resolvent_coupled_wide / _dev: the same call on the blocked LU for wide bands (resolvent_wide.hip).
-// All eight run through resolvent_call: a front function per flavour screens what is particular to it, describes the call by
+//   bspatom_tdse_spline / _dev: Crank-Nicolson steps on the coupled LU (tdse_spline.hip); a call path of its own below (every packet
+//     has its own right-hand side and the steps follow each other), the screening and the scratch rules of the coupled call.
+// The eight resolvent entry points run through resolvent_call: a front function per flavour screens what is particular to it, describes the call by
 // counts per ITEM (a matrix, a chain, a coupled matrix) and hands over its slot query and its launcher.
 #include <algorithm>
+#include <cmath>
 #include "capi_internal.h"
 
 using namespace bsp;
 
 static constexpr size_t RESOLVENT_STAGE_BYTES = (size_t)2048 << 20;
+static constexpr size_t SPLINE_STAGE_BYTES = (size_t)256 << 20;    // tdse_stage_mb's default (capi_tdse.hip)
+static constexpr int SPLINE_GROUP = 64;                            // steps per launch (tdse_spline_group)
 
 // A call as the shared path sees it: the caller's arrays and how much of each an item takes (single | chain | coupled)
 struct ResolventCall {
@@ -206,6 +211,136 @@ static int resolvent_coupled_impl(bspatom_problem *p, int nmat, int nch, const i
                               a.cr = d.cr; a.cc = d.cc; a.ctr = d.ctr; a.GB = d.GB; a.acoef = d.acoef;
                               return wide ? launch_resolvent_wide(a, slots, st) : launch_resolvent_coupled(a, slots, st);
                           });
+}
+
+// bspatom_tdse_spline / _dev: nsteps Crank-Nicolson steps of nscan packets, each step the coupled matrix at z = 2i / dt with the
+// step's coefficients.  The steps go out in launches of at most tdse_spline_group; the host variant stages the coefficients, the
+// snapshots and the rows by groups of whole steps under tdse_stage_mb (one step at least); neither changes what a step computes.
+static int tdse_spline_impl(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w, int ncoup,
+                            const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop, const double *GB, int nsteps, double dt,
+                            const double *coef, double *c, int snap_every, double *snap, int obs_every, int nproj, const double *P,
+                            double *obs, int32_t *info, bool dev)
+{
+    if (!p || !l || !c || !info || nscan < 1 || nch < 1 || nsteps < 0 || nabs < 0 || nproj < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
+    if (!std::isfinite(dt) || !(dt > 0.0)) return BSP_ERR_ARG;
+    if (ncoup < 0 || (ncoup > 0 && (nop < 1 || !cr || !cc || !ctr || !GB || (nsteps > 0 && !coef)))) return BSP_ERR_ARG;
+    if (snap_every < 0 || (snap && snap_every == 0)) return BSP_ERR_ARG;
+    if (obs_every < 0 || (obs_every == 0) != (obs == nullptr) || (obs && nproj > 0 && !P)) return BSP_ERR_ARG;
+    for (int ch = 0; ch < nch; ++ch) {
+        if (p->band_nl < 1 || l[ch] < p->band_l0 || l[ch] >= p->band_l0 + p->band_nl) return BSP_ERR_ARG;
+        if (w && (w[ch] < -1 || w[ch] >= nabs)) return BSP_ERR_ARG;
+    }
+    for (int q = 0; q < ncoup; ++q)
+        if (cr[q] < 0 || cr[q] >= nch || cc[q] < 0 || cc[q] >= nch || ctr[q] < 0 || ctr[q] > 1) return BSP_ERR_ARG;
+    const int n = p->hs.nfun, k = p->hs.k;
+    if ((long long)nch * k - 1 > resolvent_coupled_max_band()) {
+        fprintf(stderr, "bspatom_tdse_spline: half-width nch*k - 1 = %lld exceeds BSPATOM_COUPLED_MAX_BAND = %d\n", (long long)nch * k - 1,
+                resolvent_coupled_max_band());
+        return BSP_ERR_UNSUPPORTED;
+    }
+    if ((long long)nch * n > 0x3fffffffLL || (long long)nsteps * nscan > 0x3fffffffLL) return BSP_ERR_ARG;
+    const bool snapping = snap && snap_every > 0, observing = obs != nullptr;
+    if (!observing) nproj = 0;
+    const size_t N = (size_t)nch * n, wband = (size_t)(2 * k - 1) * n, RW = (size_t)nch + 2 * nproj;
+    const size_t coef_step = (size_t)2 * nscan * ncoup * (ncoup > 0 ? nop : 0), snap_one = 2 * N * nscan, row_one = RW * nscan;   // doubles
+    BSP_HIP(hipSetDevice(p->device));
+    int rc, slots = 0;
+    if ((rc = tdse_spline_slots(k, nch, nscan, &slots))) return rc;
+    if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, nscan);
+    const size_t slot_doubles = resolvent_coupled_slot_doubles(n, k, nch);
+    const size_t rstage = opts().resolvent_stage_mb > 0 ? (size_t)opts().resolvent_stage_mb << 20 : RESOLVENT_STAGE_BYTES;
+    slots = (int)std::max<size_t>(1, std::min<size_t>(slots, rstage / (slot_doubles * sizeof(double))));
+    const int group = opts().tdse_spline_group > 0 ? opts().tdse_spline_group : SPLINE_GROUP;
+    // the host variant's staging groups: whole steps, a step counted with a snapshot and a row of its own (an upper bound)
+    int sgroup = std::max(nsteps, 1);
+    if (!dev) {
+        const size_t tstage = opts().tdse_stage_mb > 0 ? (size_t)opts().tdse_stage_mb << 20 : SPLINE_STAGE_BYTES;
+        const size_t per_step = (coef_step + (snapping ? snap_one : 0) + (observing ? row_one : 0)) * sizeof(double);
+        sgroup = (int)std::max<size_t>(1, std::min<size_t>(sgroup, tstage / std::max<size_t>(per_step, 1)));
+    }
+    const size_t gsnaps = snapping ? (size_t)sgroup / snap_every + 1 : 0, grows = observing ? (size_t)(sgroup - 1) / obs_every + 2 : 0;
+    std::vector<int> chan(nch), wsel(nch, nabs > 0 && !w ? 0 : -1);
+    std::vector<double> z(2 * (size_t)nch);
+    const double zi = 2.0 / dt, g = 4.0 / dt;
+    for (int ch = 0; ch < nch; ++ch) { chan[ch] = l[ch] - p->band_l0; if (w) wsel[ch] = w[ch]; z[2 * ch] = 0.0; z[2 * ch + 1] = zi; }
+    const bool ops = ncoup > 0;
+    DevArray<double> work, dz, dcoef, dWB, dGB, dc, dP, dsnap, dobs;
+    DevArray<int> dchan, dw, dinfo, dcr, dcc, dctr;
+    if ((rc = work.alloc((size_t)slots * slot_doubles)) || (rc = dz.put(z.data(), z.size())) || (rc = dchan.put(chan.data(), nch)) ||
+        (rc = dw.put(wsel.data(), nch)) || (rc = dinfo.alloc(nscan)) ||
+        (ops && ((rc = dcr.put(cr, ncoup)) || (rc = dcc.put(cc, ncoup)) || (rc = dctr.put(ctr, ncoup))))) return rc;
+    if (!dev) {
+        if ((nabs > 0 && (rc = dWB.put(WB, (size_t)nabs * wband))) || (ops && (rc = dGB.put(GB, (size_t)nop * wband))) ||
+            (rc = dc.put(c, 2 * N * nscan)) || (nproj > 0 && (rc = dP.put(P, 2 * N * nproj))) ||
+            (ops && nsteps > 0 && (rc = dcoef.alloc((size_t)sgroup * coef_step))) || (snapping && (rc = dsnap.alloc(gsnaps * snap_one))) ||
+            (observing && (rc = dobs.alloc(grows * row_one)))) return rc;
+    }
+    BSP_HIP(hipMemsetAsync(dinfo.p, 0, (size_t)nscan * sizeof(int), p->st));
+    TdseSplineArgs a = {};
+    ResolventCoupledArgs &m = a.m;
+    m.n = n; m.k = k; m.nch = nch; m.ncoup = ncoup; m.nop = ops ? nop : 0; m.nproj = nproj;
+    m.SB = p->d_SB; m.HB = p->d_HB; m.chan = dchan.p; m.z = dz.p; m.w = dw.p;
+    m.WB = nabs > 0 ? (dev ? WB : dWB.p) : nullptr;
+    m.GB = ops ? (dev ? GB : dGB.p) : nullptr;
+    m.cr = dcr.p; m.cc = dcc.p; m.ctr = dctr.p;
+    m.P = nproj > 0 ? (dev ? P : dP.p) : nullptr;
+    m.info = dinfo.p; m.work = work.p;
+    a.nscan = nscan; a.g = g; a.c = dev ? c : dc.p;
+    a.snap_every = snapping ? snap_every : 0; a.obs_every = observing ? obs_every : 0;
+    const int nobs = observing ? (nsteps == 0 ? 1 : (nsteps - 1) / obs_every + 2) : 0;
+    rc = BSP_OK;
+    for (int n0 = 0; !rc && n0 < nsteps; n0 += sgroup) {
+        const int n1 = std::min(nsteps, n0 + sgroup);
+        // the group's snapshots s0 .. s1-1 and its rows j0 .. j1-1 (the observed steps j obs_every of n0 .. n1-1)
+        const int s0 = snapping ? n0 / snap_every : 0, s1 = snapping ? n1 / snap_every : 0;
+        const int j0 = observing ? (n0 + obs_every - 1) / obs_every : 0, j1 = observing ? (n1 + obs_every - 1) / obs_every : 0;
+        const double *gcoef = nullptr;
+        if (ops) {
+            if (dev) gcoef = coef + (size_t)n0 * coef_step;
+            else {
+                rc = HIP_RC(hipMemcpyAsync(dcoef.p, coef + (size_t)n0 * coef_step, (size_t)(n1 - n0) * coef_step * sizeof(double), hipMemcpyHostToDevice, p->st));
+                gcoef = dcoef.p;
+            }
+        }
+        a.snap = snapping ? (dev ? snap : dsnap.p) : nullptr; a.s0 = dev ? 0 : s0;
+        a.obs = observing ? (dev ? obs : dobs.p) : nullptr; a.j0 = dev ? 0 : j0;
+        for (int m0 = n0; !rc && m0 < n1; m0 += group) {
+            a.n0 = m0; a.nst = std::min(group, n1 - m0);
+            m.acoef = ops ? gcoef + (size_t)(m0 - n0) * coef_step : nullptr;
+            rc = launch_tdse_spline(a, slots, p->st);
+        }
+        if (!rc && !dev && s1 > s0)
+            rc = HIP_RC(hipMemcpyAsync(snap + (size_t)s0 * snap_one, dsnap.p, (size_t)(s1 - s0) * snap_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        if (!rc && !dev && j1 > j0)
+            rc = HIP_RC(hipMemcpyAsync(obs + (size_t)j0 * row_one, dobs.p, (size_t)(j1 - j0) * row_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        if (!rc && !dev) rc = HIP_RC(hipStreamSynchronize(p->st));     // the staging buffers are free for the next group
+    }
+    if (!rc && observing) {                                            // the row of the final packets: a launch that only measures
+        a.n0 = nsteps; a.nst = 0; a.fin = 1; a.jfin = nobs - 1; a.snap = nullptr; m.acoef = nullptr;
+        a.obs = dev ? obs : dobs.p; a.j0 = dev ? 0 : nobs - 1;
+        rc = launch_tdse_spline(a, slots, p->st);
+        if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(obs + (size_t)(nobs - 1) * row_one, dobs.p, row_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(c, dc.p, 2 * N * nscan * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    if (!rc) rc = HIP_RC(hipMemcpyAsync(info, dinfo.p, (size_t)nscan * sizeof(int), hipMemcpyDeviceToHost, p->st));
+    return drain(p, rc);
+}
+
+extern "C" int bspatom_tdse_spline(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w,
+                                   int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop, const double *GB, int nsteps,
+                                   double dt, const double *coef, double *c, int snap_every, double *snap, int obs_every, int nproj,
+                                   const double *P, double *obs, int32_t *info)
+{
+    return tdse_spline_impl(p, nscan, nch, l, nabs, WB, w, ncoup, cr, cc, ctr, nop, GB, nsteps, dt, coef, c, snap_every, snap, obs_every, nproj,
+                            P, obs, info, false);
+}
+extern "C" int bspatom_tdse_spline_dev(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB_dev,
+                                       const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop,
+                                       const double *GB_dev, int nsteps, double dt, const double *coef_dev, double *c_dev, int snap_every,
+                                       double *snap_dev, int obs_every, int nproj, const double *P_dev, double *obs_dev, int32_t *info)
+{
+    return tdse_spline_impl(p, nscan, nch, l, nabs, WB_dev, w, ncoup, cr, cc, ctr, nop, GB_dev, nsteps, dt, coef_dev, c_dev, snap_every,
+                            snap_dev, obs_every, nproj, P_dev, obs_dev, info, true);
 }
 
 extern "C" int bspatom_resolvent_coupled(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,

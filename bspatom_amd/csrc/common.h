@@ -111,6 +111,8 @@ struct Options {
                                  // group of steps) in MB (0 = 256 MiB); small values force several groups (the test's hook)
     int tdse_adapt_group = 0;    // BSP_TDSE_ADAPT_GROUP: > 0 = attempts that bspatom_tdse_adaptive enqueues between two looks at its control block (0 = 16); the
                                  // result does not depend on it (the test's hook)
+    int tdse_spline_group = 0;   // BSP_TDSE_SPLINE_GROUP: > 0 = steps per launch of bspatom_tdse_spline (0 = 64): no launch runs for long; the result does
+                                 // not depend on it (the test's hook)
     int resolvent_stage_mb = 0;  // BSP_RESOLVENT_STAGE_MB: > 0 = bound in MB on the slot scratch of bspatom_resolvent and on the X of one group of matrices
                                  // of its host variant (0 = 2048); one slot and one matrix at least; results do not depend on it (the test's hook)
     int resolvent_slots = 0;     // BSP_RESOLVENT_SLOTS: > 0 = work slots (resident waves) of resolvent_kernel, 0 = the occupancy query x CUs;
@@ -406,6 +408,22 @@ int resolvent_wide_max_band();
 size_t resolvent_wide_slot_doubles(int n, int k, int nch, int nrhs);
 int resolvent_wide_slots(int k, int nch, int nmat, int *slots);
 int launch_resolvent_wide(const ResolventCoupledArgs &a, int slots, hipStream_t st);
+// tdse_spline.hip: Crank-Nicolson steps in the spline basis on resolvent_coupled.hip's LU (bspatom_tdse_spline).  m describes the
+// matrix as for launch_resolvent_coupled with ONE record of channels: chan, w [nch], z [nch] = (0, 2/dt); acoef: the coefficients of
+// this launch's first step, [step][scan][ncoup][nop] complex; P, nproj: the projections of the rows; info [nscan]: the launch ADDS
+// its replaced pivots; work: slots * resolvent_coupled_slot_doubles.  m.nmat, m.nrhs, m.B, m.X, m.R are not read.
+// The launch runs steps n0 .. n0 + nst - 1 of every scan on c [nscan][nch][n] complex.  snap (or null): the snapshot after step n,
+// (n + 1) % snap_every == 0, goes to snapshot (n + 1) / snap_every - 1 - s0 of snap [.][nscan][nch][n].  obs (or null): the row of
+// step n, n % obs_every == 0, goes to row n / obs_every - j0 of obs [.][nscan][nch + 2 nproj]; with fin != 0 the packets after the
+// launch's last step are measured into row jfin - j0 (nst = 0: a launch that only measures).
+struct TdseSplineArgs {
+    ResolventCoupledArgs m;
+    int nscan, n0, nst, snap_every, s0, obs_every, j0, fin, jfin;
+    double g;                                  // 4 / dt
+    double *c, *snap, *obs;
+};
+int tdse_spline_slots(int k, int nch, int nscan, int *slots);
+int launch_tdse_spline(const TdseSplineArgs &a, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

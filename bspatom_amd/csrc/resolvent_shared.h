@@ -155,8 +155,10 @@ __device__ __forceinline__ double2 rc_load(const double2 *p, bool ok)
     if (ok) v = *p;
     return v;
 }
-// M(R, C) of item `it`, R = i nch + c, C = j nch + c2.  fl: the sum of the magnitudes of the terms (the pivot threshold's floor).
-__device__ __forceinline__ void rc_entry(const ResolventCoupledArgs &a, int it, int R, int C, double &re, double &im, double &fl)
+// M(R, C), R = i nch + c, C = j nch + c2: channels, z and w of item `it`, coupling coefficients of item `ita` (the resolvent calls:
+// ita = it; a time step: one record of channels, a coefficient set per step).  fl: the sum of the magnitudes of the terms (the
+// pivot threshold's floor).
+__device__ __forceinline__ void rc_entry(const ResolventCoupledArgs &a, int it, int ita, int R, int C, double &re, double &im, double &fl)
 {
     re = 0.0; im = 0.0; fl = 0.0;
     const int n = a.n, b = a.k - 1, nch = a.nch;
@@ -182,7 +184,7 @@ __device__ __forceinline__ void rc_entry(const ResolventCoupledArgs &a, int it, 
     for (int p = 0; p < a.ncoup; ++p) {
         if (a.cr[p] != c || a.cc[p] != c2) continue;
         const size_t at = a.ctr[p] ? (size_t)(i - j + b) * n + j : (size_t)(j - i + b) * n + i;   // G(i, j), or G(j, i) for the transpose
-        const double *co = a.acoef + ((size_t)it * a.ncoup + p) * a.nop * 2;
+        const double *co = a.acoef + ((size_t)ita * a.ncoup + p) * a.nop * 2;
         for (int o = 0; o < a.nop; ++o) {
             const double g = a.GB[(size_t)o * cs + at];
             re += co[2 * o] * g;

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(RW_NT) void resolvent_wide_kernel(const ResolventCo
                 const int i = c - 2 * bw + o;
                 if (i >= 0 && i < N) {
                     double re = 0.0, im = 0.0, fl = 0.0;
-                    if (o >= bw) rc_entry(a, it, i, c, re, im, fl);  // above it: the room of the fill, zero
+                    if (o >= bw) rc_entry(a, it, it, i, c, re, im, fl);  // above it: the room of the fill, zero
                     AB[(size_t)c * LD + o] = make_double2(re, im);
                     if (o == 2 * bw) { dmax = fmax(dmax, fabs(re) + fabs(im)); dflo = fmax(dflo, fl); }
                 }

@@ -1073,6 +1073,61 @@ def coupled_eigenpair(prob, l, couplings, G, a, shift, x0, zoff=None, W=None, w=
     return lam, x, history
 
 
+# ---- the TDSE in the spline basis: Crank-Nicolson steps on the coupled LU (Problem.tdse_spline) ------------------------------
+def band_symmetric(UB):
+    """The full band (2k-1, n) of the symmetric matrix whose upper band is UB (k, n), UB[d, i] = A(i, i + d) (Problem.assemble's SB,
+    HB[l]): F[d + k - 1, i] = A(i, i + d), zero where i + d is outside 0 .. n-1.  An index shuffle, no arithmetic: band_apply on it is
+    the product b = S c of a Problem.tdse_spline step bit for bit."""
+    import numpy as np
+    UB = np.asarray(UB)
+    k, n = UB.shape
+    F = np.zeros((2 * k - 1, n), dtype=UB.dtype)
+    for d in range(k):
+        F[k - 1 + d, :n - d] = UB[d, :n - d]
+        F[k - 1 - d, d:] = UB[d, :n - d]
+    return F
+
+
+def spline_midpoints(t0, dt, nsteps):
+    """The times t0 + (n + 1/2) dt, n < nsteps, at which a Crank-Nicolson step of Problem.tdse_spline takes its Hamiltonian"""
+    import numpy as np
+    return float(t0) + (np.arange(nsteps) + 0.5) * float(dt)
+
+
+def spline_coefficients(couplings_a, F_mid):
+    """The coefficient table of Problem.tdse_spline from a static pattern times the field: couplings_a = (couplings, a) as stark_system
+    (with F = 1) returns them -- couplings [(cr, cc, ctr)], a (ncoup,) or (ncoup, nop) --, F_mid the field at the steps' midpoints,
+    (nsteps,) for every scan or (nsteps, nscan), real or complex.  Entry p gets a[p] F, a transposed partner (ctr = 1) a[p] conj(F):
+    with a partner pattern that is the conjugate of its entry's, the coupling is Hermitian at every step.  Returns complex128
+    (nsteps, nscan, ncoup, nop), nscan = 1 for a one-dimensional F_mid (Problem.tdse_spline broadcasts it)."""
+    import numpy as np
+    couplings, a = couplings_a
+    ncoup = len(couplings)
+    a = np.asarray(a, dtype=np.complex128).reshape(ncoup, -1)
+    F = np.asarray(F_mid, dtype=np.complex128)
+    F = F[:, None] if F.ndim == 1 else F
+    ctr = np.array([int(t) for _, _, t in couplings], dtype=bool).reshape(ncoup)
+    f = np.where(ctr[None, None, :], np.conj(F)[:, :, None], F[:, :, None])          # (nsteps, nscan, ncoup)
+    return np.ascontiguousarray(f[..., None] * a[None, None])
+
+
+def spline_packet(prob, channels, ch, c_vec):
+    """A wave packet for Problem.tdse_spline: (nch, nfun) complex, the coefficient vector c_vec (e.g. an eigenvector from eigvecs) in
+    position `ch` of `channels`, zero elsewhere"""
+    import numpy as np
+    c = np.zeros((len(channels), prob.nfun), dtype=np.complex128)
+    c[ch] = np.asarray(c_vec).reshape(prob.nfun)
+    return c
+
+
+def spline_yield(obs, nch=None):
+    """1 - sum_c N_c of every row of Problem.tdse_spline, (nobs, nscan): with an absorber and a packet normalised to c^H S c = 1, the
+    ionisation yield so far.  nch: the channels, when the rows carry projections behind the norms (default: every column is a norm)."""
+    import numpy as np
+    obs = np.asarray(obs)
+    return 1.0 - obs[..., :obs.shape[-1] if nch is None else nch].sum(axis=-1)
+
+
 # ---- KIND_PI = 0 on several GPUs: one process per GPU, channels sharded, spectra gathered (SURVEY 8e) ---------------
 def write_structure_outputs(nfun, lmax, E, l_ini, wf, outdir):
     """Enl.dat, wf_n0.dat and the stdout text of a KIND_PI = 0 run from the spectra E[l][i] and the tabulated initial

@@ -657,6 +657,11 @@ int bspatom_tdse_adaptive_dev(bspatom_problem *p, int nch, int count, const doub
                               double tol, int max_level, int level0, int64_t *stats, int log_cap, int32_t *log_i_dev, double *log_e_dev,
                               double *log_f_dev);
 
+/* The TDSE in the B-spline basis itself, Crank-Nicolson steps on the coupled banded LU: the spline-basis entry points and their
+ * description are in bspatom_tdse_spline.h beside this file, which is part of this header (the twelve calls above are the eigenbasis
+ * family; the spline call has another argument list, bspatom_resolvent_coupled's, and its own guarantees S1 - S5). */
+#include "bspatom_tdse_spline.h"
+
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
  * solve checks it against the spectra when they are there.  state of the last solve: 0 = no early vector (other route, channel not in
