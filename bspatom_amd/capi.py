@@ -40,7 +40,7 @@ EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup
            "bspatom_set_option", "bspatom_get_option", "bspatom_kernel_times", "bspatom_kernel_slot_name"]
 
 # what include/bspatom_tdse_spline.h, the part of the header for the spline-basis TDSE, declares (EXPORTS is include/bspatom.h's own text)
-SPLINE_EXPORTS = ["bspatom_tdse_spline", "bspatom_tdse_spline_dev"]
+SPLINE_EXPORTS = ["bspatom_tdse_spline", "bspatom_tdse_spline_dev", "bspatom_tdse_spline_wide", "bspatom_tdse_spline_wide_dev"]
 
 _lib = None
 
@@ -101,6 +101,8 @@ def lib():
             getattr(L, "bspatom_tdse_" + name + "_dev").argtypes = list(types)
         L.bspatom_tdse_spline.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, dbl, vp, vp, i32, vp, i32, i32, vp, vp, vp]
         L.bspatom_tdse_spline_dev.argtypes = list(L.bspatom_tdse_spline.argtypes)
+        L.bspatom_tdse_spline_wide.argtypes = list(L.bspatom_tdse_spline.argtypes)
+        L.bspatom_tdse_spline_wide_dev.argtypes = list(L.bspatom_tdse_spline.argtypes)
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -884,6 +886,16 @@ class Problem:
         per channel, then Re, Im of sum P_r (S c) for the projections P (nproj, nch, nfun), for the steps 0, obs_every, .. < nsteps
         and the final state (tdse_nobs) --, then snaps (nsteps // snap_every, nscan, nch, nfun) if snap_every >= 1.  info (nscan,):
         replaced pivots, 0.  nsteps = 0 with obs_every >= 1 only measures.  nch * k - 1 <= 63, else BspAtomError(-5)."""
+        return self._tdse_spline("bspatom_tdse_spline", l, c0, dt, nsteps, couplings, G, coef, W, w, P, obs_every, snap_every)
+
+    def tdse_spline_wide(self, l, c0, dt, nsteps, couplings=None, G=None, coef=None, W=None, w=None, P=None, obs_every=0, snap_every=0):
+        """tdse_spline on the blocked LU for wide bands (bspatom_tdse_spline_wide): the same arguments and results, the matrix
+        resolvent_coupled_wide's at z = 2i/dt, nch * k - 1 <= 255, else BspAtomError(-5).  Not promised bit-equal to tdse_spline where
+        both apply; host.spline_propagate chooses between them."""
+        return self._tdse_spline("bspatom_tdse_spline_wide", l, c0, dt, nsteps, couplings, G, coef, W, w, P, obs_every, snap_every)
+
+    def _tdse_spline(self, entry, l, c0, dt, nsteps, couplings, G, coef, W, w, P, obs_every, snap_every):
+        """the body of tdse_spline and tdse_spline_wide: the arrays of the call, the entry point by name"""
         n = self.nfun
         W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
         G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
@@ -899,9 +911,9 @@ class Problem:
         snaps = np.zeros((nsteps // snap_every, nscan, nch, n), dtype=np.complex128) if snap_every > 0 else None
         obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj)) if obs_every > 0 else None
         info = np.zeros(nscan, dtype=np.int32)
-        _chk(lib().bspatom_tdse_spline(self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), 0 if cr is None else cr.size, _p(cr), _p(cc), _p(ctr),
-                                       nop, _p(G), nsteps, float(dt), _p(coef), _p(c), snap_every, _p(snaps), obs_every, nproj, _p(P),
-                                       _p(obs), _p(info)), "bspatom_tdse_spline")
+        _chk(getattr(lib(), entry)(self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), 0 if cr is None else cr.size, _p(cr), _p(cc), _p(ctr),
+                                   nop, _p(G), nsteps, float(dt), _p(coef), _p(c), snap_every, _p(snaps), obs_every, nproj, _p(P),
+                                   _p(obs), _p(info)), entry)
         return (c[0] if one else c, info) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
 
     def tdse_spline_dev(self, l, nscan, nsteps, dt, c_ptr, couplings=None, nop=0, G_ptr=None, coef_ptr=None, nabs=0, W_ptr=None, w=None,
@@ -909,11 +921,23 @@ class Problem:
         """tdse_spline with the packets (nscan * nch * nfun complex at c_ptr, advanced in place), G, W, the coefficient table (nsteps *
         nscan * ncoup * nop complex), P, the rows and the snapshots in device memory of this problem's device, e.g. torch tensors'
         data_ptr(); l, w and couplings are host values.  Returns info (nscan,) when the result is there."""
+        return self._tdse_spline_dev("bspatom_tdse_spline_dev", l, nscan, nsteps, dt, c_ptr, couplings, nop, G_ptr, coef_ptr, nabs, W_ptr, w, nproj,
+                                     P_ptr, obs_every, obs_ptr, snap_every, snap_ptr)
+
+    def tdse_spline_wide_dev(self, l, nscan, nsteps, dt, c_ptr, couplings=None, nop=0, G_ptr=None, coef_ptr=None, nabs=0, W_ptr=None, w=None,
+                             nproj=0, P_ptr=None, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None):
+        """tdse_spline_dev on the blocked LU for wide bands (bspatom_tdse_spline_wide_dev): the same arguments, nch * k - 1 <= 255."""
+        return self._tdse_spline_dev("bspatom_tdse_spline_wide_dev", l, nscan, nsteps, dt, c_ptr, couplings, nop, G_ptr, coef_ptr, nabs, W_ptr, w,
+                                     nproj, P_ptr, obs_every, obs_ptr, snap_every, snap_ptr)
+
+    def _tdse_spline_dev(self, entry, l, nscan, nsteps, dt, c_ptr, couplings, nop, G_ptr, coef_ptr, nabs, W_ptr, w, nproj, P_ptr, obs_every, obs_ptr,
+                         snap_every, snap_ptr):
+        """the body of tdse_spline_dev and tdse_spline_wide_dev: the entry point by name"""
         nch, l, w, cr, cc, ctr, _ = self._spline_system(l, w, couplings, None, nscan, 0, nop)
         info = np.zeros(nscan, dtype=np.int32)
-        _chk(lib().bspatom_tdse_spline_dev(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), 0 if cr is None else cr.size, _p(cr),
-                                           _p(cc), _p(ctr), nop, _ptr(G_ptr), nsteps, float(dt), _ptr(coef_ptr), _ptr(c_ptr), snap_every,
-                                           _ptr(snap_ptr), obs_every, nproj, _ptr(P_ptr), _ptr(obs_ptr), _p(info)), "bspatom_tdse_spline_dev")
+        _chk(getattr(lib(), entry)(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), 0 if cr is None else cr.size, _p(cr),
+                                   _p(cc), _p(ctr), nop, _ptr(G_ptr), nsteps, float(dt), _ptr(coef_ptr), _ptr(c_ptr), snap_every,
+                                   _ptr(snap_ptr), obs_every, nproj, _ptr(P_ptr), _ptr(obs_ptr), _p(info)), entry)
         return info
 
     def early_vector_state(self):

@@ -7,6 +7,7 @@
 //   bspatom_resolvent_coupled_wide / _dev: the same call on the blocked LU for wide bands (resolvent_wide.hip).
 //   bspatom_tdse_spline / _dev: Crank-Nicolson steps on the coupled LU (tdse_spline.hip); a call path of its own below (every packet
 //     has its own right-hand side and the steps follow each other), the screening and the scratch rules of the coupled call.
+//   bspatom_tdse_spline_wide / _dev: the same call on the blocked LU for wide bands (tdse_spline_wide.hip), through the same path.
 // The eight resolvent entry points run through resolvent_call: a front function per flavour screens what is particular to it, describes the call by
 // counts per ITEM (a matrix, a chain, a coupled matrix) and hands over its slot query and its launcher.
 #include <algorithm>
@@ -18,6 +19,19 @@ using namespace bsp;
 static constexpr size_t RESOLVENT_STAGE_BYTES = (size_t)2048 << 20;
 static constexpr size_t SPLINE_STAGE_BYTES = (size_t)256 << 20;    // tdse_stage_mb's default (capi_tdse.hip)
 static constexpr int SPLINE_GROUP = 64;                            // steps per launch (tdse_spline_group)
+// The wide call's launch length when tdse_spline_group is unset: a wide step is slow (48 to 715 ms per matrix at
+// nfun = 1024), so the largest g in 1 .. SPLINE_GROUP with
+//     g * ceil(nscan / slots) * 16 N bw^2 flop <= SPLINE_WIDE_LAUNCH_FLOP = 27.6e9:
+// two seconds at 13.8 Gflop/s per CU, the slowest rate measured for this LU under its model 8 N bw (2 bw).  Nothing computed depends
+// on it (S2).
+static constexpr double SPLINE_WIDE_LAUNCH_FLOP = 27.6e9;
+static int spline_wide_group(int N, int bw, int nscan, int slots)
+{
+    const double per_step = (double)((nscan + slots - 1) / slots) * 16.0 * (double)N * (double)bw * (double)bw;
+    int g = SPLINE_GROUP;
+    while (g > 1 && (double)g * per_step > SPLINE_WIDE_LAUNCH_FLOP) --g;
+    return g;
+}
 
 // A call as the shared path sees it: the caller's arrays and how much of each an item takes (single | chain | coupled)
 struct ResolventCall {
@@ -216,10 +230,11 @@ static int resolvent_coupled_impl(bspatom_problem *p, int nmat, int nch, const i
 // bspatom_tdse_spline / _dev: nsteps Crank-Nicolson steps of nscan packets, each step the coupled matrix at z = 2i / dt with the
 // step's coefficients.  The steps go out in launches of at most tdse_spline_group; the host variant stages the coefficients, the
 // snapshots and the rows by groups of whole steps under tdse_stage_mb (one step at least); neither changes what a step computes.
+// wide: the same arguments to tdse_spline_wide.hip, its limit, its slots, its scratch (one vector per slot) and its launch length.
 static int tdse_spline_impl(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w, int ncoup,
                             const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop, const double *GB, int nsteps, double dt,
                             const double *coef, double *c, int snap_every, double *snap, int obs_every, int nproj, const double *P,
-                            double *obs, int32_t *info, bool dev)
+                            double *obs, int32_t *info, bool dev, bool wide)
 {
     if (!p || !l || !c || !info || nscan < 1 || nch < 1 || nsteps < 0 || nabs < 0 || nproj < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
     if (!std::isfinite(dt) || !(dt > 0.0)) return BSP_ERR_ARG;
@@ -233,9 +248,10 @@ static int tdse_spline_impl(bspatom_problem *p, int nscan, int nch, const int32_
     for (int q = 0; q < ncoup; ++q)
         if (cr[q] < 0 || cr[q] >= nch || cc[q] < 0 || cc[q] >= nch || ctr[q] < 0 || ctr[q] > 1) return BSP_ERR_ARG;
     const int n = p->hs.nfun, k = p->hs.k;
-    if ((long long)nch * k - 1 > resolvent_coupled_max_band()) {
-        fprintf(stderr, "bspatom_tdse_spline: half-width nch*k - 1 = %lld exceeds BSPATOM_COUPLED_MAX_BAND = %d\n", (long long)nch * k - 1,
-                resolvent_coupled_max_band());
+    const int max_band = wide ? resolvent_wide_max_band() : resolvent_coupled_max_band();
+    if ((long long)nch * k - 1 > max_band) {
+        fprintf(stderr, "bspatom_tdse_spline%s: half-width nch*k - 1 = %lld exceeds BSPATOM_COUPLED%s_MAX_BAND = %d\n", wide ? "_wide" : "",
+                (long long)nch * k - 1, wide ? "_WIDE" : "", max_band);
         return BSP_ERR_UNSUPPORTED;
     }
     if ((long long)nch * n > 0x3fffffffLL || (long long)nsteps * nscan > 0x3fffffffLL) return BSP_ERR_ARG;
@@ -245,12 +261,14 @@ static int tdse_spline_impl(bspatom_problem *p, int nscan, int nch, const int32_
     const size_t coef_step = (size_t)2 * nscan * ncoup * (ncoup > 0 ? nop : 0), snap_one = 2 * N * nscan, row_one = RW * nscan;   // doubles
     BSP_HIP(hipSetDevice(p->device));
     int rc, slots = 0;
-    if ((rc = tdse_spline_slots(k, nch, nscan, &slots))) return rc;
+    if ((rc = wide ? tdse_spline_wide_slots(k, nch, nscan, &slots) : tdse_spline_slots(k, nch, nscan, &slots))) return rc;
     if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, nscan);
-    const size_t slot_doubles = resolvent_coupled_slot_doubles(n, k, nch);
+    const size_t slot_doubles = wide ? resolvent_wide_slot_doubles(n, k, nch, 1) : resolvent_coupled_slot_doubles(n, k, nch);
     const size_t rstage = opts().resolvent_stage_mb > 0 ? (size_t)opts().resolvent_stage_mb << 20 : RESOLVENT_STAGE_BYTES;
     slots = (int)std::max<size_t>(1, std::min<size_t>(slots, rstage / (slot_doubles * sizeof(double))));
-    const int group = opts().tdse_spline_group > 0 ? opts().tdse_spline_group : SPLINE_GROUP;
+    const int group = opts().tdse_spline_group > 0 ? opts().tdse_spline_group
+                                                   : (wide ? spline_wide_group(nch * n, nch * k - 1, nscan, slots) : SPLINE_GROUP);
+    auto launch = [&](const TdseSplineArgs &ta) { return wide ? launch_tdse_spline_wide(ta, slots, p->st) : launch_tdse_spline(ta, slots, p->st); };
     // the host variant's staging groups: whole steps, a step counted with a snapshot and a row of its own (an upper bound)
     int sgroup = std::max(nsteps, 1);
     if (!dev) {
@@ -307,7 +325,7 @@ static int tdse_spline_impl(bspatom_problem *p, int nscan, int nch, const int32_
         for (int m0 = n0; !rc && m0 < n1; m0 += group) {
             a.n0 = m0; a.nst = std::min(group, n1 - m0);
             m.acoef = ops ? gcoef + (size_t)(m0 - n0) * coef_step : nullptr;
-            rc = launch_tdse_spline(a, slots, p->st);
+            rc = launch(a);
         }
         if (!rc && !dev && s1 > s0)
             rc = HIP_RC(hipMemcpyAsync(snap + (size_t)s0 * snap_one, dsnap.p, (size_t)(s1 - s0) * snap_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
@@ -318,7 +336,7 @@ static int tdse_spline_impl(bspatom_problem *p, int nscan, int nch, const int32_
     if (!rc && observing) {                                            // the row of the final packets: a launch that only measures
         a.n0 = nsteps; a.nst = 0; a.fin = 1; a.jfin = nobs - 1; a.snap = nullptr; m.acoef = nullptr;
         a.obs = dev ? obs : dobs.p; a.j0 = dev ? 0 : nobs - 1;
-        rc = launch_tdse_spline(a, slots, p->st);
+        rc = launch(a);
         if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(obs + (size_t)(nobs - 1) * row_one, dobs.p, row_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
     }
     if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(c, dc.p, 2 * N * nscan * sizeof(double), hipMemcpyDeviceToHost, p->st));
@@ -332,7 +350,7 @@ extern "C" int bspatom_tdse_spline(bspatom_problem *p, int nscan, int nch, const
                                    const double *P, double *obs, int32_t *info)
 {
     return tdse_spline_impl(p, nscan, nch, l, nabs, WB, w, ncoup, cr, cc, ctr, nop, GB, nsteps, dt, coef, c, snap_every, snap, obs_every, nproj,
-                            P, obs, info, false);
+                            P, obs, info, false, false);
 }
 extern "C" int bspatom_tdse_spline_dev(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB_dev,
                                        const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop,
@@ -340,7 +358,24 @@ extern "C" int bspatom_tdse_spline_dev(bspatom_problem *p, int nscan, int nch, c
                                        double *snap_dev, int obs_every, int nproj, const double *P_dev, double *obs_dev, int32_t *info)
 {
     return tdse_spline_impl(p, nscan, nch, l, nabs, WB_dev, w, ncoup, cr, cc, ctr, nop, GB_dev, nsteps, dt, coef_dev, c_dev, snap_every,
-                            snap_dev, obs_every, nproj, P_dev, obs_dev, info, true);
+                            snap_dev, obs_every, nproj, P_dev, obs_dev, info, true, false);
+}
+extern "C" int bspatom_tdse_spline_wide(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w,
+                                        int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop, const double *GB,
+                                        int nsteps, double dt, const double *coef, double *c, int snap_every, double *snap, int obs_every,
+                                        int nproj, const double *P, double *obs, int32_t *info)
+{
+    return tdse_spline_impl(p, nscan, nch, l, nabs, WB, w, ncoup, cr, cc, ctr, nop, GB, nsteps, dt, coef, c, snap_every, snap, obs_every, nproj,
+                            P, obs, info, false, true);
+}
+extern "C" int bspatom_tdse_spline_wide_dev(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB_dev,
+                                            const int32_t *w, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop,
+                                            const double *GB_dev, int nsteps, double dt, const double *coef_dev, double *c_dev,
+                                            int snap_every, double *snap_dev, int obs_every, int nproj, const double *P_dev, double *obs_dev,
+                                            int32_t *info)
+{
+    return tdse_spline_impl(p, nscan, nch, l, nabs, WB_dev, w, ncoup, cr, cc, ctr, nop, GB_dev, nsteps, dt, coef_dev, c_dev, snap_every,
+                            snap_dev, obs_every, nproj, P_dev, obs_dev, info, true, true);
 }
 
 extern "C" int bspatom_resolvent_coupled(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,

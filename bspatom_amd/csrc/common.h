@@ -424,6 +424,10 @@ struct TdseSplineArgs {
 };
 int tdse_spline_slots(int k, int nch, int nscan, int *slots);
 int launch_tdse_spline(const TdseSplineArgs &a, int slots, hipStream_t st);
+// tdse_spline_wide.hip: the same steps and arguments on resolvent_wide.hip's blocked LU, half-widths up to BSPATOM_COUPLED_WIDE_MAX_BAND
+// (bspatom_tdse_spline_wide); work: slots * resolvent_wide_slot_doubles(n, k, nch, 1)
+int tdse_spline_wide_slots(int k, int nch, int nscan, int *slots);
+int launch_tdse_spline_wide(const TdseSplineArgs &a, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

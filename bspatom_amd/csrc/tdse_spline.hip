@@ -22,77 +22,10 @@
 #include "wave_ops.h"
 #include "resolvent_shared.h"
 #include "resolvent_coupled_lu.h"
+#include "tdse_spline_steps.h"
 #include "../../include/bspatom.h"
 
 namespace bsp {
-namespace {
-
-// b = S c of one packet (c: [nch][n] complex as doubles, channel-major) into y at position i nch + ch.  S(i, j) from the problem's
-// upper band SB[|d| n + min(i, j)], the band rc_entry reads; b_re, b_im start at +0.0 and add S(i, i + d) c(i + d) for d = -(k-1) ..
-// k-1 ascending, columns outside 0 .. n-1 skipped; IEEE multiplies and adds, nothing contracted.  The whole workgroup.
-__device__ __forceinline__ void ts_rhs(const int n, const int nch, const int b, const double *__restrict__ SB, const double *c, double2 *y,
-                                       const int tid)
-{
-#pragma clang fp contract(off)
-    for (int e = tid; e < n * nch; e += RC_NT) {
-        const int ch = e / n, i = e - ch * n;
-        const double *cc = c + (size_t)2 * ch * n;
-        double br = 0.0, bi = 0.0;
-        for (int d = -b; d <= b; ++d) {
-            const int j = i + d;
-            if (j < 0 || j >= n) continue;
-            const double s = SB[(size_t)(d < 0 ? -d : d) * n + (d < 0 ? j : i)];
-            br = br + s * cc[2 * j];
-            bi = bi + s * cc[2 * j + 1];
-        }
-        y[i * nch + ch] = make_double2(br, bi);
-    }
-}
-
-// The row of a packet from b = S c in y (visible to the workgroup): row[ch] = Re sum_i conj(c(i, ch)) b(i, ch) -- thread-strided
-// partial sums over i ascending, each wave's fixed tree, the waves in ascending order --, then rc_project's p_r^T b, Re and Im,
-// r < nproj.  red: RC_NW words of LDS; the whole workgroup.
-__device__ __forceinline__ void ts_row(const int n, const int nch, const int nproj, const double *P, const double *c, const double2 *y,
-                                       double *row, double2 *red, const int tid)
-{
-#pragma clang fp contract(off)
-    const int lane = tid & 63, wv = tid >> 6;
-    for (int ch = 0; ch < nch; ++ch) {
-        const double *cc = c + (size_t)2 * ch * n;
-        double s = 0.0;
-        for (int i = tid; i < n; i += RC_NT) {
-            const double2 bv = y[i * nch + ch];
-            s = s + (cc[2 * i] * bv.x + cc[2 * i + 1] * bv.y);
-        }
-        s = wave_sum(s);
-        if (lane == 0) red[wv] = make_double2(s, 0.0);
-        lds_barrier();
-        if (tid == 0) {
-            double t = red[0].x;
-#pragma unroll
-            for (int u = 1; u < RC_NW; ++u) t = t + red[u].x;
-            row[ch] = t;
-        }
-        lds_barrier();
-    }
-    if (nproj > 0) rc_project<RC_NT>(n, nch, nproj, P, y, row + nch, red, tid);
-}
-
-// c' = -(4 i / dt) x - c with g = 4 / dt: c'_re = g x_im - c_re, c'_im = -(g x_re) - c_im, one multiply and one subtract each, nothing
-// contracted; x in y in the matrix's ordering.  snap (or null) takes a copy.  The whole workgroup.
-__device__ __forceinline__ void ts_update(const int n, const int nch, const double g, const double2 *y, double *c, double *snap, const int tid)
-{
-#pragma clang fp contract(off)
-    for (int e = tid; e < n * nch; e += RC_NT) {
-        const int ch = e / n, i = e - ch * n;
-        const double2 x = y[i * nch + ch];
-        const double pr = g * x.y, pi = g * x.x;
-        const double nr = pr - c[2 * e], ni = -pi - c[2 * e + 1];
-        c[2 * e] = nr; c[2 * e + 1] = ni;
-        if (snap) { snap[2 * e] = nr; snap[2 * e + 1] = ni; }
-    }
-}
-}  // namespace
 
 // A PERSISTENT grid of workgroups, one per work slot, takes the scans by static stride and runs the launch's steps of a scan one
 // after the other.  Slot scratch: resolvent_coupled_kernel's (rc_slot_doubles).
@@ -114,11 +47,11 @@ __global__ __launch_bounds__(RC_NT) void tdse_spline_kernel(const TdseSplineArgs
         for (int s = 0; s < a.nst + (a.fin && a.obs ? 1 : 0); ++s) {
             const int nstep = a.n0 + s;
             const bool last = s == a.nst;
-            ts_rhs(n, nch, m.k - 1, m.SB, c, y, tid);
+            ts_rhs<RC_NT>(n, nch, m.k - 1, m.SB, c, y, tid);
             if (last || (a.obs && nstep % a.obs_every == 0)) {
                 const int j = last ? a.jfin : nstep / a.obs_every;
                 __syncthreads();                                     // b is in memory
-                ts_row(n, nch, m.nproj, m.P, c, y, a.obs + ((size_t)(j - a.j0) * a.nscan + q) * RW, red, tid);
+                ts_row<RC_NT>(n, nch, m.nproj, m.P, c, y, a.obs + ((size_t)(j - a.j0) * a.nscan + q) * RW, red, tid);
             }
             if (last) {
                 __syncthreads();                                     // every load of y is back before the next scan's b overwrites it
@@ -132,7 +65,7 @@ __global__ __launch_bounds__(RC_NT) void tdse_spline_kernel(const TdseSplineArgs
             double *sn = nullptr;
             if (a.snap && (nstep + 1) % a.snap_every == 0)
                 sn = a.snap + ((size_t)((nstep + 1) / a.snap_every - 1 - a.s0) * a.nscan + q) * 2 * N;
-            ts_update(n, nch, a.g, y, c, sn, tid);
+            ts_update<RC_NT>(n, nch, a.g, y, c, sn, tid);
             __syncthreads();                                         // the packet is in memory before the next step reads it across threads
         }
         if (tid == 0 && a.nst > 0) m.info[q] += nper;

@@ -936,6 +936,7 @@ def cauchy_moments(prob, n_ini, order):
 
 # ---- channels coupled to all orders: one banded LU across the channels (Problem.resolvent_coupled) --------------------------
 COUPLED_MAX_BAND = 63                      # BSPATOM_COUPLED_MAX_BAND of include/bspatom.h: resolvent_coupled's half-width limit
+COUPLED_WIDE_MAX_BAND = 255                # BSPATOM_COUPLED_WIDE_MAX_BAND: the limit of resolvent_coupled_wide and tdse_spline_wide
 
 
 def band_transpose(G):
@@ -1118,6 +1119,20 @@ def spline_packet(prob, channels, ch, c_vec):
     c = np.zeros((len(channels), prob.nfun), dtype=np.complex128)
     c[ch] = np.asarray(c_vec).reshape(prob.nfun)
     return c
+
+
+def spline_propagate(prob, l, c0, dt, nsteps, **kw):
+    """Problem.tdse_spline where its LU applies (nch k - 1 <= COUPLED_MAX_BAND) and Problem.tdse_spline_wide beyond it, up to
+    COUPLED_WIDE_MAX_BAND: coupled_eigenpair's rule for the two resolvent calls.  The arguments and the results are theirs; where the
+    narrow call applies the result has its bits.  ValueError beyond 255."""
+    import numpy as np
+    nch = np.asarray(l).size
+    bw = nch * prob.k - 1
+    if bw > COUPLED_WIDE_MAX_BAND:
+        raise ValueError("spline_propagate: half-width nch*k - 1 = %d (nch = %d, k = %d) exceeds COUPLED_WIDE_MAX_BAND = %d"
+                         % (bw, nch, prob.k, COUPLED_WIDE_MAX_BAND))
+    call = prob.tdse_spline_wide if bw > COUPLED_MAX_BAND else prob.tdse_spline
+    return call(l, c0, dt, nsteps, **kw)
 
 
 def spline_yield(obs, nch=None):

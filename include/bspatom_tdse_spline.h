@@ -69,4 +69,29 @@ int bspatom_tdse_spline_dev(bspatom_problem *p, int nscan, int nch, const int32_
                             double dt, const double *coef_dev, double *c_dev, int snap_every, double *snap_dev, int obs_every, int nproj,
                             const double *P_dev, double *obs_dev, int32_t *info);
 
+/* The same call on the blocked LU for wide bands (csrc/tdse_spline_wide.hip): the 24 arguments, the layouts, the rows, the arithmetic
+ * rules 1 and 3 and the error returns of bspatom_tdse_spline; what differs:
+ *   the limit   any half-width bw = nch*k - 1 from 1 to BSPATOM_COUPLED_WIDE_MAX_BAND = 255 (28 channels at k = 9, 16 at k = 16); beyond it
+ *               BSPATOM_ERR_UNSUPPORTED with that limit on stderr.  bspatom_tdse_spline is not rerouted: it keeps its limit and its bits.
+ *   rule 2      M is bspatom_resolvent_coupled_wide's entry, pivot threshold, factorisation and solve with ONE right-hand side: the same
+ *               statements (csrc/resolvent_wide_lu.h), not copies.  Guarantees S1 - S5 hold with "bspatom_resolvent_coupled" read as
+ *               "bspatom_resolvent_coupled_wide": in S3 one step equals the band product, bspatom_resolvent_coupled_wide at z = 2i/dt with
+ *               nrhs = 1, B = b and a = the step's coefficients, and the two operations of rule 3, bit for bit.
+ *   how         one workgroup of the wide kernel's shape per work slot; the slot scratch is the wide call's with one vector.
+ *   launches    a wide step takes tens to hundreds of milliseconds, so 64 steps per launch would run for most of a minute.  Unless
+ *               "tdse_spline_group" is set, a launch takes the largest g in 1 .. 64 with
+ *                   g * ceil(nscan/slots) * 16 * N * bw^2 flop <= 27.6e9,   N = nch*nfun,
+ *               two seconds at 13.8 Gflop/s per CU, the slowest rate measured for this LU under its model 8 N bw (2 bw).  The option
+ *               overrides it; nothing computed depends on either (S2).
+ * NOT promised, beside what bspatom_tdse_spline does not promise: equality with bspatom_tdse_spline where both apply (bw <= 63) -- another
+ * elimination order, the same backward error class. */
+int bspatom_tdse_spline_wide(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w, int ncoup,
+                             const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop, const double *GB, int nsteps, double dt,
+                             const double *coef, double *c, int snap_every, double *snap, int obs_every, int nproj, const double *P,
+                             double *obs, int32_t *info);
+int bspatom_tdse_spline_wide_dev(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB_dev, const int32_t *w,
+                                 int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr, int nop, const double *GB_dev,
+                                 int nsteps, double dt, const double *coef_dev, double *c_dev, int snap_every, double *snap_dev,
+                                 int obs_every, int nproj, const double *P_dev, double *obs_dev, int32_t *info);
+
 #endif
