@@ -109,6 +109,7 @@ const OptName OPT_TABLE[] = {
     {"sb8_wgs", "BSP_SB8_WGS", &Options::sb8_wgs},
     {"sbr_phased", "BSP_SBR_PHASED", &Options::sbr_phased},
     {"sbr_lag", "BSP_SBR_LAG", &Options::sbr_lag},
+    {"sbr_xdpp", "BSP_SBR_XDPP", &Options::sbr_xdpp},
     {"fused_probe", "BSP_FUSED_PROBE", &Options::fused_probe},
     {"dipole_stage_mb", "BSP_DIPOLE_STAGE_MB", &Options::dipole_stage_mb},
     {"resolvent_stage_mb", "BSP_RESOLVENT_STAGE_MB", &Options::resolvent_stage_mb},

@@ -32,6 +32,8 @@ __host__ __device__ inline size_t ab_stride(int npad) { return (size_t)npad * 12
 
 namespace bsp {
 
+constexpr int SBR_XDPP_DEFAULT = 2;   // Options::sbr_xdpp: the best measured setting (profiles/r24_chase8_dpp.txt)
+
 // ---- run-time switches (A/B comparisons, diagnostics, test hooks) ---------------------------------
 // Read ONCE per process from the environment (BSP_* variables) at the first use; the tests flip
 // them in-process through bspatom_set_option (include/bspatom.h) to drive the fallback paths.
@@ -98,6 +100,10 @@ struct Options {
     int sbr_lag = 0;             // BSP_SBR_LAG: tiles-of-8 chase, the data-moving wave's lag (steps between the request of a column and the
                                  // wait for it): 0 = short in the passes where the ring is bound by its stagger, long elsewhere; 1 = always
                                  // long; 2 = always short; bit-identical results
+    int sbr_xdpp = SBR_XDPP_DEFAULT;   // BSP_SBR_XDPP: tiles-of-8 chase, the phased loop: what reaches the FMAs as a DPP operand (row_newbcast inside the 8
+                                 // lanes that own an item) instead of through LDS: 0 = nothing (the cross-check), 1 = z of the diagonal-tile
+                                 // wave, 2 = that wave's reflector as well (the default), 3 = the reflector in all three roles (as fast as 2
+                                 // at 128 channels, slower than 0 at 16: profiles/r24_chase8_dpp.txt); bit-identical results
     int cw_ipw = 0;              // BSP_CW_IPW: items per wave of crawford_item4_kernel (0 = 4; 1, 2: experiment 9; bit-identical results)
     int cw_ldspad = 0;           // BSP_CW_LDSPAD: KB of unused dynamic LDS per workgroup of crawford_item4_kernel (timing experiment: occupancy)
     int cw_onediv = 0;           // BSP_CW_ONEDIV: reflectors of the band route's RQ loop in the one-division form (A/B switch)

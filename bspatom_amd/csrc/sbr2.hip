@@ -808,6 +808,14 @@ constexpr int SBR_MLAG_SHORT = 2;                       // the short lag of the 
 // window element at BYTE offset `off` (the tile addresses of the chasing waves are kept in bytes: as indices every access
 // paid a shift, 16 vector instructions per step of a role)
 __device__ __forceinline__ double &ldsb(double *Lw, int off) { return *reinterpret_cast<double *>(reinterpret_cast<char *>(Lw) + off); }
+// The same element by its LDS ADDRESS (lds_addr(Lw) + off).  The window's own address is a constant the compiler learns too late to fold:
+// through ldsb every access whose offset is a lane value pays a `v_add_u32 x, 0, off` in front of it: 16 per step of role 1, which
+// instead (tiles of 8, the phased loop) adds lds_addr(Lw) once per pass to the lane constants its addresses are formed from.
+typedef __attribute__((address_space(3))) double lds_f64;
+__device__ __forceinline__ int lds_addr(double *Lw) { return (int)(size_t)(__attribute__((address_space(3))) double *)Lw; }
+__device__ __forceinline__ double &ldsa(int addr) { return *(double *)(lds_f64 *)(size_t)(unsigned)addr; }
+template <bool ABS>
+__device__ __forceinline__ double &ldsx(double *Lw, int off) { return ABS ? ldsa(off) : ldsb(Lw, off); }
 
 template <int B>
 struct Rw {
@@ -854,18 +862,101 @@ __device__ __forceinline__ void rsumBx2(double &a, double &b)
 // The reflector of the column whose element j is x0 in lane j of the item: v and tau into the slot xw, beta (lane 0) resp. zeros
 // into the window at index hx (the column's own place).  Branch-free: a column that is zero below its first element gives
 // tau = 0, v = e_0, beta = alpha.
+// vlo, tqo: what the slot receives, as this lane holds it -- its own component of v, and tau (the same bits in every lane of the item: the
+// sums of rsumBx2 are).
 template <int B>
-__device__ __forceinline__ void next_reflector(double *Lw, const double x0, const int j, const int xw, const int hx)
+__device__ __forceinline__ void next_reflector(double *Lw, const double x0, const int j, const int xw, const int hx, double &vlo, double &tqo)
 {
     double nrm2 = j > 0 ? x0 * x0 : 0.0, alpha = j == 0 ? x0 : 0.0;
     rsumBx2<B>(nrm2, alpha);
     const bool nz = nrm2 != 0.0;
     const double beta0 = -copysign(sqrt(fma(alpha, alpha, nz ? nrm2 : 1.0)), alpha);      // never zero
     const double tq0 = (beta0 - alpha) / beta0, scale0 = 1.0 / (alpha - beta0);
-    const double beta = nz ? beta0 : alpha, tq = nz ? tq0 : 0.0, scale = nz ? scale0 : 0.0;
-    Lw[xw + j] = j == 0 ? 1.0 : x0 * scale;
+    const double beta = nz ? beta0 : alpha, scale = nz ? scale0 : 0.0;
+    double tq = nz ? tq0 : 0.0;
+    // Both quotients are formed in EVERY lane, from operands that are safe either way (beta0 is never zero).  tau is stored by lane 0 alone,
+    // and left to itself the compiler sinks the whole second division (a dozen dependent fp64 instructions) under that store's EXEC
+    // region, behind the first division and the store of v: one after the other instead of side by side (the finding of
+    // crawford.hip::rq4_step).  The empty statement is a use of tau in all lanes that cannot be sunk.
+    asm volatile("" : "+v"(tq));
+    const double vl = j == 0 ? 1.0 : x0 * scale;
+    Lw[xw + j] = vl;
     if (j == 0) Lw[xw + B] = tq;
     ldsb(Lw, hx) = j == 0 ? beta : 0.0;                                 // hx: a byte offset
+    vlo = vl; tqo = tq;
+}
+template <int B>
+__device__ __forceinline__ void next_reflector(double *Lw, const double x0, const int j, const int xw, const int hx)
+{
+    double vl, tq;
+    next_reflector<B>(Lw, x0, j, xw, hx, vl, tq);
+}
+
+// ---- the reflector and z as OPERANDS of the FMAs (tiles of 8, BSP_SBR_XDPP).  Lane i of an item holds component i of the reflector
+// (vl = slot[j]) and of z; what the LDS forms read as v[i] and zz[i] is a broadcast inside the 8 lanes that own the item.  DPP's
+// row_newbcast:I hands lane I of a DPP row to the row's 16 lanes and is the one DPP control that 64-bit instructions take
+// (crawford.hip uses it the same way), and an item is HALF a DPP row: every broadcast is two instructions, row_newbcast:i written to
+// lanes 0 .. 7 of the row (bank_mask:0x3) and row_newbcast:8+i written to lanes 8 .. 15 (bank_mask:0xc); the lanes a bank mask
+// leaves out keep their destination, which for v_fmac is the accumulator.  The products and the single rounding of each FMA are
+// those of the LDS forms: the same bits.  gfx950 has no DPP form of v_mul_f64 (it is VOP3 only), so the partial sums that open with
+// a product, y_k = v[k] * d[k], accumulate onto -0.0: fma(a, b, -0.0) is a * b rounded once for every a and b, zeros of either
+// sign included (onto +0.0 a product of -0.0 would come out +0.0).
+// The compiler does not form these instructions: inline assembly, and the wait states are ours.  HAZARD RULE: a DPP instruction
+// reads a register -- its DPP source, AND ITS DESTINATION when a mask leaves lanes out: those lanes are written back with what was
+// read -- no sooner than 2 wait states after a VALU instruction wrote it (5 after a VALU write of EXEC).  Measured
+// (profiles/r24_chase8_dpp.txt): a masked DPP FMA directly behind an instruction that wrote its accumulator puts the accumulator's
+// OLD value back into the lanes it leaves out; with one wait state in between it does not.  So: every statement opens with
+// `s_nop 1` (the producers are compiler code in front of it); inside a statement no instruction writes a register that a later one
+// reads by DPP (the DPP sources are vl and z, the destinations sums and tile elements); and the two halves of a broadcast are NOT
+// neighbours: a statement runs through all its lower halves first, then through all its upper halves, and no accumulator comes
+// up again with fewer than two instructions in between.  tests/test_host_chase8_dpp.py walks the assembly for all of it.  Not volatile: outputs only.
+#define XD_PAD "s_nop 1\n\t"
+#define XD_LO " row_mask:0xf bank_mask:0x3\n\t"
+#define XD_HI " row_mask:0xf bank_mask:0xc\n\t"
+// a_k += bcast_k(s) * m, lower / upper half of the row (m may carry a sign)
+#define XD_FL(k, s, m) "v_fmac_f64_dpp %[a" #k "], %[" #s "], " m " row_newbcast:" #k XD_LO
+#define XD_FH(k, s, m) "v_fmac_f64_dpp %[a" #k "], %[" #s "], " m " row_newbcast:%[u" #k "]" XD_HI
+// y_(k & 3) += bcast_k(vl) * x_k
+#define XD_DL(y, k) "v_fmac_f64_dpp %[y" #y "], %[vl], %[x" #k "] row_newbcast:" #k XD_LO
+#define XD_DH(y, k) "v_fmac_f64_dpp %[y" #y "], %[vl], %[x" #k "] row_newbcast:%[u" #k "]" XD_HI
+#define XD_U [u0] "i"(8), [u1] "i"(9), [u2] "i"(10), [u3] "i"(11), [u4] "i"(12), [u5] "i"(13), [u6] "i"(14), [u7] "i"(15)
+#define XD_A(k) [a##k] "+v"(a[k])
+#define XD_F7(s, m) XD_FL(1, s, m) XD_FL(2, s, m) XD_FL(3, s, m) XD_FL(4, s, m) XD_FL(5, s, m) XD_FL(6, s, m) XD_FL(7, s, m) \
+                    XD_FH(1, s, m) XD_FH(2, s, m) XD_FH(3, s, m) XD_FH(4, s, m) XD_FH(5, s, m) XD_FH(6, s, m) XD_FH(7, s, m)
+#define XD_F8(s, m) XD_FL(0, s, m) XD_FL(1, s, m) XD_FL(2, s, m) XD_FL(3, s, m) XD_FL(4, s, m) XD_FL(5, s, m) XD_FL(6, s, m) XD_FL(7, s, m) \
+                    XD_FH(0, s, m) XD_FH(1, s, m) XD_FH(2, s, m) XD_FH(3, s, m) XD_FH(4, s, m) XD_FH(5, s, m) XD_FH(6, s, m) XD_FH(7, s, m)
+
+// v^T x inside a lane as ((y0 + y1) + (y2 + y3)), the partial sums term for term those of the LDS forms: y0 = x[0] (v[0] = 1),
+// y_k = v[k] x[k] (k = 1, 2, 3), y_(k & 3) = fma(v[k], x[k], y_(k & 3)) (k = 4 .. 7)
+__device__ __forceinline__ double xd_dot(const double vl, const double (&x)[8])
+{
+    double y0 = x[0], y1 = -0.0, y2 = -0.0, y3 = -0.0;
+    asm(XD_PAD XD_DL(1, 1) XD_DL(2, 2) XD_DL(3, 3) XD_DL(0, 4) XD_DL(1, 5) XD_DL(2, 6) XD_DL(3, 7)
+        XD_DH(1, 1) XD_DH(2, 2) XD_DH(3, 3) XD_DH(0, 4) XD_DH(1, 5) XD_DH(2, 6) XD_DH(3, 7)
+        : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [y3] "+v"(y3)
+        : [vl] "v"(vl), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]), [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]), XD_U);
+    return (y0 + y1) + (y2 + y3);
+}
+// a[i] = fma(-c, v[i], a[i]), i = FROM .. 7, as a[i] += bcast_i(vl) * (-c)
+template <int FROM>
+__device__ __forceinline__ void xd_axpy(double (&a)[8], const double vl, const double c)
+{
+    static_assert(FROM == 0 || FROM == 1, "the whole tile, or all but its first element");
+    if constexpr (FROM == 0)
+        asm(XD_PAD XD_F8(s, "-%[c]") : XD_A(0), XD_A(1), XD_A(2), XD_A(3), XD_A(4), XD_A(5), XD_A(6), XD_A(7) : [s] "v"(vl), [c] "v"(c), XD_U);
+    else
+        asm(XD_PAD XD_F7(s, "-%[c]") : XD_A(1), XD_A(2), XD_A(3), XD_A(4), XD_A(5), XD_A(6), XD_A(7) : [s] "v"(vl), [c] "v"(c), XD_U);
+}
+// role 1's update: a[i] = fma(-z_i, vl, INNER ? fma(-v_i, z, a[i]) : a[i]), i = 0 .. 7.  One statement: both DPP sources (vl, z) are
+// written in front of it
+template <bool INNER>
+__device__ __forceinline__ void xd_rank2(double (&a)[8], const double vl, const double z)
+{
+    if constexpr (INNER)
+        asm(XD_PAD XD_F8(vl, "-%[z]") XD_F8(z, "-%[vl]") : XD_A(0), XD_A(1), XD_A(2), XD_A(3), XD_A(4), XD_A(5), XD_A(6), XD_A(7)
+            : [vl] "v"(vl), [z] "v"(z), XD_U);
+    else
+        asm(XD_PAD XD_F8(z, "-%[vl]") : XD_A(0), XD_A(1), XD_A(2), XD_A(3), XD_A(4), XD_A(5), XD_A(6), XD_A(7) : [vl] "v"(vl), [z] "v"(z), XD_U);
 }
 
 // Window BYTE offset of the element (r0 + B + j, r0 + i) of an item's next tile, i = 0 .. B - 1, as base[i] + 8 (WR - 1) i: the column
@@ -887,72 +978,123 @@ __device__ __forceinline__ void diag_tile_addr(const int r0, const int j, const 
     for (int i = 0; i < B; ++i) ad[i] = ((!FAST && i >= iw) ? udq : ud) + offD[i];
 }
 
-// role 0, the arithmetic of an item: next tile bt (lane j = row j) <- bt H, the reflector of its first column for the next item
-template <int B>
-__device__ __forceinline__ void chase4_next(double *Lw, double (&bt)[B], const double (&v)[B], const double tq, const int (&at)[B],
+// role 0, the arithmetic of an item: next tile bt (lane j = row j) <- bt H, the reflector of its first column for the next item.
+// XD: v by DPP from vl, this lane's component (B = 8); bt then holds the updated tile.  (vl, tq) leave as the next item's.
+template <int B, bool XD>
+__device__ __forceinline__ void chase4_next(double *Lw, double (&bt)[B], const double (&v)[B], double &vl, double &tq, const int (&at)[B],
                                             const int j, const int xw)
 {
-    double y0 = bt[0], y1 = v[1] * bt[1], y2 = v[2] * bt[2], y3 = v[3] * bt[3];
+    if constexpr (XD) {
+        static_assert(B == 8, "the DPP forms are built for tiles of 8");
+        const double ct = tq * xd_dot(vl, bt);
+        const double x0 = bt[0] - ct;
+        xd_axpy<1>(bt, vl, ct);
+        next_reflector<B>(Lw, x0, j, xw, at[0], vl, tq);
 #pragma unroll
-    for (int i = 4; i < B; i += 4) {
-        y0 = fma(v[i], bt[i], y0); y1 = fma(v[i + 1], bt[i + 1], y1);
-        y2 = fma(v[i + 2], bt[i + 2], y2); y3 = fma(v[i + 3], bt[i + 3], y3);
+        for (int i = 1; i < B; ++i) ldsb(Lw, at[i] + (Rw<B>::WR - 1) * 8 * i) = bt[i];
+    } else {
+        double y0 = bt[0], y1 = v[1] * bt[1], y2 = v[2] * bt[2], y3 = v[3] * bt[3];
+#pragma unroll
+        for (int i = 4; i < B; i += 4) {
+            y0 = fma(v[i], bt[i], y0); y1 = fma(v[i + 1], bt[i + 1], y1);
+            y2 = fma(v[i + 2], bt[i + 2], y2); y3 = fma(v[i + 3], bt[i + 3], y3);
+        }
+        const double ct = tq * ((y0 + y1) + (y2 + y3));
+        next_reflector<B>(Lw, bt[0] - ct, j, xw, at[0]);                 // B'(j, 0): element j of the next item's column
+#pragma unroll
+        for (int i = 1; i < B; ++i) ldsb(Lw, at[i] + (Rw<B>::WR - 1) * 8 * i) = fma(-ct, v[i], bt[i]);
     }
-    const double ct = tq * ((y0 + y1) + (y2 + y3));
-    next_reflector<B>(Lw, bt[0] - ct, j, xw, at[0]);                 // B'(j, 0): element j of the next item's column
-#pragma unroll
-    for (int i = 1; i < B; ++i) ldsb(Lw, at[i] + (Rw<B>::WR - 1) * 8 * i) = fma(-ct, v[i], bt[i]);
 }
 
-// role 1: diagonal tile d (lane j = column j) <- H d H; (v, tau) from slot xr
-template <int B>
+// role 1: diagonal tile d (lane j = column j) <- H d H; (v, tau) from slot xr.
+// XD (B = 8; BSP_SBR_XDPP): 0 = v and z through LDS; 1 = z stays in its lane and reaches the outer FMA by DPP (the round trip
+// through the Z region -- a transposition inside the item's 8 lanes -- leaves the chain); 2 = v as well: the role reads its own
+// component vl and tau and nothing else of the slot.
+// ABS: ad[] and dumpb are LDS addresses (ldsa), not offsets into the window.  dumpb: this item's dump, in bytes.
+template <int B, int XD, bool ABS>
 __device__ __forceinline__ void chase4_diag(double *Lw, const double (&d)[B], const int (&ad)[B], const int j, const int xr,
-                                            const int zi, const int dumpi)
+                                            const int zi, const int dumpb)
 {
-    double v[B];
+    if constexpr (XD >= 2) {
+        static_assert(B == 8, "the DPP forms are built for tiles of 8");
+        const double tq = Lw[xr + B], vl = Lw[xr + j];
+        const double p = tq * xd_dot(vl, d);
+        const double vtp = rsumB<B>(vl * p);
+        const double z = fma(-(0.5 * tq * vtp), vl, p);
+        double a[B];
 #pragma unroll
-    for (int i = 0; i < B; ++i) v[i] = Lw[xr + i];
-    const double tq = Lw[xr + B], vl = Lw[xr + j];
-    double y0 = d[0], y1 = v[1] * d[1], y2 = v[2] * d[2], y3 = v[3] * d[3];
+        for (int i = 0; i < B; ++i) a[i] = d[i];
+        xd_rank2<true>(a, vl, z);
 #pragma unroll
-    for (int i = 4; i < B; i += 4) {
-        y0 = fma(v[i], d[i], y0); y1 = fma(v[i + 1], d[i + 1], y1);
-        y2 = fma(v[i + 2], d[i + 2], y2); y3 = fma(v[i + 3], d[i + 3], y3);
+        for (int i = 0; i < B; ++i) ldsx<ABS>(Lw, i >= j ? ad[i] : dumpb + 8 * i) = a[i];
+    } else {
+        double v[B];
+#pragma unroll
+        for (int i = 0; i < B; ++i) v[i] = Lw[xr + i];
+        const double tq = Lw[xr + B], vl = Lw[xr + j];
+        double y0 = d[0], y1 = v[1] * d[1], y2 = v[2] * d[2], y3 = v[3] * d[3];
+#pragma unroll
+        for (int i = 4; i < B; i += 4) {
+            y0 = fma(v[i], d[i], y0); y1 = fma(v[i + 1], d[i + 1], y1);
+            y2 = fma(v[i + 2], d[i + 2], y2); y3 = fma(v[i + 3], d[i + 3], y3);
+        }
+        const double p = tq * ((y0 + y1) + (y2 + y3));
+        const double vtp = rsumB<B>(vl * p);
+        const double z = fma(-(0.5 * tq * vtp), vl, p);
+        if constexpr (XD == 1) {
+            static_assert(B == 8, "the DPP forms are built for tiles of 8");
+            double a[B];
+#pragma unroll
+            for (int i = 0; i < B; ++i) a[i] = fma(-v[i], z, d[i]);
+            xd_rank2<false>(a, vl, z);
+#pragma unroll
+            for (int i = 0; i < B; ++i) ldsx<ABS>(Lw, i >= j ? ad[i] : dumpb + 8 * i) = a[i];
+        } else {
+            Lw[zi + j] = z;
+            double zz[B];
+#pragma unroll
+            for (int i = 0; i < B; ++i) zz[i] = Lw[zi + i];
+            // the lower triangle is what the band stores; the mirrored values go to the dump (a select on the address, no branch)
+#pragma unroll
+            for (int i = 0; i < B; ++i) ldsx<ABS>(Lw, i >= j ? ad[i] : dumpb + 8 * i) = fma(-zz[i], vl, fma(-v[i], z, d[i]));
+        }
     }
-    const double p = tq * ((y0 + y1) + (y2 + y3));
-    const double vtp = rsumB<B>(vl * p);
-    const double z = fma(-(0.5 * tq * vtp), vl, p);
-    Lw[zi + j] = z;
-    double zz[B];
-#pragma unroll
-    for (int i = 0; i < B; ++i) zz[i] = Lw[zi + i];
-    // the lower triangle is what the band stores; the mirrored values go to the dump (a select on the address, no branch)
-#pragma unroll
-    for (int i = 0; i < B; ++i) ldsb(Lw, i >= j ? ad[i] : (dumpi + i) * 8) = fma(-zz[i], vl, fma(-v[i], z, d[i]));
 }
 
 // role 2: bulge tile of item (r0, c0): column c0 + j, rows r0 .. r0 + B - 1 (contiguous; no wrap inside a lane).  Column 0 holds
-// (beta, 0, .., 0) already: lane 0 works on the dump
-template <int B>
+// (beta, 0, .., 0) already: lane 0 works on the dump.  XD: v by DPP from this lane's component
+template <int B, bool XD>
 __device__ __forceinline__ void chase4_bulge(double *Lw, const int r0, const int c0, const int j, const int xr, const int dumpi)
 {
-    double v[B], b[B];
-#pragma unroll
-    for (int i = 0; i < B; ++i) v[i] = Lw[xr + i];
-    const double tq = Lw[xr + B];
+    double b[B];
     int ab = (((c0 + j) & (WCOLS - 1)) << Rw<B>::WSH) + (r0 - c0 - j);
     if (j == 0) ab = dumpi;
+    if constexpr (XD) {
+        static_assert(B == 8, "the DPP forms are built for tiles of 8");
+        const double tq = Lw[xr + B], vl = Lw[xr + j];
 #pragma unroll
-    for (int i = 0; i < B; ++i) b[i] = Lw[ab + i];
-    double w0 = b[0], w1 = v[1] * b[1], w2 = v[2] * b[2], w3 = v[3] * b[3];
+        for (int i = 0; i < B; ++i) b[i] = Lw[ab + i];
+        const double cb = tq * xd_dot(vl, b);
+        xd_axpy<0>(b, vl, cb);
 #pragma unroll
-    for (int i = 4; i < B; i += 4) {
-        w0 = fma(v[i], b[i], w0); w1 = fma(v[i + 1], b[i + 1], w1);
-        w2 = fma(v[i + 2], b[i + 2], w2); w3 = fma(v[i + 3], b[i + 3], w3);
+        for (int i = 0; i < B; ++i) Lw[ab + i] = b[i];
+    } else {
+        double v[B];
+#pragma unroll
+        for (int i = 0; i < B; ++i) v[i] = Lw[xr + i];
+        const double tq = Lw[xr + B];
+#pragma unroll
+        for (int i = 0; i < B; ++i) b[i] = Lw[ab + i];
+        double w0 = b[0], w1 = v[1] * b[1], w2 = v[2] * b[2], w3 = v[3] * b[3];
+#pragma unroll
+        for (int i = 4; i < B; i += 4) {
+            w0 = fma(v[i], b[i], w0); w1 = fma(v[i + 1], b[i + 1], w1);
+            w2 = fma(v[i + 2], b[i + 2], w2); w3 = fma(v[i + 3], b[i + 3], w3);
+        }
+        const double cb = tq * ((w0 + w1) + (w2 + w3));
+#pragma unroll
+        for (int i = 0; i < B; ++i) Lw[ab + i] = fma(-cb, v[i], b[i]);
     }
-    const double cb = tq * ((w0 + w1) + (w2 + w3));
-#pragma unroll
-    for (int i = 0; i < B; ++i) Lw[ab + i] = fma(-cb, v[i], b[i]);
 }
 
 // Rows and columns of the band storage beyond the matrix are made zero before the rows kernel runs (wr = the rows of its window
@@ -1052,10 +1194,16 @@ __device__ __forceinline__ void mover_step(double *Lw, double *__restrict__ AB, 
 // (the tile) = 12 in the general and the wrapping body and 4 + 4 ds_read2_b64 = 8 in the plain steady body, where the tile's addresses
 // are one register and immediates and the loads pair up.  8 is the least the count of 7 allows: whoever makes these loads wider
 // lowers the count with them.
-template <int B>
+// NLOADS: the load instructions behind the wave's last store, at least, in every body that reaches this barrier (0 = the counts above).
+// With the reflector by DPP in role 0 (BSP_SBR_XDPP=3) the (v, tau) loads are gone.  Re-read in the code as compiled: behind its last
+// store role 0 then has 8 ds_read_b64 (the tile) in the general and the wrapping body and 4 ds_read2_b64 in the plain steady body, so
+// its barriers wait with a count of 3.  Role 1 reads the slot after the barrier and keeps its 8 ds_read_b64 in every body and setting.
+template <int B, int NLOADS = 0>
 __device__ __forceinline__ void stores_done_barrier()
 {
-    if (B == 16) asm volatile("s_waitcnt lgkmcnt(15)\n\ts_barrier" ::: "memory");
+    static_assert(NLOADS >= 0 && NLOADS <= 16, "lgkmcnt is a four-bit counter");
+    if (NLOADS > 0) asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" ::"n"(NLOADS - 1) : "memory");
+    else if (B == 16) asm volatile("s_waitcnt lgkmcnt(15)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt lgkmcnt(7)\n\ts_barrier" ::: "memory");
 }
 
@@ -1105,7 +1253,11 @@ __device__ __forceinline__ void mover_pass(double *Lw, double *__restrict__ AB, 
 // 64-bit mask built once per pass (the ring is 512 columns, a tile advances 8 per step: the pattern repeats every 64 steps).  The
 // arithmetic of a step (chase4_*) and every address it uses are those of the general body: bit-identical results.
 constexpr int SBR_PASSDIAG = 256;                        // per-pass stamps of workgroup 0 behind the 45 per-wave ones, four words each
-template <int B, bool DIAG, bool PHASED>
+// XDPP (B = 8, the phased loop; BSP_SBR_XDPP): what reaches the FMAs by DPP instead of through LDS -- 0 nothing, 1 role 1's z, 2 role 1's
+// reflector as well (the default: role 1 is the wave with an LDS round trip on its chain to lose), 3 the reflector in roles 0 and 2
+// too (role 0 then keeps (v, tau) of its next item in registers: it has just formed them; no faster than 2 at 128 channels and
+// slower than 0 at 16, where twice the FMAs weigh more than the LDS instructions saved).  The same bits in every setting (chase4_*).
+template <int B, bool DIAG, bool PHASED, int XDPP>
 __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double *__restrict__ ABall, double *__restrict__ dall,
                                               double *__restrict__ eall, long long *diag, Sb16Ctl *ctl, int P, int *status,
                                               int force_abort, int lagmode)
@@ -1114,8 +1266,15 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
     constexpr int WSH = W::WSH, WR = W::WR, RPW = W::RPW, NSW = W::NSW, MLAG = W::MLAG, LP0 = W::LP0;
     constexpr int RINGB = WCOLS * WR * 8, STEPB = B * WR * 8;   // bytes of the ring of window columns, of the B columns a tile advances per step
     static_assert(!PHASED || B == 8, "the phased step loop is built for tiles of 8");
+    static_assert(XDPP >= 0 && XDPP <= 3 && (XDPP == 0 || B == 8), "the DPP forms are built for tiles of 8");
+    constexpr bool XD0 = XDPP >= 3;                        // roles 0 and 2: the reflector by DPP
+    // the phased instance: role 1's tile addresses are LDS addresses (ldsa): the window's own address goes once per pass into the lane
+    // constants they are formed from.  (Role 0's plain steady body has two such adds, the bases of its stores and of its loads: a running
+    // address would save one of them for a register the instrumented instance does not have.)
+    constexpr bool ABS = PHASED;
     extern __shared__ double lds[];
     double *Lw = lds;
+    const int lb = ABS ? lds_addr(Lw) : 0;
     // the whole batch waits for the slowest channel: first on a SIMD shared with a long-running wave of another kernel (as the band
     // reduction's waves, crawford.hip)
     __builtin_amdgcn_s_setprio(3);
@@ -1242,14 +1401,18 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                 }
             }
             if (role == 0) {
-                double bt[B], v[B], tq = 0.0;
+                double bt[B], v[B], tq = 0.0, vl = 0.0;    // vl: this lane's component of v (XD0: it stands for v)
                 int at[B];
                 for (int i = 0; i < B; ++i) { bt[i] = 0.0; v[i] = 0.0; at[i] = 0; }
                 if (sw == 0 && live && s4 + 1 < n) {      // item (s0, 0) runs at step 0
                     next_tile_addr<B, false>(s4 + 1, j, at);
 #pragma unroll
-                    for (int i = 0; i < B; ++i) { bt[i] = ldsb(Lw, at[i] + (WR - 1) * 8 * i); v[i] = Lw[xs0 + i]; }
+                    for (int i = 0; i < B; ++i) {
+                        bt[i] = ldsb(Lw, at[i] + (WR - 1) * 8 * i);
+                        if (!XD0) v[i] = Lw[xs0 + i];
+                    }
                     tq = Lw[xs0 + B];
+                    if (XD0) vl = Lw[xs0 + j];
                 }
                 __syncthreads();
                 auto general_step = [&](const int t) {
@@ -1258,10 +1421,11 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                     const bool act = k4 >= 0 && live && r04 < n, actN = k4 >= -1 && live && r04 + B < n;
                     const int xw = xs0 + (((t + 1) & 1) << 8);
                     if (act) {
-                        chase4_next<B>(Lw, bt, v, tq, at, j, xw);
+                        chase4_next<B, XD0>(Lw, bt, v, vl, tq, at, j, xw);
                     } else if (k4 == -1 && live) {        // the sweep starts in the next step: its reflector from the band column
                         const int hx = ((s4 & (WCOLS - 1)) << WSH) + 1 + j;
-                        next_reflector<B>(Lw, Lw[hx], j, xw, hx * 8);
+                        if (XD0) next_reflector<B>(Lw, Lw[hx], j, xw, hx * 8, vl, tq);
+                        else next_reflector<B>(Lw, Lw[hx], j, xw, hx * 8);
                     }
                     // for the next step: (v, tau) back from the slot, the next item's tile (general addresses for the whole wave
                     // if the tile of one of its items wraps around the ring)
@@ -1269,14 +1433,16 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                     if (actN) {
                         if (wrapN) next_tile_addr<B, false>(r04 + B, j, at);
                         else next_tile_addr<B, true>(r04 + B, j, at);
+                        if (!XD0) {                       // XD0: (vl, tq) of the next item are in registers, act or k4 == -1 has formed them
 #pragma unroll
-                        for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
-                        tq = Lw[xw + B];
+                            for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
+                            tq = Lw[xw + B];
+                        }
 #pragma unroll
                         for (int i = 0; i < B; ++i) bt[i] = ldsb(Lw, at[i] + (WR - 1) * 8 * i);
                     }
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
-                    if (__builtin_amdgcn_ballot_w64(actN) != 0) stores_done_barrier<B>();
+                    if (__builtin_amdgcn_ballot_w64(actN) != 0) stores_done_barrier<B, XD0 ? 4 : 0>();   // XD0: the tile's loads alone
                     else lds_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
                 };
@@ -1292,11 +1458,13 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                             int af[B];
 #pragma unroll
                             for (int i = 0; i < B; ++i) af[i] = a0;
-                            chase4_next<B>(Lw, bt, v, tq, af, j, xw);
+                            chase4_next<B, XD0>(Lw, bt, v, vl, tq, af, j, xw);
                             a0 = (a0 + STEPB) & (RINGB - 1);
+                            if (!XD0) {
 #pragma unroll
-                            for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
-                            tq = Lw[xw + B];
+                                for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
+                                tq = Lw[xw + B];
+                            }
 #pragma unroll
                             for (int i = 0; i < B; ++i) bt[i] = ldsb(Lw, a0 + (WR - 1) * 8 * i);
                             asm volatile("; plain step" ::: "memory");      // two texts: the bodies stay apart (merged, the loads would go
@@ -1304,19 +1472,21 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                             int ag[B];
                             const int r04 = r04b + B * t;
                             next_tile_addr<B, false>(r04, j, ag);
-                            chase4_next<B>(Lw, bt, v, tq, ag, j, xw);
+                            chase4_next<B, XD0>(Lw, bt, v, vl, tq, ag, j, xw);
                             next_tile_addr<B, false>(r04 + B, j, ag);
                             a0 = (a0 + STEPB) & (RINGB - 1);
+                            if (!XD0) {
 #pragma unroll
-                            for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
-                            tq = Lw[xw + B];
+                                for (int i = 0; i < B; ++i) v[i] = Lw[xw + i];
+                                tq = Lw[xw + B];
+                            }
 #pragma unroll
                             for (int i = 0; i < B; ++i) bt[i] = ldsb(Lw, ag[i] + (WR - 1) * 8 * i);
                             asm volatile("; wrapping step" ::: "memory");
                         }
                         xw ^= 256;
                         if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
-                        stores_done_barrier<B>();            // every item has a successor: the loads are behind the stores in both bodies
+                        stores_done_barrier<B, XD0 ? 4 : 0>();   // every item has a successor: the loads are behind the stores in both bodies
                         if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
                     }
                     next_tile_addr<B, false>(r04b + B * tB, j, at);      // the tiles fetched in the last steady step, for the general body
@@ -1329,24 +1499,25 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                 // would hold registers in all of them, and the phased instance has none to spare beside two workgroups per CU
                 int jo = j;
                 if (PHASED) asm volatile("" : "+v"(jo));
-                for (int i = 0; i < B; ++i) { d[i] = 0.0; ad[i] = 0; offD[i] = (i >= jo ? (WR - 1) * jo + i : (WR - 1) * i + jo) * 8; }
+                for (int i = 0; i < B; ++i) { d[i] = 0.0; ad[i] = 0; offD[i] = (i >= jo ? (WR - 1) * jo + i : (WR - 1) * i + jo) * 8 + lb; }
+                const int dumpb = dumpi * 8 + lb;
                 if (sw == 0 && live && s4 + 1 < n) {
                     diag_tile_addr<B, false>(s4 + 1, j, offD, ad);
 #pragma unroll
-                    for (int i = 0; i < B; ++i) d[i] = ldsb(Lw, ad[i]);
+                    for (int i = 0; i < B; ++i) d[i] = ldsx<ABS>(Lw, ad[i]);
                 }
                 __syncthreads();
                 auto general_step = [&](const int t) {
                     if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
                     const int k4 = t - LAG * sw, r04 = r04b + B * t;
                     const bool act = k4 >= 0 && live && r04 < n, actN = k4 >= -1 && live && r04 + B < n;
-                    if (act) chase4_diag<B>(Lw, d, ad, j, xs0 + ((t & 1) << 8), zi, dumpi);
+                    if (act) chase4_diag<B, XDPP < 2 ? XDPP : 2, ABS>(Lw, d, ad, j, xs0 + ((t & 1) << 8), zi, dumpb);
                     const bool wrapN = __builtin_amdgcn_ballot_w64(actN && ((r04 + B) & (WCOLS - 1)) > WCOLS - B) != 0;
                     if (actN) {
                         if (wrapN) diag_tile_addr<B, false>(r04 + B, j, offD, ad);
                         else diag_tile_addr<B, true>(r04 + B, j, offD, ad);
 #pragma unroll
-                        for (int i = 0; i < B; ++i) d[i] = ldsb(Lw, ad[i]);
+                        for (int i = 0; i < B; ++i) d[i] = ldsx<ABS>(Lw, ad[i]);
                     }
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
                     if (__builtin_amdgcn_ballot_w64(actN) != 0) stores_done_barrier<B>();
@@ -1360,7 +1531,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                     int xr = xs0 + ((tA & 1) << 8);
                     for (int t = tA; t < tB; ++t) {
                         if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
-                        chase4_diag<B>(Lw, d, ad, j, xr, zi, dumpi);
+                        chase4_diag<B, XDPP < 2 ? XDPP : 2, ABS>(Lw, d, ad, j, xr, zi, dumpb);
                         ud = (ud + STEPB) & (RINGB - 1);
                         if ((wmask >> (t & 63)) & 1) {
                             diag_tile_addr<B, false>(r04b + B * (t + 1), j, offD, ad);
@@ -1372,7 +1543,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                             asm volatile("; plain step" : "+v"(ad[0]), "+v"(ad[1]), "+v"(ad[2]), "+v"(ad[3]), "+v"(ad[4]), "+v"(ad[5]), "+v"(ad[6]), "+v"(ad[7]));
                         }
 #pragma unroll
-                        for (int i = 0; i < B; ++i) d[i] = ldsb(Lw, ad[i]);
+                        for (int i = 0; i < B; ++i) d[i] = ldsx<ABS>(Lw, ad[i]);
                         xr ^= 256;
                         if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
                         stores_done_barrier<B>();
@@ -1385,7 +1556,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                 auto general_step = [&](const int t) {
                     if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
                     const int k4 = t - LAG * sw, r04 = r04b + B * t;
-                    if (k4 > 0 && live && r04 < n) chase4_bulge<B>(Lw, r04, r04 - B, j, xs0 + ((t & 1) << 8), dumpi);
+                    if (k4 > 0 && live && r04 < n) chase4_bulge<B, XD0>(Lw, r04, r04 - B, j, xs0 + ((t & 1) << 8), dumpi);
                     if (DIAG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
                     lds_barrier();
                     if (DIAG) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[3] += t_ - dt0; dacc[4] += 1; }
@@ -1397,7 +1568,7 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
                     int r04 = r04b + B * tA2, xr = xs0 + ((tA2 & 1) << 8);
                     for (int t = tA2; t < tB; ++t) {
                         if (DIAG) dt0 = (long long)__builtin_amdgcn_s_memtime();
-                        chase4_bulge<B>(Lw, r04, r04 - B, j, xr, dumpi);
+                        chase4_bulge<B, XD0>(Lw, r04, r04 - B, j, xr, dumpi);
                         r04 += B; xr ^= 256;
                         if (DIAG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = (long long)__builtin_amdgcn_s_memtime(); dacc[2] += t_ - dt0; dt0 = t_; }
                         lds_barrier();
@@ -1444,12 +1615,24 @@ __device__ __forceinline__ void sbr_rows_body(int n, int npad, int batch, double
 template <int B, bool DIAG = false>
 __global__ __launch_bounds__(SB16R_THREADS) __attribute__((amdgpu_waves_per_eu(B == 8 ? 4 : 2))) void sbr_rows_kernel(SBR_ROWS_ARGS)
 {
-    sbr_rows_body<B, DIAG, B == 8>(n, npad, batch, ABall, dall, eall, diag, ctl, P, status, force_abort, lagmode);
+    sbr_rows_body<B, DIAG, B == 8, B == 8 ? SBR_XDPP_DEFAULT : 0>(n, npad, batch, ABall, dall, eall, diag, ctl, P, status, force_abort, lagmode);
+}
+// tiles of 8, the phased loop with another setting of BSP_SBR_XDPP than the default's
+template <bool DIAG, int XDPP>
+__global__ __launch_bounds__(SB16R_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void sbr_rows_xdpp_kernel(SBR_ROWS_ARGS)
+{
+    sbr_rows_body<8, DIAG, true, XDPP>(n, npad, batch, ABall, dall, eall, diag, ctl, P, status, force_abort, lagmode);
 }
 template <int B, bool DIAG = false>
 __global__ __launch_bounds__(SB16R_THREADS) __attribute__((amdgpu_waves_per_eu(B == 8 ? 4 : 2))) void sbr_rows_general_kernel(SBR_ROWS_ARGS)
 {
-    sbr_rows_body<B, DIAG, false>(n, npad, batch, ABall, dall, eall, diag, ctl, P, status, force_abort, lagmode);
+    sbr_rows_body<B, DIAG, false, 0>(n, npad, batch, ABall, dall, eall, diag, ctl, P, status, force_abort, lagmode);
+}
+template <bool DIAG, int XDPP>
+auto sbr_rows8_kernel()
+{
+    if constexpr (XDPP == SBR_XDPP_DEFAULT) return &sbr_rows_kernel<8, DIAG>;
+    else return &sbr_rows_xdpp_kernel<DIAG, XDPP>;
 }
 #undef SBR_ROWS_ARGS
 
@@ -1500,8 +1683,14 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
         BSP_HIP(allow_lds(sb16st_kernel, SB16_LDS));
         BSP_HIP(allow_lds(sbr_rows_kernel<16, false>, Rw<16>::LDS));
         BSP_HIP(allow_lds(sbr_rows_kernel<16, true>, Rw<16>::LDS));
-        BSP_HIP(allow_lds(sbr_rows_kernel<8, false>, Rw<8>::LDS));
-        BSP_HIP(allow_lds(sbr_rows_kernel<8, true>, Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<false, 0>(), Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<true, 0>(), Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<false, 1>(), Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<true, 1>(), Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<false, 2>(), Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<true, 2>(), Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<false, 3>(), Rw<8>::LDS));
+        BSP_HIP(allow_lds(sbr_rows8_kernel<true, 3>(), Rw<8>::LDS));
         BSP_HIP(allow_lds(sbr_rows_general_kernel<8, false>, Rw<8>::LDS));
         BSP_HIP(allow_lds(sbr_rows_general_kernel<8, true>, Rw<8>::LDS));
         int nb = 0;
@@ -1540,15 +1729,27 @@ int launch_sb16st(int n, int npad, int batch, double *d_AB, double *d_d, double 
     const int fab = opts().sb2st_force_abort;
     const bool phased = opts().sbr_phased != 0;            // tiles of 8 only: the step loop in three parts / the lag of the data-moving wave
     const int lagmode = opts().sbr_lag;
+    const int xdpp = opts().sbr_xdpp < 0 ? 0 : (opts().sbr_xdpp > 3 ? 3 : opts().sbr_xdpp);   // the phased loop only: what goes by DPP
     auto launch = [&](long long *dbuf) {
         if (rows) hipLaunchKernelGGL(band_tail_zero_kernel, dim3(batch), dim3(256), 0, st, n, npad, 2 * hb, d_AB);
 #define SBR_LAUNCH(K, ...) hipLaunchKernelGGL((K<__VA_ARGS__>), dim3(nblk), dim3(SB16R_THREADS), Rw<8>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf, \
                                               d_ctl, P, d_status, fab, lagmode)
-        if (hb == 8 && dbuf && phased) SBR_LAUNCH(sbr_rows_kernel, 8, true);
-        else if (hb == 8 && dbuf) SBR_LAUNCH(sbr_rows_general_kernel, 8, true);
-        else if (hb == 8 && phased) SBR_LAUNCH(sbr_rows_kernel, 8, false);
-        else if (hb == 8) SBR_LAUNCH(sbr_rows_general_kernel, 8, false);
+#define SBR_LAUNCH8(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(SB16R_THREADS), Rw<8>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf, d_ctl, P, d_status, \
+                                          fab, lagmode)
+        if (hb == 8 && dbuf && phased) {
+            if (xdpp == 3) SBR_LAUNCH8((sbr_rows8_kernel<true, 3>()));
+            else if (xdpp == 2) SBR_LAUNCH8((sbr_rows8_kernel<true, 2>()));
+            else if (xdpp == 1) SBR_LAUNCH8((sbr_rows8_kernel<true, 1>()));
+            else SBR_LAUNCH8((sbr_rows8_kernel<true, 0>()));
+        } else if (hb == 8 && dbuf) SBR_LAUNCH(sbr_rows_general_kernel, 8, true);
+        else if (hb == 8 && phased) {
+            if (xdpp == 3) SBR_LAUNCH8((sbr_rows8_kernel<false, 3>()));
+            else if (xdpp == 2) SBR_LAUNCH8((sbr_rows8_kernel<false, 2>()));
+            else if (xdpp == 1) SBR_LAUNCH8((sbr_rows8_kernel<false, 1>()));
+            else SBR_LAUNCH8((sbr_rows8_kernel<false, 0>()));
+        } else if (hb == 8) SBR_LAUNCH(sbr_rows_general_kernel, 8, false);
 #undef SBR_LAUNCH
+#undef SBR_LAUNCH8
         else if (rows && dbuf)
             hipLaunchKernelGGL((sbr_rows_kernel<16, true>), dim3(nblk), dim3(SB16R_THREADS), Rw<16>::LDS, st, n, npad, batch, d_AB, d_d, d_e, dbuf,
                                d_ctl, P, d_status, fab, 1);
