@@ -42,6 +42,9 @@ EXPORTS = ["bspatom_input_defaults", "bspatom_device_count", "bspatom_host_setup
 # what include/bspatom_tdse_spline.h, the part of the header for the spline-basis TDSE, declares (EXPORTS is include/bspatom.h's own text)
 SPLINE_EXPORTS = ["bspatom_tdse_spline", "bspatom_tdse_spline_dev", "bspatom_tdse_spline_wide", "bspatom_tdse_spline_wide_dev"]
 
+# what include/bspatom_tdse_split.h, the part of the header for the split-step spline-basis TDSE, declares
+SPLIT_EXPORTS = ["bspatom_tdse_split", "bspatom_tdse_split_dev"]
+
 _lib = None
 
 
@@ -103,6 +106,8 @@ def lib():
         L.bspatom_tdse_spline_dev.argtypes = list(L.bspatom_tdse_spline.argtypes)
         L.bspatom_tdse_spline_wide.argtypes = list(L.bspatom_tdse_spline.argtypes)
         L.bspatom_tdse_spline_wide_dev.argtypes = list(L.bspatom_tdse_spline.argtypes)
+        L.bspatom_tdse_split.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, dbl, vp, vp, i32, vp, i32, i32, vp, vp, vp]
+        L.bspatom_tdse_split_dev.argtypes = list(L.bspatom_tdse_split.argtypes)
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -938,6 +943,59 @@ class Problem:
         _chk(getattr(lib(), entry)(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), 0 if cr is None else cr.size, _p(cr),
                                    _p(cc), _p(ctr), nop, _ptr(G_ptr), nsteps, float(dt), _ptr(coef_ptr), _ptr(c_ptr), snap_every,
                                    _ptr(snap_ptr), obs_every, nproj, _ptr(P_ptr), _ptr(obs_ptr), _p(info)), entry)
+        return info
+
+    def tdse_split(self, l, c0, dt, nsteps, G=None, Q=None, lam=None, f=None, W=None, w=None, P=None, obs_every=0, snap_every=0):
+        """nsteps split Crank-Nicolson steps dt of i S dc/dt = (sum_c (H_l[c] - i W_w[c]) + f(t) A (x) G) c in the B-spline basis
+        (bspatom_tdse_split): ONE operator term, A = Q diag(lam) Q^T the constant real symmetric angular matrix (host.split_angular), G
+        one full band (2k-1, nfun) (dipole_bands()[0] for the length gauge).  Every substep is nch independent systems of half-width
+        k - 1: the cost is linear in nch, and nch has no limit; k <= 16, else BspAtomError(-5).  l, w: (nch,); W as in tdse_spline; f:
+        COMPLEX (nsteps, nscan), the field at every step's MIDPOINT (host.spline_midpoints), broadcast from (nsteps,).  c0: complex
+        (nscan, nch, nfun) or (nch, nfun).  Returns what tdse_spline returns: (c, info), then obs if obs_every >= 1, then snaps if
+        snap_every >= 1, in its shapes.  Second order in dt like tdse_spline, not equal to it: another splitting of the same equation."""
+        n = self.nfun
+        W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
+        nabs = 0 if W is None else W.shape[0]
+        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
+        nch = l.size
+        w = None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), l.shape))
+        c = np.array(c0, dtype=np.complex128, order="C")
+        one = c.ndim == 2
+        c = np.ascontiguousarray(c.reshape(-1, nch, n))
+        nscan = c.shape[0]
+        G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(2 * self.k - 1, n))
+        Q = None if Q is None else np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(nch, nch))
+        lam = None if lam is None else np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(nch))
+        if f is not None and nsteps > 0:
+            f = np.asarray(f, dtype=np.complex128)
+            f = f[:, None] if f.ndim == 1 else f
+            assert f.ndim == 2 and f.shape[0] == nsteps, (f.shape, nsteps)
+            f = np.ascontiguousarray(np.broadcast_to(f, (nsteps, nscan)))
+        else:
+            f = None
+        P = None if P is None or obs_every < 1 else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, nch, n))
+        nproj = 0 if P is None else P.shape[0]
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, n), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj)) if obs_every > 0 else None
+        info = np.zeros(nscan, dtype=np.int32)
+        _chk(lib().bspatom_tdse_split(self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), _p(G), _p(Q), _p(lam), nsteps, float(dt), _p(f), _p(c),
+                                      snap_every, _p(snaps), obs_every, nproj, _p(P), _p(obs), _p(info)), "bspatom_tdse_split")
+        return (c[0] if one else c, info) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+
+    def tdse_split_dev(self, l, nscan, nsteps, dt, c_ptr, G_ptr=None, Q=None, lam=None, f_ptr=None, nabs=0, W_ptr=None, w=None, nproj=0,
+                       P_ptr=None, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None):
+        """tdse_split with the packets (nscan * nch * nfun complex at c_ptr, advanced in place), G, W, the field table (nsteps * nscan
+        complex), P, the rows and the snapshots in device memory of this problem's device, e.g. torch tensors' data_ptr(); l, w, Q and
+        lam are host values.  Returns info (nscan,) when the result is there."""
+        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
+        nch = l.size
+        w = None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), l.shape))
+        Q = None if Q is None else np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(nch, nch))
+        lam = None if lam is None else np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(nch))
+        info = np.zeros(nscan, dtype=np.int32)
+        _chk(lib().bspatom_tdse_split_dev(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), _ptr(G_ptr), _p(Q), _p(lam), nsteps, float(dt),
+                                          _ptr(f_ptr), _ptr(c_ptr), snap_every, _ptr(snap_ptr), obs_every, nproj, _ptr(P_ptr), _ptr(obs_ptr),
+                                          _p(info)), "bspatom_tdse_split_dev")
         return info
 
     def early_vector_state(self):

@@ -118,6 +118,7 @@ const OptName OPT_TABLE[] = {
     {"tdse_stage_mb", "BSP_TDSE_STAGE_MB", &Options::tdse_stage_mb},
     {"tdse_adapt_group", "BSP_TDSE_ADAPT_GROUP", &Options::tdse_adapt_group},
     {"tdse_spline_group", "BSP_TDSE_SPLINE_GROUP", &Options::tdse_spline_group},
+    {"tdse_split_group", "BSP_TDSE_SPLIT_GROUP", &Options::tdse_split_group},
 };
 }  // namespace
 

@@ -8,6 +8,7 @@
 //   bspatom_tdse_spline / _dev: Crank-Nicolson steps on the coupled LU (tdse_spline.hip); a call path of its own below (every packet
 //     has its own right-hand side and the steps follow each other), the screening and the scratch rules of the coupled call.
 //   bspatom_tdse_spline_wide / _dev: the same call on the blocked LU for wide bands (tdse_spline_wide.hip), through the same path.
+//   bspatom_tdse_split / _dev: split Crank-Nicolson steps, nch one-wave systems per substep (tdse_split.hip); a call path of its own.
 // The eight resolvent entry points run through resolvent_call: a front function per flavour screens what is particular to it, describes the call by
 // counts per ITEM (a matrix, a chain, a coupled matrix) and hands over its slot query and its launcher.
 #include <algorithm>
@@ -376,6 +377,160 @@ extern "C" int bspatom_tdse_spline_wide_dev(bspatom_problem *p, int nscan, int n
 {
     return tdse_spline_impl(p, nscan, nch, l, nabs, WB_dev, w, ncoup, cr, cc, ctr, nop, GB_dev, nsteps, dt, coef_dev, c_dev, snap_every,
                             snap_dev, obs_every, nproj, P_dev, obs_dev, info, true, true);
+}
+
+// bspatom_tdse_split / _dev: nsteps split Crank-Nicolson steps of nscan packets (tdse_split.hip).  A step is three launches over the
+// nscan * nch one-wave systems -- atomic half step, field step, atomic half step -- on two packet buffers that alternate; the atomic
+// matrices are factored once, one per distinct (l, w).  The launches of tdse_split_group steps are enqueued, then waited for; the host
+// variant stages f, the snapshots and the rows by groups of whole steps under tdse_stage_mb (one step at least); neither changes what
+// a step computes.
+static int tdse_split_impl(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w, const double *G,
+                           const double *Q, const double *lam, int nsteps, double dt, const double *f, double *c, int snap_every, double *snap,
+                           int obs_every, int nproj, const double *P, double *obs, int32_t *info, bool dev)
+{
+    if (!p || !l || !c || !info || nscan < 1 || nch < 1 || nsteps < 0 || nabs < 0 || nproj < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
+    if (!std::isfinite(dt) || !(dt > 0.0)) return BSP_ERR_ARG;
+    if (nsteps > 0 && (!G || !Q || !lam || !f)) return BSP_ERR_ARG;
+    if (snap_every < 0 || (snap && snap_every == 0)) return BSP_ERR_ARG;
+    if (obs_every < 0 || (obs_every == 0) != (obs == nullptr) || (obs && nproj > 0 && !P)) return BSP_ERR_ARG;
+    for (int ch = 0; ch < nch; ++ch) {
+        if (p->band_nl < 1 || l[ch] < p->band_l0 || l[ch] >= p->band_l0 + p->band_nl) return BSP_ERR_ARG;
+        if (w && (w[ch] < -1 || w[ch] >= nabs)) return BSP_ERR_ARG;
+    }
+    const int n = p->hs.nfun, k = p->hs.k;
+    if (k > tdse_split_max_k()) {
+        fprintf(stderr, "bspatom_tdse_split: k = %d exceeds the one-wave window's limit k <= %d\n", k, tdse_split_max_k());
+        return BSP_ERR_UNSUPPORTED;
+    }
+    if ((long long)nch * n > 0x3fffffffLL || (long long)nscan * nch > 0x3fffffffLL || (long long)nsteps * nscan > 0x3fffffffLL) return BSP_ERR_ARG;
+    const bool snapping = snap && snap_every > 0, observing = obs != nullptr;
+    if (!observing) nproj = 0;
+    const int items = nscan * nch;
+    const size_t N = (size_t)nch * n, wband = (size_t)(2 * k - 1) * n, RW = (size_t)nch + 2 * nproj;
+    const size_t f_step = (size_t)2 * nscan, snap_one = 2 * N * nscan, row_one = RW * nscan;   // doubles
+    BSP_HIP(hipSetDevice(p->device));
+    int rc, slots = 0;
+    if ((rc = tdse_split_slots(k, items, &slots))) return rc;
+    if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, items);
+    const size_t slot_doubles = tdse_split_slot_doubles(n, k), fac_doubles = tdse_split_factor_doubles(n, k);
+    const size_t rstage = opts().resolvent_stage_mb > 0 ? (size_t)opts().resolvent_stage_mb << 20 : RESOLVENT_STAGE_BYTES;
+    slots = (int)std::max<size_t>(1, std::min<size_t>(slots, rstage / (slot_doubles * sizeof(double))));
+    const int group = opts().tdse_split_group > 0 ? opts().tdse_split_group : SPLINE_GROUP;
+    // the host variant's staging groups: whole steps, a step counted with a snapshot and a row of its own (an upper bound)
+    int sgroup = std::max(nsteps, 1);
+    if (!dev) {
+        const size_t tstage = opts().tdse_stage_mb > 0 ? (size_t)opts().tdse_stage_mb << 20 : SPLINE_STAGE_BYTES;
+        const size_t per_step = (f_step + (snapping ? snap_one : 0) + (observing ? row_one : 0)) * sizeof(double);
+        sgroup = (int)std::max<size_t>(1, std::min<size_t>(sgroup, tstage / per_step));
+    }
+    const size_t gsnaps = snapping ? (size_t)sgroup / snap_every + 1 : 0, grows = observing ? (size_t)(sgroup - 1) / obs_every + 2 : 0;
+    // the channels, and the distinct (band, absorber) pairs among them in the order of their first appearance: one atomic matrix each
+    std::vector<int> chan(nch), wsel(nch, nabs > 0 && !w ? 0 : -1), fac(nch), fchan, fw;
+    for (int ch = 0; ch < nch; ++ch) {
+        chan[ch] = l[ch] - p->band_l0;
+        if (w) wsel[ch] = w[ch];
+        size_t at = 0;
+        while (at < fchan.size() && (fchan[at] != chan[ch] || fw[at] != wsel[ch])) ++at;
+        if (at == fchan.size()) { fchan.push_back(chan[ch]); fw.push_back(wsel[ch]); }
+        fac[ch] = (int)at;
+    }
+    const int nfac = (int)fchan.size();
+    DevArray<double> work, fstore, buf0, buf1, dQ, dlam, dpart, dWB, dG, dP, df, dsnap, dobs;
+    DevArray<int> dfac, dfchan, dfw, dfinfo, dpinfo;
+    if ((rc = work.alloc((size_t)slots * slot_doubles)) || (rc = fstore.alloc((size_t)nfac * fac_doubles)) || (rc = buf0.alloc(2 * N * nscan)) ||
+        (rc = buf1.alloc(2 * N * nscan)) || (rc = dpart.alloc((size_t)2 * nscan * nproj * nch)) ||
+        (rc = dfac.put(fac.data(), nch)) || (rc = dfchan.put(fchan.data(), nfac)) ||
+        (rc = dfw.put(fw.data(), nfac)) || (rc = dfinfo.alloc(nfac)) || (rc = dpinfo.alloc(items)) ||
+        (nsteps > 0 && ((rc = dQ.put(Q, (size_t)nch * nch)) || (rc = dlam.put(lam, nch))))) return rc;
+    if (!dev) {
+        if ((nabs > 0 && (rc = dWB.put(WB, (size_t)nabs * wband))) || (nsteps > 0 && (rc = dG.put(G, wband))) ||
+            (nproj > 0 && (rc = dP.put(P, 2 * N * nproj))) || (nsteps > 0 && (rc = df.alloc((size_t)sgroup * f_step))) ||
+            (snapping && (rc = dsnap.alloc(gsnaps * snap_one))) || (observing && (rc = dobs.alloc(grows * row_one)))) return rc;
+    }
+    BSP_HIP(hipMemsetAsync(dfinfo.p, 0, (size_t)nfac * sizeof(int), p->st));
+    BSP_HIP(hipMemsetAsync(dpinfo.p, 0, (size_t)items * sizeof(int), p->st));
+    BSP_HIP(hipMemcpyAsync(buf0.p, c, 2 * N * nscan * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, p->st));
+    TdseSplitArgs a = {};
+    a.n = n; a.k = k; a.nch = nch; a.nscan = nscan; a.nproj = nproj; a.nfac = nfac;
+    a.SB = p->d_SB; a.HB = p->d_HB;
+    a.WB = nabs > 0 ? (dev ? WB : dWB.p) : nullptr;
+    a.GB = nsteps > 0 ? (dev ? G : dG.p) : nullptr;
+    a.fac = dfac.p; a.fchan = dfchan.p; a.fw = dfw.p;
+    a.Q = dQ.p; a.lam = dlam.p;
+    a.P = nproj > 0 ? (dev ? P : dP.p) : nullptr;
+    a.g = 8.0 / dt; a.zi = 4.0 / dt; a.h = 0.5 * dt;
+    a.part = dpart.p; a.fstore = fstore.p; a.finfo = dfinfo.p; a.pinfo = dpinfo.p; a.work = work.p;
+    double *buf[2] = {buf0.p, buf1.p};
+    int cur = 0;                                                       // the buffer that holds the packets
+    rc = nsteps > 0 ? launch_tdse_split(a, 0, slots, p->st) : BSP_OK;
+    // one launch on the packets in buf[cur]; what = 1: an atomic half step, 2: the field step
+    auto launch = [&](int what, int mix, int measure, const double *fq, double *row, double *sn) {
+        a.mix = mix; a.measure = measure; a.f = fq; a.row = row; a.snap = sn;
+        a.in = buf[cur]; a.out = buf[cur ^ 1];
+        const int r = launch_tdse_split(a, what, slots, p->st);
+        if (!r && !measure) cur ^= 1;
+        return r;
+    };
+    const int nobs = observing ? (nsteps == 0 ? 1 : (nsteps - 1) / obs_every + 2) : 0;
+    for (int n0 = 0; !rc && n0 < nsteps; n0 += sgroup) {
+        const int n1 = std::min(nsteps, n0 + sgroup);
+        // the group's snapshots s0 .. s1-1 and its rows j0 .. j1-1 (the observed steps j obs_every of n0 .. n1-1)
+        const int s0 = snapping ? n0 / snap_every : 0, s1 = snapping ? n1 / snap_every : 0;
+        const int j0 = observing ? (n0 + obs_every - 1) / obs_every : 0, j1 = observing ? (n1 + obs_every - 1) / obs_every : 0;
+        const double *gf = dev ? f + (size_t)n0 * f_step : df.p;
+        if (!dev) rc = HIP_RC(hipMemcpyAsync(df.p, f + (size_t)n0 * f_step, (size_t)(n1 - n0) * f_step * sizeof(double), hipMemcpyHostToDevice, p->st));
+        // where the group's first snapshot and row go: the caller's arrays from their start (_dev), else the staging buffers
+        double *gsnap = snapping ? (dev ? snap + (size_t)s0 * snap_one : dsnap.p) : nullptr;
+        double *gobs = observing ? (dev ? obs + (size_t)j0 * row_one : dobs.p) : nullptr;
+        for (int m = n0; !rc && m < n1; ++m) {
+            double *row = observing && m % obs_every == 0 ? gobs + (size_t)(m / obs_every - j0) * row_one : nullptr;
+            double *sn = snapping && (m + 1) % snap_every == 0 ? gsnap + (size_t)((m + 1) / snap_every - 1 - s0) * snap_one : nullptr;
+            rc = launch(1, 0, 0, nullptr, row, nullptr);
+            if (!rc) rc = launch(2, 0, 0, gf + (size_t)(m - n0) * f_step, nproj > 0 ? row : nullptr, nullptr);
+            if (!rc) rc = launch(1, 1, 0, nullptr, nullptr, sn);
+            if (!rc && ((m + 1 - n0) % group == 0 || m + 1 == n1)) rc = HIP_RC(hipStreamSynchronize(p->st));
+        }
+        if (!rc && !dev && s1 > s0)
+            rc = HIP_RC(hipMemcpyAsync(snap + (size_t)s0 * snap_one, dsnap.p, (size_t)(s1 - s0) * snap_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        if (!rc && !dev && j1 > j0)
+            rc = HIP_RC(hipMemcpyAsync(obs + (size_t)j0 * row_one, dobs.p, (size_t)(j1 - j0) * row_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        if (!rc && !dev) rc = HIP_RC(hipStreamSynchronize(p->st));     // the staging buffers are free for the next group
+    }
+    if (!rc && observing) {                                            // the row of the final packets: launches that only measure
+        double *row = dev ? obs + (size_t)(nobs - 1) * row_one : dobs.p;
+        rc = launch(1, 0, 1, nullptr, row, nullptr);
+        if (!rc && nproj > 0) rc = launch(2, 0, 1, nullptr, row, nullptr);
+        if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(obs + (size_t)(nobs - 1) * row_one, dobs.p, row_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    }
+    if (!rc && nsteps > 0)
+        rc = HIP_RC(hipMemcpyAsync(c, buf[cur], 2 * N * nscan * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, p->st));
+    std::vector<int> finfo(nfac), pinfo(items);
+    if (!rc) rc = HIP_RC(hipMemcpyAsync(finfo.data(), dfinfo.p, (size_t)nfac * sizeof(int), hipMemcpyDeviceToHost, p->st));
+    if (!rc) rc = HIP_RC(hipMemcpyAsync(pinfo.data(), dpinfo.p, (size_t)items * sizeof(int), hipMemcpyDeviceToHost, p->st));
+    if ((rc = drain(p, rc))) return rc;
+    int atomic = 0;
+    for (int v : finfo) atomic += v;
+    for (int q = 0; q < nscan; ++q) {
+        int s = nsteps > 0 ? atomic : 0;
+        for (int j = 0; j < nch; ++j) s += pinfo[(size_t)q * nch + j];
+        info[q] = s;
+    }
+    return BSP_OK;
+}
+
+extern "C" int bspatom_tdse_split(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w,
+                                  const double *G, const double *Q, const double *lam, int nsteps, double dt, const double *f, double *c,
+                                  int snap_every, double *snap, int obs_every, int nproj, const double *P, double *obs, int32_t *info)
+{
+    return tdse_split_impl(p, nscan, nch, l, nabs, WB, w, G, Q, lam, nsteps, dt, f, c, snap_every, snap, obs_every, nproj, P, obs, info, false);
+}
+extern "C" int bspatom_tdse_split_dev(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB_dev,
+                                      const int32_t *w, const double *G_dev, const double *Q, const double *lam, int nsteps, double dt,
+                                      const double *f_dev, double *c_dev, int snap_every, double *snap_dev, int obs_every, int nproj,
+                                      const double *P_dev, double *obs_dev, int32_t *info)
+{
+    return tdse_split_impl(p, nscan, nch, l, nabs, WB_dev, w, G_dev, Q, lam, nsteps, dt, f_dev, c_dev, snap_every, snap_dev, obs_every, nproj,
+                           P_dev, obs_dev, info, true);
 }
 
 extern "C" int bspatom_resolvent_coupled(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,

@@ -119,6 +119,8 @@ struct Options {
                                  // result does not depend on it (the test's hook)
     int tdse_spline_group = 0;   // BSP_TDSE_SPLINE_GROUP: > 0 = steps per launch of bspatom_tdse_spline (0 = 64): no launch runs for long; the result does
                                  // not depend on it (the test's hook)
+    int tdse_split_group = 0;    // BSP_TDSE_SPLIT_GROUP: > 0 = steps whose launches bspatom_tdse_split enqueues before it waits for them (0 = 64); the result
+                                 // does not depend on it (the test's hook)
     int resolvent_stage_mb = 0;  // BSP_RESOLVENT_STAGE_MB: > 0 = bound in MB on the slot scratch of bspatom_resolvent and on the X of one group of matrices
                                  // of its host variant (0 = 2048); one slot and one matrix at least; results do not depend on it (the test's hook)
     int resolvent_slots = 0;     // BSP_RESOLVENT_SLOTS: > 0 = work slots (resident waves) of resolvent_kernel, 0 = the occupancy query x CUs;
@@ -434,6 +436,31 @@ int launch_tdse_spline(const TdseSplineArgs &a, int slots, hipStream_t st);
 // (bspatom_tdse_spline_wide); work: slots * resolvent_wide_slot_doubles(n, k, nch, 1)
 int tdse_spline_wide_slots(int k, int nch, int nscan, int *slots);
 int launch_tdse_spline_wide(const TdseSplineArgs &a, int slots, hipStream_t st);
+// tdse_split.hip: split Crank-Nicolson steps in the spline basis (bspatom_tdse_split), one wave per (scan, channel) system of
+// half-width k - 1.  fac [nch]: the channel's atomic factorisation among the nfac distinct ones, which are described by fchan, fw
+// [nfac] -- the band in HB and the absorber (-1: none) -- and kept in fstore (nfac * tdse_split_factor_doubles; finfo [nfac]: their
+// replaced pivots).  GB: ONE full band; Q [nch][nch], lam [nch]; f: the field of this launch's step, [nscan] complex.
+// g = 8 / dt, zi = 4 / dt, h = dt / 2.  in, out: the packets [nscan][nch][n] complex, 16-byte aligned, never the same buffer.
+// row (or null): this step's row [nscan][nch + 2 nproj]; part: [nscan][nproj][nch] complex between the atomic and the field launch;
+// snap (or null): a copy of out [nscan][nch][n]; pinfo [nscan][nch]: the field launch ADDS its replaced pivots.
+// work: slots * tdse_split_slot_doubles.  launch_tdse_split's what: 0 the atomic factorisations, 1 an atomic half step (mix: its
+// input mixed with Q), 2 a field step; measure: the row alone.
+struct TdseSplitArgs {
+    int n, k, nch, nscan, nproj, nfac, mix, measure;
+    const double *SB, *HB, *WB, *GB;
+    const int *fac, *fchan, *fw;
+    const double *Q, *lam, *f, *P;
+    double g, zi, h;
+    const double *in;
+    double *out, *snap, *row, *part, *fstore;
+    int *finfo, *pinfo;
+    double *work;
+};
+int tdse_split_max_k();                        // the one-wave window's limit on k
+size_t tdse_split_factor_doubles(int n, int k);
+size_t tdse_split_slot_doubles(int n, int k);
+int tdse_split_slots(int k, int items, int *slots);
+int launch_tdse_split(const TdseSplitArgs &a, int what, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

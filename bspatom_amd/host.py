@@ -1135,6 +1135,35 @@ def spline_propagate(prob, l, c0, dt, nsteps, **kw):
     return call(l, c0, dt, nsteps, **kw)
 
 
+def split_angular(channels):
+    """The angular matrix of the field term for Problem.tdse_split: A[c', c] = <l' m| cos theta |l m> between `channels` (a list of
+    (l, m)) -- the factors of stark_system(channels, 1.0), both directions of every dipole block, symmetric, zero elsewhere -- as
+    (Q, lam) of numpy.linalg.eigh: A = Q diag(lam) Q^T, Q orthogonal with the eigenvectors in its columns.  The field term of the
+    split call is then f(t) A (x) G with G = dipole_bands()[0], what tdse_spline gets from spline_coefficients(stark_system(channels,
+    1.0), f)."""
+    import numpy as np
+    nch = len(channels)
+    A = np.zeros((nch, nch))
+    couplings, a = stark_system(channels, 1.0)
+    for (cr, cc, _t), v in zip(couplings, a):
+        A[cr, cc] = v.real
+    lam, Q = np.linalg.eigh(A)
+    return np.ascontiguousarray(Q), lam
+
+
+def split_propagate(prob, l, c0, dt, angular, F_mid, G=None, **kw):
+    """Problem.tdse_split from the pieces the other helpers give: angular = (Q, lam) of split_angular, F_mid the field at the steps'
+    midpoints (spline_midpoints), (nsteps,) for every scan or (nsteps, nscan), real or complex, as spline_coefficients takes it; G
+    the radial band, dipole_bands()[0] unless given.  nsteps = len(F_mid).  W, w, P, obs_every, snap_every and the results are
+    tdse_split's."""
+    import numpy as np
+    Q, lam = angular
+    F = np.asarray(F_mid, dtype=np.complex128)
+    if G is None:
+        G = prob.dipole_bands()[0]
+    return prob.tdse_split(l, c0, dt, F.shape[0], G=G, Q=Q, lam=lam, f=F, **kw)
+
+
 def spline_yield(obs, nch=None):
     """1 - sum_c N_c of every row of Problem.tdse_spline, (nobs, nscan): with an absorber and a packet normalised to c^H S c = 1, the
     ionisation yield so far.  nch: the channels, when the rows carry projections behind the norms (default: every column is a norm)."""

@@ -661,6 +661,9 @@ int bspatom_tdse_adaptive_dev(bspatom_problem *p, int nch, int count, const doub
  * description are in bspatom_tdse_spline.h beside this file, which is part of this header (the twelve calls above are the eigenbasis
  * family; the spline call has another argument list, bspatom_resolvent_coupled's, and its own guarantees S1 - S5). */
 #include "bspatom_tdse_spline.h"
+/* The same equation with one operator term by split Crank-Nicolson steps, nch independent systems of half-width k - 1 per substep and
+ * no limit on the channels: bspatom_tdse_split.h, a part of this header like the one above, with its guarantees P1 - P4. */
+#include "bspatom_tdse_split.h"
 
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
