@@ -45,6 +45,9 @@ SPLINE_EXPORTS = ["bspatom_tdse_spline", "bspatom_tdse_spline_dev", "bspatom_tds
 # what include/bspatom_tdse_split.h, the part of the header for the split-step spline-basis TDSE, declares
 SPLIT_EXPORTS = ["bspatom_tdse_split", "bspatom_tdse_split_dev"]
 
+# what include/bspatom_spline_expect.h, the part of the header for expectation values in the spline basis, declares
+EXPECT_EXPORTS = ["bspatom_spline_expect", "bspatom_spline_expect_dev", "bspatom_tdse_split_observe", "bspatom_tdse_split_observe_dev"]
+
 _lib = None
 
 
@@ -108,6 +111,10 @@ def lib():
         L.bspatom_tdse_spline_wide_dev.argtypes = list(L.bspatom_tdse_spline.argtypes)
         L.bspatom_tdse_split.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, dbl, vp, vp, i32, vp, i32, i32, vp, vp, vp]
         L.bspatom_tdse_split_dev.argtypes = list(L.bspatom_tdse_split.argtypes)
+        L.bspatom_spline_expect.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+        L.bspatom_spline_expect_dev.argtypes = list(L.bspatom_spline_expect.argtypes)
+        L.bspatom_tdse_split_observe.argtypes = L.bspatom_tdse_split.argtypes + [i32, vp, vp]
+        L.bspatom_tdse_split_observe_dev.argtypes = list(L.bspatom_tdse_split_observe.argtypes)
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
         L.bspatom_stage_gemm.argtypes = [i32, i32, i32, i32, vp, lng, lng, lng, lng, vp, lng, lng, lng, lng,
@@ -953,6 +960,54 @@ class Problem:
         COMPLEX (nsteps, nscan), the field at every step's MIDPOINT (host.spline_midpoints), broadcast from (nsteps,).  c0: complex
         (nscan, nch, nfun) or (nch, nfun).  Returns what tdse_spline returns: (c, info), then obs if obs_every >= 1, then snaps if
         snap_every >= 1, in its shapes.  Second order in dt like tdse_spline, not equal to it: another splitting of the same equation."""
+        return self._tdse_split(l, c0, dt, nsteps, G, Q, lam, f, W, w, P, obs_every, snap_every, None)
+
+    def tdse_split_observe(self, l, c0, dt, nsteps, G=None, Q=None, lam=None, f=None, W=None, w=None, P=None, obs_every=0, snap_every=0,
+                           expect=None):
+        """tdse_split with expectation values along the run (bspatom_tdse_split_observe): expect = (B, GE) as spline_expect takes them
+        (host.split_expect_dipole, host.split_expect_accel; stack several with numpy.stack).  The rows are nch + 2 nproj + 2 nexp wide:
+        behind tdse_split's entries come Re, Im of <c| B_o (x) G_o |c>, o ascending, of the packets the row's N_ch are taken from
+        (host.split_expect_rows extracts them).  Everything else has the bits of tdse_split; expect=None is that call."""
+        return self._tdse_split(l, c0, dt, nsteps, G, Q, lam, f, W, w, P, obs_every, snap_every, expect)
+
+    def _expect_operators(self, nch, expect):
+        """(nexp, B (nexp, nch, nch), GE (nexp, 2k-1, nfun)) of an expect=(B, GE) argument; None: (0, None, None)"""
+        if expect is None:
+            return 0, None, None
+        B, GE = expect
+        B = np.ascontiguousarray(np.asarray(B, dtype=np.float64).reshape(-1, nch, nch))
+        GE = np.ascontiguousarray(np.asarray(GE, dtype=np.float64).reshape(-1, 2 * self.k - 1, self.nfun))
+        assert B.shape[0] == GE.shape[0], (B.shape, GE.shape)
+        return B.shape[0], B, GE
+
+    def spline_expect(self, c, B, GE):
+        """e(q, o) = sum_c conj(c_c)^T G_o (sum_c' B_o(c, c') c_c') of packets in the spline basis (bspatom_spline_expect): c complex
+        (nscan, nch, nfun) or (nch, nfun) -- tdse_spline's and tdse_split's packets, their snapshots --; B (nexp, nch, nch) or (nch, nch)
+        real angular matrices of any pattern; GE (nexp, 2k-1, nfun) or (2k-1, nfun) real full bands, symmetric or not (dipole_bands,
+        operator_bands, host.band_symmetric(SB)).  Returns complex (nscan, nexp), or (nexp,) for one packet.  The summation order is
+        fixed (include/bspatom_spline_expect.h): the same bits from run to run and whatever else is in the call."""
+        n = self.nfun
+        B = np.asarray(B, dtype=np.float64)
+        nch = B.shape[-1]
+        nexp, B, GE = self._expect_operators(nch, (B, GE))
+        c = np.asarray(c, dtype=np.complex128)
+        one = c.ndim == 2
+        c = np.ascontiguousarray(c.reshape(-1, nch, n))
+        e = np.zeros((c.shape[0], nexp), dtype=np.complex128)
+        _chk(lib().bspatom_spline_expect(self._h, c.shape[0], nch, nexp, _p(B), _p(GE), _p(c), _p(e)), "bspatom_spline_expect")
+        return e[0] if one else e
+
+    def spline_expect_dev(self, nscan, c_ptr, B, GE_ptr, e_ptr):
+        """spline_expect with the packets (nscan * nch * nfun complex at c_ptr), the bands (nexp * (2k-1) * nfun doubles at GE_ptr)
+        and the result (nscan * nexp complex at e_ptr) in device memory of this problem's device; B (nexp, nch, nch) is a host array."""
+        B = np.asarray(B, dtype=np.float64)
+        nch = B.shape[-1]
+        B = np.ascontiguousarray(B.reshape(-1, nch, nch))
+        _chk(lib().bspatom_spline_expect_dev(self._h, nscan, nch, B.shape[0], _p(B), _ptr(GE_ptr), _ptr(c_ptr), _ptr(e_ptr)),
+             "bspatom_spline_expect_dev")
+
+    def _tdse_split(self, l, c0, dt, nsteps, G, Q, lam, f, W, w, P, obs_every, snap_every, expect):
+        """the body of tdse_split and tdse_split_observe: the arrays of the call; expect None: bspatom_tdse_split"""
         n = self.nfun
         W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
         nabs = 0 if W is None else W.shape[0]
@@ -976,10 +1031,15 @@ class Problem:
         P = None if P is None or obs_every < 1 else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, nch, n))
         nproj = 0 if P is None else P.shape[0]
         snaps = np.zeros((nsteps // snap_every, nscan, nch, n), dtype=np.complex128) if snap_every > 0 else None
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj)) if obs_every > 0 else None
+        nexp, B, GE = self._expect_operators(nch, expect if obs_every > 0 else None)
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj + 2 * nexp)) if obs_every > 0 else None
         info = np.zeros(nscan, dtype=np.int32)
-        _chk(lib().bspatom_tdse_split(self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), _p(G), _p(Q), _p(lam), nsteps, float(dt), _p(f), _p(c),
-                                      snap_every, _p(snaps), obs_every, nproj, _p(P), _p(obs), _p(info)), "bspatom_tdse_split")
+        args = (self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), _p(G), _p(Q), _p(lam), nsteps, float(dt), _p(f), _p(c), snap_every, _p(snaps),
+                obs_every, nproj, _p(P), _p(obs), _p(info))
+        if expect is None:
+            _chk(lib().bspatom_tdse_split(*args), "bspatom_tdse_split")
+        else:
+            _chk(lib().bspatom_tdse_split_observe(*args, nexp, _p(B), _p(GE)), "bspatom_tdse_split_observe")
         return (c[0] if one else c, info) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
 
     def tdse_split_dev(self, l, nscan, nsteps, dt, c_ptr, G_ptr=None, Q=None, lam=None, f_ptr=None, nabs=0, W_ptr=None, w=None, nproj=0,
@@ -996,6 +1056,24 @@ class Problem:
         _chk(lib().bspatom_tdse_split_dev(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), _ptr(G_ptr), _p(Q), _p(lam), nsteps, float(dt),
                                           _ptr(f_ptr), _ptr(c_ptr), snap_every, _ptr(snap_ptr), obs_every, nproj, _ptr(P_ptr), _ptr(obs_ptr),
                                           _p(info)), "bspatom_tdse_split_dev")
+        return info
+
+    def tdse_split_observe_dev(self, l, nscan, nsteps, dt, c_ptr, G_ptr=None, Q=None, lam=None, f_ptr=None, nabs=0, W_ptr=None, w=None, nproj=0,
+                               P_ptr=None, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None, expect=None):
+        """tdse_split_dev with expectation values along the run (bspatom_tdse_split_observe_dev): expect = (B, GE_ptr), B a host array
+        (nexp, nch, nch), GE_ptr nexp * (2k-1) * nfun doubles in device memory; the rows at obs_ptr are nch + 2 nproj + 2 nexp wide."""
+        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
+        nch = l.size
+        w = None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), l.shape))
+        Q = None if Q is None else np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(nch, nch))
+        lam = None if lam is None else np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(nch))
+        B, GE_ptr = (None, None) if expect is None else expect
+        B = None if B is None else np.ascontiguousarray(np.asarray(B, dtype=np.float64).reshape(-1, nch, nch))
+        info = np.zeros(nscan, dtype=np.int32)
+        _chk(lib().bspatom_tdse_split_observe_dev(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), _ptr(G_ptr), _p(Q), _p(lam), nsteps,
+                                                  float(dt), _ptr(f_ptr), _ptr(c_ptr), snap_every, _ptr(snap_ptr), obs_every, nproj,
+                                                  _ptr(P_ptr), _ptr(obs_ptr), _p(info), 0 if B is None else B.shape[0], _p(B), _ptr(GE_ptr)),
+             "bspatom_tdse_split_observe_dev")
         return info
 
     def early_vector_state(self):

@@ -9,6 +9,8 @@
 //     has its own right-hand side and the steps follow each other), the screening and the scratch rules of the coupled call.
 //   bspatom_tdse_spline_wide / _dev: the same call on the blocked LU for wide bands (tdse_spline_wide.hip), through the same path.
 //   bspatom_tdse_split / _dev: split Crank-Nicolson steps, nch one-wave systems per substep (tdse_split.hip); a call path of its own.
+//   bspatom_spline_expect / _dev: <c| B (x) G |c> on packets in the spline basis (spline_expect.hip);
+//   bspatom_tdse_split_observe / _dev: the split call's path with those numbers appended to its rows.
 // The eight resolvent entry points run through resolvent_call: a front function per flavour screens what is particular to it, describes the call by
 // counts per ITEM (a matrix, a chain, a coupled matrix) and hands over its slot query and its launcher.
 #include <algorithm>
@@ -379,16 +381,96 @@ extern "C" int bspatom_tdse_spline_wide_dev(bspatom_problem *p, int nscan, int n
                             snap_dev, obs_every, nproj, P_dev, obs_dev, info, true, true);
 }
 
+// What a measurement of nexp operators B_o (x) G_o on packets needs on the device (spline_expect.hip), built once per call: the rows of
+// the angular matrices compacted to their non-zero entries -- cos theta couples two neighbours, not nch --, the bands (staged here for
+// a host caller), the partials and the slots' scratch.  measure() enqueues the two launches of one measurement.
+struct ExpectPlan {
+    SplineExpectArgs a = {};
+    int slots = 0;
+    DevArray<double> work, part, dval, dGE;
+    DevArray<int> drptr, didx;
+    int init(const bspatom_problem *p, int nscan, int nch, int nexp, const double *B, const double *GE, bool ge_dev)
+    {
+        const int n = p->hs.nfun, k = p->hs.k;
+        if ((long long)nscan * nexp * nch > 0x3fffffffLL || (long long)nexp * nch * nch > 0x3fffffffLL) return BSP_ERR_ARG;
+        const int items = nscan * nexp * nch;
+        std::vector<int> rptr(1, 0), idx;
+        std::vector<double> val;
+        for (size_t r = 0; r < (size_t)nexp * nch; ++r) {
+            for (int cc = 0; cc < nch; ++cc)
+                if (B[r * nch + cc] != 0.0) { idx.push_back(cc); val.push_back(B[r * nch + cc]); }
+            rptr.push_back((int)idx.size());
+        }
+        int rc;
+        if ((rc = spline_expect_slots(items, &slots))) return rc;
+        if (opts().resolvent_slots > 0) slots = std::min(opts().resolvent_slots, items);
+        const size_t slot_doubles = spline_expect_slot_doubles(n);
+        const size_t rstage = opts().resolvent_stage_mb > 0 ? (size_t)opts().resolvent_stage_mb << 20 : RESOLVENT_STAGE_BYTES;
+        slots = (int)std::max<size_t>(1, std::min<size_t>(slots, rstage / (slot_doubles * sizeof(double))));
+        if ((rc = work.alloc((size_t)slots * slot_doubles)) || (rc = part.alloc((size_t)2 * items)) || (rc = drptr.put(rptr.data(), rptr.size())) ||
+            (rc = didx.put(idx.data(), idx.size())) || (rc = dval.put(val.data(), val.size())) ||
+            (!ge_dev && (rc = dGE.put(GE, (size_t)nexp * (2 * k - 1) * n)))) return rc;
+        a.n = n; a.k = k; a.nch = nch; a.nscan = nscan; a.nexp = nexp;
+        a.GE = ge_dev ? GE : dGE.p;
+        a.rptr = drptr.p; a.cidx = didx.p; a.cval = dval.p;
+        a.part = part.p; a.work = work.p;
+        return BSP_OK;
+    }
+    int measure(const double *c_dev, double *e_dev, hipStream_t st)
+    {
+        a.c = c_dev; a.e = e_dev;
+        return launch_spline_expect(a, slots, st);
+    }
+};
+
+// bspatom_spline_expect / _dev: one measurement on the caller's packets.  The kernels read the packets as 16-byte complex values: a
+// device pointer that is not so aligned is copied first.
+static int spline_expect_impl(bspatom_problem *p, int nscan, int nch, int nexp, const double *B, const double *GE, const double *c, double *e,
+                              bool dev)
+{
+    if (!p || !c || !e || nscan < 1 || nch < 1 || nexp < 0 || (nexp > 0 && (!B || !GE))) return BSP_ERR_ARG;
+    if (nexp == 0) return BSP_OK;
+    const int n = p->hs.nfun;
+    if ((long long)nch * n > 0x3fffffffLL || (long long)nscan * nch > 0x3fffffffLL) return BSP_ERR_ARG;
+    const size_t cdoubles = (size_t)2 * nscan * nch * n, edoubles = (size_t)2 * nscan * nexp;
+    BSP_HIP(hipSetDevice(p->device));
+    ExpectPlan plan;
+    DevArray<double> dc, de;
+    int rc;
+    if ((rc = plan.init(p, nscan, nch, nexp, B, GE, dev))) return rc;
+    const bool copy = !dev || (reinterpret_cast<uintptr_t>(c) & 15) != 0;
+    if (copy && (rc = dc.alloc(cdoubles))) return rc;
+    if (!dev && (rc = de.alloc(edoubles))) return rc;
+    if (copy) rc = HIP_RC(hipMemcpyAsync(dc.p, c, cdoubles * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, p->st));
+    if (!rc) rc = plan.measure(copy ? dc.p : c, dev ? e : de.p, p->st);
+    if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(e, de.p, edoubles * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    return drain(p, rc);
+}
+extern "C" int bspatom_spline_expect(bspatom_problem *p, int nscan, int nch, int nexp, const double *B, const double *GE, const double *c,
+                                     double *e)
+{
+    return spline_expect_impl(p, nscan, nch, nexp, B, GE, c, e, false);
+}
+extern "C" int bspatom_spline_expect_dev(bspatom_problem *p, int nscan, int nch, int nexp, const double *B, const double *GE_dev,
+                                         const double *c_dev, double *e_dev)
+{
+    return spline_expect_impl(p, nscan, nch, nexp, B, GE_dev, c_dev, e_dev, true);
+}
+
 // bspatom_tdse_split / _dev: nsteps split Crank-Nicolson steps of nscan packets (tdse_split.hip).  A step is three launches over the
 // nscan * nch one-wave systems -- atomic half step, field step, atomic half step -- on two packet buffers that alternate; the atomic
 // matrices are factored once, one per distinct (l, w).  The launches of tdse_split_group steps are enqueued, then waited for; the host
 // variant stages f, the snapshots and the rows by groups of whole steps under tdse_stage_mb (one step at least); neither changes what
-// a step computes.
+// a step computes.  With nexp > 0 (bspatom_tdse_split_observe) a row is nch + 2 nproj + 2 nexp wide: on an observed step the measuring
+// launches of spline_expect.hip run on the buffer the step's first atomic launch reads, in front of it; the kernels of tdse_split.hip
+// write their rows at the width they know into a buffer of their own, and one launch per staging group puts the two side by side.
 static int tdse_split_impl(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w, const double *G,
                            const double *Q, const double *lam, int nsteps, double dt, const double *f, double *c, int snap_every, double *snap,
-                           int obs_every, int nproj, const double *P, double *obs, int32_t *info, bool dev)
+                           int obs_every, int nproj, const double *P, double *obs, int32_t *info, int nexp, const double *EB, const double *GE,
+                           bool dev)
 {
     if (!p || !l || !c || !info || nscan < 1 || nch < 1 || nsteps < 0 || nabs < 0 || nproj < 0 || (nabs > 0 && !WB)) return BSP_ERR_ARG;
+    if (nexp < 0 || (nexp > 0 && (!EB || !GE))) return BSP_ERR_ARG;
     if (!std::isfinite(dt) || !(dt > 0.0)) return BSP_ERR_ARG;
     if (nsteps > 0 && (!G || !Q || !lam || !f)) return BSP_ERR_ARG;
     if (snap_every < 0 || (snap && snap_every == 0)) return BSP_ERR_ARG;
@@ -404,10 +486,13 @@ static int tdse_split_impl(bspatom_problem *p, int nscan, int nch, const int32_t
     }
     if ((long long)nch * n > 0x3fffffffLL || (long long)nscan * nch > 0x3fffffffLL || (long long)nsteps * nscan > 0x3fffffffLL) return BSP_ERR_ARG;
     const bool snapping = snap && snap_every > 0, observing = obs != nullptr;
-    if (!observing) nproj = 0;
+    if (!observing) { nproj = 0; nexp = 0; }
+    const bool expecting = nexp > 0;
     const int items = nscan * nch;
-    const size_t N = (size_t)nch * n, wband = (size_t)(2 * k - 1) * n, RW = (size_t)nch + 2 * nproj;
-    const size_t f_step = (size_t)2 * nscan, snap_one = 2 * N * nscan, row_one = RW * nscan;   // doubles
+    // RW0: the row as the kernels of tdse_split.hip write it; RW: the caller's row
+    const size_t N = (size_t)nch * n, wband = (size_t)(2 * k - 1) * n, RW0 = (size_t)nch + 2 * nproj, RW = RW0 + 2 * (size_t)nexp;
+    const size_t f_step = (size_t)2 * nscan, snap_one = 2 * N * nscan, row_one = RW * nscan, row0_one = RW0 * nscan,
+                 e_one = (size_t)2 * nexp * nscan;   // doubles
     BSP_HIP(hipSetDevice(p->device));
     int rc, slots = 0;
     if ((rc = tdse_split_slots(k, items, &slots))) return rc;
@@ -436,7 +521,11 @@ static int tdse_split_impl(bspatom_problem *p, int nscan, int nch, const int32_t
     }
     const int nfac = (int)fchan.size();
     DevArray<double> work, fstore, buf0, buf1, dQ, dlam, dpart, dWB, dG, dP, df, dsnap, dobs;
+    DevArray<double> drow0, dexp;
     DevArray<int> dfac, dfchan, dfw, dfinfo, dpinfo;
+    ExpectPlan plan;
+    if (expecting && ((rc = plan.init(p, nscan, nch, nexp, EB, GE, dev)) || (rc = drow0.alloc(grows * row0_one)) || (rc = dexp.alloc(grows * e_one))))
+        return rc;
     if ((rc = work.alloc((size_t)slots * slot_doubles)) || (rc = fstore.alloc((size_t)nfac * fac_doubles)) || (rc = buf0.alloc(2 * N * nscan)) ||
         (rc = buf1.alloc(2 * N * nscan)) || (rc = dpart.alloc((size_t)2 * nscan * nproj * nch)) ||
         (rc = dfac.put(fac.data(), nch)) || (rc = dfchan.put(fchan.data(), nfac)) ||
@@ -483,13 +572,17 @@ static int tdse_split_impl(bspatom_problem *p, int nscan, int nch, const int32_t
         double *gsnap = snapping ? (dev ? snap + (size_t)s0 * snap_one : dsnap.p) : nullptr;
         double *gobs = observing ? (dev ? obs + (size_t)j0 * row_one : dobs.p) : nullptr;
         for (int m = n0; !rc && m < n1; ++m) {
-            double *row = observing && m % obs_every == 0 ? gobs + (size_t)(m / obs_every - j0) * row_one : nullptr;
+            const bool observed = observing && m % obs_every == 0;
+            const size_t jr = observed ? (size_t)(m / obs_every - j0) : 0;          // the row's place in the group
+            double *row = observed ? (expecting ? drow0.p + jr * row0_one : gobs + jr * row_one) : nullptr;
             double *sn = snapping && (m + 1) % snap_every == 0 ? gsnap + (size_t)((m + 1) / snap_every - 1 - s0) * snap_one : nullptr;
-            rc = launch(1, 0, 0, nullptr, row, nullptr);
+            if (row && expecting) rc = plan.measure(buf[cur], dexp.p + jr * e_one, p->st);
+            if (!rc) rc = launch(1, 0, 0, nullptr, row, nullptr);
             if (!rc) rc = launch(2, 0, 0, gf + (size_t)(m - n0) * f_step, nproj > 0 ? row : nullptr, nullptr);
             if (!rc) rc = launch(1, 1, 0, nullptr, nullptr, sn);
             if (!rc && ((m + 1 - n0) % group == 0 || m + 1 == n1)) rc = HIP_RC(hipStreamSynchronize(p->st));
         }
+        if (!rc && expecting && j1 > j0) rc = launch_spline_expect_rows(gobs, drow0.p, dexp.p, (int)RW0, nexp, (j1 - j0) * nscan, p->st);
         if (!rc && !dev && s1 > s0)
             rc = HIP_RC(hipMemcpyAsync(snap + (size_t)s0 * snap_one, dsnap.p, (size_t)(s1 - s0) * snap_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
         if (!rc && !dev && j1 > j0)
@@ -497,9 +590,11 @@ static int tdse_split_impl(bspatom_problem *p, int nscan, int nch, const int32_t
         if (!rc && !dev) rc = HIP_RC(hipStreamSynchronize(p->st));     // the staging buffers are free for the next group
     }
     if (!rc && observing) {                                            // the row of the final packets: launches that only measure
-        double *row = dev ? obs + (size_t)(nobs - 1) * row_one : dobs.p;
-        rc = launch(1, 0, 1, nullptr, row, nullptr);
+        double *wide = dev ? obs + (size_t)(nobs - 1) * row_one : dobs.p, *row = expecting ? drow0.p : wide;
+        if (expecting) rc = plan.measure(buf[cur], dexp.p, p->st);
+        if (!rc) rc = launch(1, 0, 1, nullptr, row, nullptr);
         if (!rc && nproj > 0) rc = launch(2, 0, 1, nullptr, row, nullptr);
+        if (!rc && expecting) rc = launch_spline_expect_rows(wide, drow0.p, dexp.p, (int)RW0, nexp, nscan, p->st);
         if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(obs + (size_t)(nobs - 1) * row_one, dobs.p, row_one * sizeof(double), hipMemcpyDeviceToHost, p->st));
     }
     if (!rc && nsteps > 0)
@@ -522,7 +617,8 @@ extern "C" int bspatom_tdse_split(bspatom_problem *p, int nscan, int nch, const 
                                   const double *G, const double *Q, const double *lam, int nsteps, double dt, const double *f, double *c,
                                   int snap_every, double *snap, int obs_every, int nproj, const double *P, double *obs, int32_t *info)
 {
-    return tdse_split_impl(p, nscan, nch, l, nabs, WB, w, G, Q, lam, nsteps, dt, f, c, snap_every, snap, obs_every, nproj, P, obs, info, false);
+    return tdse_split_impl(p, nscan, nch, l, nabs, WB, w, G, Q, lam, nsteps, dt, f, c, snap_every, snap, obs_every, nproj, P, obs, info, 0, nullptr, nullptr,
+                           false);
 }
 extern "C" int bspatom_tdse_split_dev(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB_dev,
                                       const int32_t *w, const double *G_dev, const double *Q, const double *lam, int nsteps, double dt,
@@ -530,7 +626,24 @@ extern "C" int bspatom_tdse_split_dev(bspatom_problem *p, int nscan, int nch, co
                                       const double *P_dev, double *obs_dev, int32_t *info)
 {
     return tdse_split_impl(p, nscan, nch, l, nabs, WB_dev, w, G_dev, Q, lam, nsteps, dt, f_dev, c_dev, snap_every, snap_dev, obs_every, nproj,
-                           P_dev, obs_dev, info, true);
+                           P_dev, obs_dev, info, 0, nullptr, nullptr, true);
+}
+extern "C" int bspatom_tdse_split_observe(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w,
+                                          const double *G, const double *Q, const double *lam, int nsteps, double dt, const double *f, double *c,
+                                          int snap_every, double *snap, int obs_every, int nproj, const double *P, double *obs, int32_t *info,
+                                          int nexp, const double *B, const double *GE)
+{
+    return tdse_split_impl(p, nscan, nch, l, nabs, WB, w, G, Q, lam, nsteps, dt, f, c, snap_every, snap, obs_every, nproj, P, obs, info, nexp, B,
+                           GE, false);
+}
+extern "C" int bspatom_tdse_split_observe_dev(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB_dev,
+                                              const int32_t *w, const double *G_dev, const double *Q, const double *lam, int nsteps, double dt,
+                                              const double *f_dev, double *c_dev, int snap_every, double *snap_dev, int obs_every, int nproj,
+                                              const double *P_dev, double *obs_dev, int32_t *info, int nexp, const double *B,
+                                              const double *GE_dev)
+{
+    return tdse_split_impl(p, nscan, nch, l, nabs, WB_dev, w, G_dev, Q, lam, nsteps, dt, f_dev, c_dev, snap_every, snap_dev, obs_every, nproj,
+                           P_dev, obs_dev, info, nexp, B, GE_dev, true);
 }
 
 extern "C" int bspatom_resolvent_coupled(bspatom_problem *p, int nmat, int nch, const int32_t *l, const double *z, int nabs,

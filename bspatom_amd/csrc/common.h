@@ -461,6 +461,24 @@ size_t tdse_split_factor_doubles(int n, int k);
 size_t tdse_split_slot_doubles(int n, int k);
 int tdse_split_slots(int k, int items, int *slots);
 int launch_tdse_split(const TdseSplitArgs &a, int what, int slots, hipStream_t st);
+// spline_expect.hip: e(q, o) = sum_c conj(c_c)^T G_o (sum_c' B_o(c, c') c_c') on packets in the spline basis (bspatom_spline_expect).
+// GE: nexp full bands [2k-1][n]; the rows of the angular matrices compacted by the host: row r = o*nch + c holds its non-zero entries
+// rptr[r] .. rptr[r+1]-1, cidx ascending, cval; c: the packets [nscan][nch][n] complex, 16-byte aligned; part: [nscan][nexp][nch]
+// complex, one partial per item, between the two launches; e: [nscan][nexp] complex; work: slots * spline_expect_slot_doubles.
+struct SplineExpectArgs {
+    int n, k, nch, nscan, nexp;
+    const double *GE;
+    const int *rptr, *cidx;
+    const double *cval;
+    const double *c;
+    double *part, *e;
+    double *work;
+};
+size_t spline_expect_slot_doubles(int n);
+int spline_expect_slots(int items, int *slots);
+int launch_spline_expect(const SplineExpectArgs &a, int slots, hipStream_t st);
+// out [nrows][rw0 + 2 nexp] = row0 [nrows][rw0] beside e [nrows][2 nexp]: the rows of bspatom_tdse_split_observe
+int launch_spline_expect_rows(double *out, const double *row0, const double *e, int rw0, int nexp, int nrows, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

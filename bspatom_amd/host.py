@@ -1161,7 +1161,83 @@ def split_propagate(prob, l, c0, dt, angular, F_mid, G=None, **kw):
     F = np.asarray(F_mid, dtype=np.complex128)
     if G is None:
         G = prob.dipole_bands()[0]
+    if kw.get("expect") is not None:
+        return prob.tdse_split_observe(l, c0, dt, F.shape[0], G=G, Q=Q, lam=lam, f=F, **kw)
+    kw.pop("expect", None)
     return prob.tdse_split(l, c0, dt, F.shape[0], G=G, Q=Q, lam=lam, f=F, **kw)
+
+
+def _split_cos_theta(channels):
+    """A[c', c] = <l' m| cos theta |l m> between `channels`: the matrix split_angular diagonalises"""
+    import numpy as np
+    nch = len(channels)
+    A = np.zeros((nch, nch))
+    couplings, a = stark_system(channels, 1.0)
+    for (cr, cc, _t), v in zip(couplings, a):
+        A[cr, cc] = v.real
+    return A
+
+
+def split_expect_dipole(prob, channels):
+    """(B, GE) of the induced dipole <z> = <c| cos theta (x) r |c> for Problem.spline_expect and the expect= argument of
+    Problem.tdse_split_observe: B (1, nch, nch) the cos theta matrix of stark_system(channels, 1.0) -- split_angular's A, both
+    directions of every dipole block, two non-zero entries per row at most --, GE (1, 2k-1, nfun) = dipole_bands()[0], the band of r.
+    Both are symmetric: the value is real to rounding."""
+    import numpy as np
+    return _split_cos_theta(channels)[None], np.ascontiguousarray(prob.dipole_bands()[0][None])
+
+
+def split_expect_accel(prob, channels, dVdr=None):
+    """(B, GE) of the dipole acceleration form <c| cos theta (x) dV/dr |c>, the observable an absorbing boundary does not spoil
+    (a(t) = -<dV/dr cos theta> - F(t) for one electron): the B of split_expect_dipole, GE (1, 2k-1, nfun) the operator_bands of dV/dr on
+    the quadrature points.  dVdr: the profile on prob.quadrature()[0], or a callable of r; None: zatom / r^2, the Coulomb potential's,
+    valid for kind_pot = 0 alone -- with another potential and no profile: ValueError."""
+    import numpy as np
+    r = prob.quadrature()[0]
+    if dVdr is None:
+        if int(prob.inp.kind_pot) != 0:
+            raise ValueError("split_expect_accel: kind_pot = %d is not the Coulomb potential: give dVdr on the quadrature points"
+                             % int(prob.inp.kind_pot))
+        g = float(prob.inp.zatom) / (r * r)
+    else:
+        g = np.asarray(dVdr(r) if callable(dVdr) else dVdr, dtype=np.float64).reshape(r.shape)
+    return _split_cos_theta(channels)[None], np.ascontiguousarray(prob.operator_bands(g, [0]))
+
+
+def split_expect_rows(obs, nch, nproj):
+    """The expectation values of the rows of Problem.tdse_split_observe: complex (nobs, nscan, nexp) from obs (nobs, nscan, nch +
+    2 nproj + 2 nexp), operator o from the entries nch + 2 nproj + 2 o (Re) and + 1 (Im)."""
+    import numpy as np
+    obs = np.asarray(obs, dtype=np.float64)
+    off = nch + 2 * nproj
+    if obs.ndim != 3 or obs.shape[-1] < off or (obs.shape[-1] - off) % 2:
+        raise ValueError("split_expect_rows: rows of width %s do not hold nch = %d norms, %d projections and whole complex entries"
+                         % (obs.shape[-1:], nch, nproj))
+    e = obs[..., off:]
+    return e[..., 0::2] + 1j * e[..., 1::2]
+
+
+def hhg_spectrum(d, dt_rows, window="hann", kind="dipole"):
+    """The harmonic spectrum of a dipole or acceleration signal sampled every dt_rows (obs_every * dt): (omega, S), omega = 2 pi
+    rfftfreq, S = |omega^2 d~(omega)|^2 for kind = "dipole" (the acceleration's spectrum from the length form) or |a~(omega)|^2 for
+    kind = "accel", with x~(omega) = dt_rows sum_n w_n x_n exp(-i omega t_n).  d: (nt,) or (nt, ...), the time on axis 0, real or
+    complex (the real part is taken: the observables are real); window "hann" or None.  Pure NumPy."""
+    import numpy as np
+    x = np.real(np.asarray(d))
+    nt = x.shape[0]
+    if window == "hann":
+        wn = np.hanning(nt)
+    elif window is None:
+        wn = np.ones(nt)
+    else:
+        raise ValueError("hhg_spectrum: window %r (\"hann\" or None)" % (window,))
+    if kind not in ("dipole", "accel"):
+        raise ValueError("hhg_spectrum: kind %r (\"dipole\" or \"accel\")" % (kind,))
+    omega = 2.0 * np.pi * np.fft.rfftfreq(nt, float(dt_rows))
+    xt = float(dt_rows) * np.fft.rfft(x * wn.reshape((nt,) + (1,) * (x.ndim - 1)), axis=0)
+    if kind == "dipole":
+        xt = xt * (omega ** 2).reshape((-1,) + (1,) * (x.ndim - 1))
+    return omega, np.abs(xt) ** 2
 
 
 def spline_yield(obs, nch=None):

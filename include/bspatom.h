@@ -664,6 +664,9 @@ int bspatom_tdse_adaptive_dev(bspatom_problem *p, int nch, int count, const doub
 /* The same equation with one operator term by split Crank-Nicolson steps, nch independent systems of half-width k - 1 per substep and
  * no limit on the channels: bspatom_tdse_split.h, a part of this header like the one above, with its guarantees P1 - P4. */
 #include "bspatom_tdse_split.h"
+/* Expectation values <c| B (x) G |c> on packets in the spline basis -- the induced dipole, the dipole acceleration -- in a call of
+ * their own and as further row entries along a split-step run: bspatom_spline_expect.h, a part of this header like the two above. */
+#include "bspatom_spline_expect.h"
 
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the

@@ -54,7 +54,9 @@
  * is conserved).
  * BSPATOM_ERR_ARG: what bspatom_tdse_spline names for p, l, w, nabs, WB, nscan, nch, nsteps, dt, c, info, snap_every, snap, obs_every,
  * obs, nproj, P; G, Q, lam or f NULL with nsteps > 0.
- * The _dev variant: WB, G, f, c, snap, P, obs in device memory of the problem's device; l, w, Q, lam, info stay host pointers. */
+ * The _dev variant: WB, G, f, c, snap, P, obs in device memory of the problem's device; l, w, Q, lam, info stay host pointers.
+ * The same call with expectation values <c| B (x) G |c> -- the dipole, the acceleration -- behind the entries of every row:
+ * bspatom_tdse_split_observe in bspatom_spline_expect.h. */
 int bspatom_tdse_split(bspatom_problem *p, int nscan, int nch, const int32_t *l, int nabs, const double *WB, const int32_t *w, const double *G,
                        const double *Q, const double *lam, int nsteps, double dt, const double *f, double *c, int snap_every, double *snap,
                        int obs_every, int nproj, const double *P, double *obs, int32_t *info);
