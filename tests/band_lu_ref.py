@@ -7,7 +7,9 @@ among the rows j .. j + bw of column j, ties to the smallest row), with two faul
                            window, the second register set of the backward pass, the second chunk of the trailing update left out).
 
 Unmutated it is LU with partial pivoting of the dense matrix, as LAPACK's; the mutants are the evidence that a test would notice such a
-kernel (test_resolvent_pivots_cpu.py).  No zero-pivot replacement: the matrices it is given are regular."""
+kernel (test_resolvent_pivots_cpu.py, test_tdse_split_pivots_cpu.py).  No zero-pivot replacement: the matrices it solves with are
+regular; factor() alone also takes a matrix with exactly zero columns (a zero pivot over a zero column is left where it is, its
+multipliers are zero), so that the other pivots of such a matrix can be looked at."""
 import numpy as np
 
 
@@ -32,7 +34,7 @@ def factor(M, bw, max_pivot_distance=None, fill_width=None):
             A[j, min(N, j + fill_width + 1):ce] = 0.0
         nz = np.nonzero(A[j, j:ce])[0]
         widest = max(widest, int(nz[-1]) if nz.size else 0)
-        if hi > j + 1:
+        if hi > j + 1 and (A[j, j] != 0.0 or np.any(A[j + 1:hi, j] != 0.0)):
             lm = A[j + 1:hi, j] / A[j, j]
             A[j + 1:hi, j] = lm
             A[j + 1:hi, j + 1:ce] -= lm[:, None] * A[j, j + 1:ce][None, :]
@@ -42,6 +44,11 @@ def factor(M, bw, max_pivot_distance=None, fill_width=None):
 def solve(M, b, bw, max_pivot_distance=None, fill_width=None):
     """x with M x = b by factor() and the two substitutions; b (N,) or (nrhs, N), x alike"""
     LU, piv, _ = factor(M, bw, max_pivot_distance, fill_width)
+    return substitute(LU, piv, b, bw)
+
+
+def substitute(LU, piv, b, bw):
+    """the two substitutions of solve() on what factor() returned: a matrix factored once solves many right-hand sides"""
     N = LU.shape[0]
     y = np.array(np.asarray(b, dtype=np.complex128).reshape(-1, N).T)
     for j in range(N):

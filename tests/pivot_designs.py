@@ -23,7 +23,23 @@ spreads: the mutant's backward error is 240 .. 5e5 eps on every matrix, against 
 Every builder returns a `system`: a dict of the call's own arguments (l, z (nmat, nch), w (nmat, nch) or None, couplings, G, a (nmat,
 ncoup, nop); W (nabs, 2k-1, n) for the single-channel call).  The GPU call and dense() are given the same arrays.  The conditions the
 designs must meet are asserted on LAPACK's factorisation in test_resolvent_pivots_cpu.py; the GPU cases are in
-test_gpu_resolvent_pivots.py."""
+test_gpu_resolvent_pivots.py.
+
+The split-step TDSE (csrc/tdse_split.hip) has its own one-wave LU and two kinds of matrix, both reached through bspatom_tdse_split's
+public arguments at dt = SPLIT_DT = 2^-11, where everything the host derives is a power of two (4 / dt = 8192, dt / 2 = 2^-12):
+
+  atomic   M_c = H_l - i W - (4i / dt) S is bspatom_resolvent's matrix at z = 8192 i: design (A) of the single-channel call goes into
+           the call's absorbers, one per l (split_atomic).
+  field    N_j = S + i (dt/2) f lam_j G.  With f = -2i / dt the factor is lam_j exactly, and lam_j = 1 makes N_j = S + G: G is (A)'s
+           swap pairs at t max |S| minus the eraser of the first halves' columns, which then cancels exactly (split_field); f = +2i / dt
+           puts the same matrix into the eigenchannel lam_j = -1.  A never is an argument: lam and Q are (SPLIT_LAM, split_q()).
+  zeros    G = minus the columns j1 = n // 3 and j2 = 2n // 3 + 1 of S: N_j has two exactly zero columns where lam_j times the sign of
+           -Im f is +1 and is regular elsewhere (split_singular).  The atomic matrix cannot be made singular through the public
+           arguments (H_l cannot be cancelled), and which of two equal candidates becomes the pivot shows in the bits alone: no design
+           asks for either.
+
+split_system() puts them into the arguments of one call; test_tdse_split_pivots_cpu.py proves them, test_gpu_tdse_split_pivots.py
+runs them."""
 import numpy as np
 
 import resolvent_ref as ref
@@ -34,8 +50,9 @@ import resolvent_coupled_ref as cref
 _LIN = dict(kind_grid=0, ra=0.0, l_fin=1, l_ini=0, n0_ini=1, zatom=1.0)
 GRIDS = {"tiny8": dict(_LIN, rb=12.0, k=5, nfun=8), "n65_k4": dict(_LIN, rb=40.0, k=4, nfun=65),
          "lin256": dict(_LIN, rb=50.0, k=9, nfun=256), "k16_n40": dict(_LIN, rb=20.0, k=16, nfun=40),
-         "k16_n20": dict(_LIN, rb=20.0, k=16, nfun=20)}
-SINGLE_CASES = ["n65_k4", "lin256", "k16_n40"]
+         "k16_n20": dict(_LIN, rb=20.0, k=16, nfun=20), "k10_n65": dict(_LIN, rb=30.0, k=10, nfun=65)}
+# k10_n65: b = 9, the kernels' instances for b <= 15 with rows of the register window unused
+SINGLE_CASES = ["n65_k4", "lin256", "k10_n65", "k16_n40"]
 NARROW_CASES = [("tiny8", 2), ("n65_k4", 3), ("lin256", 7), ("k16_n40", 4)]
 WIDE_CASES = [("n65_k4", 17), ("k16_n20", 5), ("k16_n40", 9), ("k16_n40", 16)]
 WIDE_C = [("n65_k4", 17), ("k16_n20", 5)]                      # the integer design on the two smaller wide cases
@@ -237,3 +254,82 @@ def coupled_systems(name, nch, SB, HB, WB, kinds):
         else:
             out.append(design_c(SB, HB, nch))
     return out
+
+
+# ---- the split-step TDSE -------------------------------------------------------------------------------------------------------
+SPLIT_DT = 2.0 ** -11
+SPLIT_GRIDS = ["tiny8", "n65_k4", "lin256", "k10_n65", "k16_n40"]
+SPLIT_VARIANTS = ["atomic", "field", "both"]
+SPLIT_L, SPLIT_W = [0, 1, 0], [0, 1, -1]                       # the designed absorber m belongs to l = m; channel 2 stays physical
+SPLIT_LAM = np.array([-1.0, 0.5, 1.0])                         # +-1: the designed eigenchannels of f = -+2i / dt; 0.5: the same bands at half the strength
+SPLIT_NSTEPS, SPLIT_NSCAN = 2, 3
+SPLIT_ZERO_GRIDS = ["n65_k4", "lin256", "k10_n65"]
+
+
+def split_q():
+    """a fixed orthogonal 3 x 3 matrix without a zero entry: the Q factor of a seeded Gaussian matrix"""
+    Q = np.linalg.qr(np.random.default_rng(77).standard_normal((3, 3)))[0]
+    assert np.min(np.abs(Q)) > 0.05
+    return np.ascontiguousarray(Q)
+
+
+def split_atomic(SB, HB, dt=SPLIT_DT):
+    """(2, 2k-1, n): the absorbers that make M_c = H_l - i W_l - (4i / dt) S design (A) at t = 20 (l = 0) and t = 2 (l = 1)"""
+    return design_a_single(SB, HB, mats=((0, 0.0), (1, 0.0)), y=4.0 / dt)["W"]
+
+
+def split_field(SB, t=T_STRONG):
+    """the band G with S + G = design (A) on the overlap: t max |S| (lo + hi) minus the eraser of the first halves' columns"""
+    k, n = SB.shape
+    return t * float(np.max(np.abs(SB))) * swap_bands(n, k).sum(axis=0) - lower_overlap(SB, swap_rows(n, k) - (k - 1))
+
+
+def split_zero_columns(n):
+    return n // 3, (2 * n) // 3 + 1
+
+
+def split_singular(SB, cols=None):
+    """the band G = minus the columns `cols` (None: both of split_zero_columns) of S's full band: S + G has those columns exactly
+    zero, S - G and S + G / 2 are regular"""
+    k, n = SB.shape
+    F = full_band(SB)
+    G = np.zeros_like(F)
+    for j in (split_zero_columns(n) if cols is None else cols):
+        for i in range(max(0, j - (k - 1)), min(n, j + k)):    # the entry (i, j) is stored at [j - i + k - 1, i]
+            G[j - i + k - 1, i] = -F[j - i + k - 1, i]
+    return G
+
+
+def split_fields(dt=SPLIT_DT, nsteps=SPLIT_NSTEPS):
+    """(nsteps, 3) complex: scan 0 f = -2i / dt (the factor of G is lam_j), scan 1 +2i / dt (-lam_j), scan 2 a real 0.5"""
+    return np.ascontiguousarray(np.broadcast_to(np.array([-2j / dt, 2j / dt, 0.5]), (nsteps, 3)))
+
+
+def split_packets(n, nch=3, nscan=SPLIT_NSCAN, seed=300):
+    """(nscan, nch, n) complex Gaussian packets of norm about 1, the first real"""
+    rng = np.random.default_rng(seed + n)
+    c0 = (rng.standard_normal((nscan, nch, n)) + 1j * rng.standard_normal((nscan, nch, n))) / np.sqrt(n)
+    c0[0] = c0[0].real
+    return c0
+
+
+def split_system(variant, SB, HB, RB, dt=SPLIT_DT):
+    """The arguments of one bspatom_tdse_split call on three channels, two steps and three scans.  variant "atomic": the designed
+    absorbers, G = RB (the band of r) and a real field U(0.2, 1) per step and scan (an imaginary f of size 2 / dt on the band of r
+    would make S + lam r indefinite); "field": no absorber, G = split_field, f = split_fields; "both"; "zeros" / "zero": no absorber,
+    G = split_singular with both columns / with column j2 alone, f = split_fields."""
+    k, n = SB.shape
+    designed_f = variant != "atomic"
+    f = split_fields(dt) if designed_f else np.random.default_rng(400 + n).uniform(0.2, 1.0, (SPLIT_NSTEPS, SPLIT_NSCAN)).astype(np.complex128)
+    if variant in ("zeros", "zero"):
+        G = split_singular(SB, None if variant == "zeros" else split_zero_columns(n)[1:])
+    else:
+        G = split_field(SB) if designed_f else np.array(RB, dtype=np.float64)
+    W = split_atomic(SB, HB, dt) if variant in ("atomic", "both") else None
+    return dict(variant=variant, l=list(SPLIT_L), w=None if W is None else list(SPLIT_W), W=W, G=np.ascontiguousarray(G), Q=split_q(),
+                lam=SPLIT_LAM.copy(), f=f, c0=split_packets(n), dt=dt, nsteps=SPLIT_NSTEPS)
+
+
+def split_field_matrix(sy, SB, q, j, step=0):
+    """the dense N_j of scan q at a step, as tests/tdse_split_ref.py forms it"""
+    return ref.upper_to_dense(SB) + 0.5j * sy["dt"] * sy["f"][step, q] * sy["lam"][j] * ref.full_to_dense(sy["G"])

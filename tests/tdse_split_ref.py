@@ -7,10 +7,13 @@ the three substeps of a step in complex128 with per-channel DENSE matrices built
 
 with the linear solves written twice: numpy.linalg.solve on the dense blocks ("dense") and scipy.linalg.solve_banded on the same
 matrices in LAPACK's band storage ("banded").  The largest difference between the two in the S-norm is the fp64 noise of the scheme
-on a case (delta_ref).  Packets are (nch, n); matrices are (n, n) per channel."""
+on a case (delta_ref).  A third way ("lu") solves with tests/band_lu_ref.py, the plain banded LU in the device solvers' pivot rule,
+and takes its two fault knobs: what a kernel with a cut pivot search or dropped fill would return (test_tdse_split_pivots_cpu.py).
+Packets are (nch, n); matrices are (n, n) per channel."""
 import numpy as np
 import scipy.linalg
 
+import band_lu_ref as blu
 import resolvent_ref as ref
 import tdse_spline_ref as sref
 
@@ -26,14 +29,22 @@ def to_banded(M, b):
 
 
 class Solver:
-    """x = M^-1 b for a dense banded matrix, by numpy.linalg.solve ("dense") or scipy.linalg.solve_banded ("banded")"""
-    def __init__(self, M, b, how):
+    """x = M^-1 b for a dense banded matrix, by numpy.linalg.solve ("dense"), scipy.linalg.solve_banded ("banded") or band_lu_ref
+    ("lu": factored here once, with the knobs max_pivot_distance and fill_width of band_lu_ref.factor where given)"""
+    def __init__(self, M, b, how, **knobs):
+        assert how in ("dense", "banded", "lu") and (how == "lu" or not knobs)
         self.M, self.b, self.how = M, b, how
         self.ab = to_banded(M, b) if how == "banded" else None
+        if how == "lu":
+            with np.errstate(all="ignore"):                    # a mutant may divide by a pivot that is zero
+                self.LU, self.piv, _ = blu.factor(M, b, **knobs)
 
     def __call__(self, rhs):
         if self.how == "dense":
             return np.linalg.solve(self.M, rhs)
+        if self.how == "lu":
+            with np.errstate(all="ignore"):
+                return blu.substitute(self.LU, self.piv, rhs, self.b)
         return scipy.linalg.solve_banded((self.b, self.b), self.ab, rhs)
 
 
@@ -57,14 +68,15 @@ def s_norm(S, c):
     return float(np.sqrt(max(sum(np.real(np.vdot(v, S @ v)) for v in c), 0.0)))
 
 
-def propagate(SB, HB, l, dt, c0, G, Q, lam, f, WB=None, w=None, P=None, how="dense"):
+def propagate(SB, HB, l, dt, c0, G, Q, lam, f, WB=None, w=None, P=None, how="dense", knobs=None):
     """len(f) steps of ONE packet c0 (nch, n); f: the complex field value per step; G a full band (2k-1, n); Q (nch, nch), lam (nch,).
-    Returns (c, the packets after every step (nsteps, nch, n), the rows of the steps 0 .. nsteps (nsteps + 1, nch + 2 nproj))."""
+    knobs: band_lu_ref's fault knobs for how = "lu", on every solve of the run.  Returns (c, the packets after every step (nsteps, nch, n), the rows of the steps 0 .. nsteps (nsteps + 1, nch + 2 nproj))."""
     nch, b = len(l), SB.shape[0] - 1
     S = ref.upper_to_dense(SB)
     Gd = ref.full_to_dense(np.asarray(G).reshape(2 * b + 1, -1)) if G is not None else None
     Q, lam = np.asarray(Q, dtype=np.float64).reshape(nch, nch), np.asarray(lam, dtype=np.float64).reshape(nch)
-    atomic = [Solver(M, b, how) for M in atomic_matrices(SB, HB, l, dt, WB, w)]
+    knobs = knobs or {}
+    atomic = [Solver(M, b, how, **knobs) for M in atomic_matrices(SB, HB, l, dt, WB, w)]
     c = np.array(c0, dtype=np.complex128).reshape(nch, -1)
     g = 8.0 / dt
 
@@ -75,7 +87,7 @@ def propagate(SB, HB, l, dt, c0, G, Q, lam, f, WB=None, w=None, P=None, how="den
     for fn in np.asarray(f, dtype=np.complex128).reshape(-1):
         c = half(c)
         d = Q.T @ c                                             # d_j = sum_c Q(c, j) c_c
-        d = np.stack([2.0 * Solver(S + 0.5j * dt * fn * lam[j] * Gd, b, how)(S @ d[j]) - d[j] for j in range(nch)])
+        d = np.stack([2.0 * Solver(S + 0.5j * dt * fn * lam[j] * Gd, b, how, **knobs)(S @ d[j]) - d[j] for j in range(nch)])
         c = half(Q @ d)                                         # c_c = sum_j Q(c, j) d_j
         traj.append(c)
         rows.append(sref.row(SB, c, P))

@@ -8,6 +8,7 @@ import pytest
 import torch                               # first: its HIP runtime is the one the process uses
 from test_gpu_stages import input_from_case, note
 
+import pivot_designs
 import resolvent_ref as ref
 from bspatom_amd import capi, host
 
@@ -21,6 +22,8 @@ HYD = dict(kind_grid=0, ra=0.0, rb=40.0, k=9, nfun=96, l_fin=1, l_ini=0, n0_ini=
 def _input(name):
     if name == "k16_n40":
         return capi.make_input(**K16)
+    if name == "k10_n65":
+        return capi.make_input(**pivot_designs.GRIDS[name])
     if name == "c5_k11_n130":
         return input_from_case("c5_1024_k11", nfun=130)
     return input_from_case(name)

@@ -91,10 +91,10 @@ def _coupled_case(entry, name, nch, kinds):
 @pytest.mark.parametrize("name", pd.SINGLE_CASES)
 def test_single_channel_far_pivots(name):
     """bspatom_resolvent on design (A), which enters through W: two matrices (t = 20 on l = 0, t = 2 on l = 1), every second group of
-    k - 1 columns pivots at distance b = k - 1 and U's rows are 2 b wide; b = 3 (n65_k4), 8 (lin256), 15, the limit of the one-wave
-    window (k16_n40).  The criterion of test_gpu_resolvent's T1.  The single-channel call cannot cancel its base (W enters as -i W
-    alone), so it gets no exactly singular case.  Measured on the MI355X, maximum of omega / max(omega_ref, eps): n65_k4 0.249,
-    lin256 1.0, k16_n40 0.162."""
+    k - 1 columns pivots at distance b = k - 1 and U's rows are 2 b wide; b = 3 (n65_k4), 8 (lin256), 9, the instance for b <= 15 with
+    rows of its register window unused (k10_n65), 15, the limit of the one-wave window (k16_n40).  The criterion of
+    test_gpu_resolvent's T1.  The single-channel call cannot cancel its base (W enters as -i W alone), so it gets no exactly singular
+    case.  Measured on the MI355X, maximum of omega / max(omega_ref, eps): n65_k4 0.249, lin256 1.0, k10_n65 0.135, k16_n40 0.162."""
     prob, SB, HB, _, _ = _assembled(name)
     n = prob.nfun
     sy = pd.design_a_single(SB, HB)

@@ -22,8 +22,8 @@ same = single._same
 DT = 0.05
 NSCAN, SLOTS, GROUP, OBS_EVERY, SNAP_EVERY = 5, 2, 3, 2, 3
 # (fixture, nch, nsteps): n = 8 below the window width 2b + 1; n one past a wave multiple; b = 8; b = 15, the full register window;
-# a single channel
-SHAPES = [("tiny8", 2, 7), ("n65_k4", 3, 7), ("lin256", 4, 7), ("k16_n40", 4, 2), ("n65_k4", 1, 3)]
+# a single channel; b = 9: the instances for b <= 15 with rows of the register window unused (pivot_designs.GRIDS)
+SHAPES = [("tiny8", 2, 7), ("n65_k4", 3, 7), ("lin256", 4, 7), ("k16_n40", 4, 2), ("n65_k4", 1, 3), ("k10_n65", 3, 3)]
 CASES = [(name, nch, nsteps, absorb) for name, nch, nsteps in SHAPES for absorb in (False, True)]
 IDS = ["%s-nch%d-%s" % (c[0], c[1], "cap" if c[3] else "nocap") for c in CASES]
 
