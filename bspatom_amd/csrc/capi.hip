@@ -98,6 +98,9 @@ const OptName OPT_TABLE[] = {
     {"cw_items4", "BSP_CW_ITEMS4", &Options::cw_items4},
     {"cw_bcast", "BSP_CW_BCAST", &Options::cw_bcast},
     {"cw_nw", "BSP_CW_NW", &Options::cw_nw},
+    {"cw_spread", "BSP_CW_SPREAD", &Options::cw_spread},
+    {"cw_spread_cap4", "BSP_CW_SPREAD_CAP4", &Options::cw_spread_cap4},
+    {"cw_spread_cap2", "BSP_CW_SPREAD_CAP2", &Options::cw_spread_cap2},
     {"cw_ldspad", "BSP_CW_LDSPAD", &Options::cw_ldspad},
     {"cw_ipw", "BSP_CW_IPW", &Options::cw_ipw},
     {"cw_band8", "BSP_CW_BAND8", &Options::cw_band8},

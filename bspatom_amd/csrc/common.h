@@ -109,6 +109,11 @@ struct Options {
     int cw_onediv = 0;           // BSP_CW_ONEDIV: reflectors of the band route's RQ loop in the one-division form (A/B switch)
     int cw_bcast = 1;            // BSP_CW_BCAST: crawford_item4_kernel's reflector row 1 = as a DPP operand of the FMAs (row_newbcast; half the
                                  // registers and LDS, four waves per SIMD), 0 = through LDS (the cross-check); bit-identical results
+    int cw_spread = 1;           // BSP_CW_SPREAD: a quad's congruences (phase B of crawford_item4_kernel's DPP form) on the waves of a workgroup, one
+                                 // SIMD each: 0 = never, 1 (the default) = on 4 / 2 waves where the launch has at most cw_spread_cap4 / cw_spread_cap2 quads over all
+                                 // channels, 2 / 4 = on that many waves at every launch (the tests' hook); bit-identical results
+    int cw_spread_cap4 = -1;     // BSP_CW_SPREAD_CAP4, BSP_CW_SPREAD_CAP2: the two caps of cw_spread=1 in quads per launch (-1 = the measured ones,
+    int cw_spread_cap2 = -1;     // crawford.hip::CW_SPREAD_CAP4 / 2, scaled by the chip's CUs)
     int dipole_stage_mb = 0;    // BSP_DIPOLE_STAGE_MB: > 0 = device scratch of one group of pairs of bspatom_dipole_matrix in MB (0 = 2 GiB); small
                                  // values force several groups (the results do not depend on the grouping: the test's hook)
     int wf_stage_mb = 0;         // BSP_WF_STAGE_MB: > 0 = device staging of bspatom_tabulate / bspatom_wavefunctions (U and dU of one group of vectors,

@@ -442,12 +442,20 @@ __device__ __forceinline__ void rq4_step_dpp(double (&x)[16], double (&q)[16], c
 // The work of one wave on its (up to) four items of wavefront t of channel `chan`: items idx0 .. idx0 + ipw - 1 of the wavefront's
 // list (nch chase items j = jlo .., then the elimination jel if any).  Qsw / Bcw: the wave's LDS (4 x 16 x QLD and 4 x 16 doubles).
 // BCAST: the reflector row by DPP (rq4_step_dpp), no Bcw, and Qsw IS Wsw: phase B's operands are in registers before Q is stored.
-template <bool ONEDIV, bool BCAST>
+// SPREAD = S > 1 (DPP form, ipw = 4): the quad belongs to a WORKGROUP of S waves, `wave` its number in it, Qsw and Wsw the
+// workgroup's and apart.  Wave 0 runs phase A for all four items as ever (an item is a DPP row: one item costs what four cost);
+// phase B, whose four congruences a lone wave issues one after the other into one SIMD's matrix pipe, is dealt out: wave w
+// requests the operands of the slots s with s S / 4 == w, holds them in registers while wave 0 works, and after ONE barrier (Q
+// is in LDS) runs the per-item body below for those slots on its own SIMD.  An item's arithmetic is the same whoever runs it.
+template <bool ONEDIV, bool BCAST, int SPREAD = 1>
 __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo, int nch, int jel, const int ipw, const int nlh,
                                         const int qstride, const int nlead, const int chan, const int idx0, const int lane,
                                         double *Qsw, double *Bcw, double *Wsw, const double *__restrict__ Qel, double *Dall, double *Eall,
-                                        double *Gall, double *Uall, unsigned long long *diag)
+                                        double *Gall, double *Uall, unsigned long long *diag, const int wave = 0)
 {
+    static_assert(SPREAD == 1 || (BCAST && (SPREAD == 2 || SPREAD == 4)), "phase B over 2 or 4 waves: the DPP form only");
+    constexpr int NS = 4 / SPREAD;                                         // item slots of a wave in phase B
+    const int s0 = SPREAD > 1 ? wave * NS : 0;                             // ... the first of them (uniform)
     unsigned long long ts0 = 0, tsa = 0, tsb = 0, tsc = 0, tsd = 0, tse = 0;
     if (diag) ts0 = __builtin_amdgcn_s_memtime();
     if (chan >= nlh) {                                                     // a leading part of nlead blocks: the items beyond do not exist
@@ -464,7 +472,8 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     // memory, 576 B from lanes 0 .. 35 (the others are masked off: a lane's 16 bytes land at 16 x its number, so the image in Wsw is
     // the same 576 B); E_p goes with the block in front of the window, E_{p-1} (E_p again where there is none), 1 KB. ----
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int k = 0; k < NS; ++k) {
+        const int s = s0 + k;
         const int idx = idx0 + s;
         const int kd = s >= ipw ? 0 : (idx < nch ? 1 : ((idx == nch && jel > 0) ? 2 : 0));
         if (kd != 0) {                                                   // uniform
@@ -481,7 +490,7 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     }
 
     // phase B's operands as they lie in Wsw (the lane's places in the layout of the matrix cores; they do not depend on the item)
-    double wv[4][4], sdv[4][2];
+    double wv[NS][4], sdv[NS][2];                                          // (slot s0 + k at [k])
     auto read_ws = [&]() {
         const int g = lane >> 4, c8 = lane & 7;
         const bool left = (lane & 15) < CB;
@@ -496,19 +505,19 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
             om[r] = 3 * CBB + R * CB + c8;
         }
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const double *W0 = Wsw + s * 4 * CBB;
+        for (int k = 0; k < NS; ++k) {
+            const double *W0 = Wsw + (s0 + k) * 4 * CBB;
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                wv[s][r] = W0[oa[r]];
-                wv[s][r + 2] = W0[ob[r]];
-                sdv[s][r] = W0[om[r]];
+                wv[k][r] = W0[oa[r]];
+                wv[k][r + 2] = W0[ob[r]];
+                sdv[k][r] = W0[om[r]];
             }
         }
     };
 
     // ---- phase A: the RQ loops of the wave's chase items, an item per DPP row ----
-    if (idx0 < nch) {
+    if (idx0 < nch && (SPREAD == 1 || wave == 0)) {
         const int it = lane >> 4, r = lane & 15;
         const int idx = idx0 + it;
         const bool live = idx < nch && it < ipw && r < CB;               // lanes that hold a row of X
@@ -570,6 +579,13 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     if constexpr (BCAST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the DMA was waited for before Q took its place)
     else if (idx0 < nch) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    // SPREAD: wave 0's Q is in LDS (the wait above), the others hold their operands: the one meeting of the workgroup.  The bare
+    // instruction, not __syncthreads(): that one also waits until memory has acknowledged the stores of R (vmcnt(0)), which no
+    // wave of the workgroup reads -- only LDS crosses this barrier.
+    if constexpr (SPREAD > 1) {
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    }
     // Everything phase B computes from the kernel's arguments (item numbers, block addresses of four items) would otherwise be
     // hoisted in front of phase A and sit in registers across it (96 dwords spilled at three waves per SIMD): the two values it
     // all derives from are redefined here, as far as the compiler can tell.
@@ -585,7 +601,7 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     // memory per wave instead of one per item. ----
     const int g = lane >> 4, c = lane & 15, c8 = c & 7;
     const bool left = c < CB;
-    int kind[4], jj[4], pp[4];                                           // kind: 0 none, 1 chase, 2 elimination
+    int kind[NS], jj[NS], pp[NS];                                        // kind: 0 none, 1 chase, 2 elimination
     // where the lane's two elements of the window's diagonal blocks go: a lane of the left half holds (4 r + g, c8) of D_p, one of
     // the right half that of D_{p+1}.  Row >= column: into the records, one run of 2 CWD doubles from D_p (one store under one mask
     // for both halves).  The others are not stored -- except block 0's, which go to the side array.
@@ -599,19 +615,19 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     double qe[4], xt[2] = {0.0, 0.0};
     if constexpr (!BCAST) read_ws();
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int idx = idx0b + s;
-        kind[s] = s >= ipw ? 0 : (idx < nch ? 1 : ((idx == nch && jel > 0) ? 2 : 0));
-        jj[s] = kind[s] == 1 ? jlo + idx : (kind[s] == 2 ? jel : jlo + idx0b);
-        pp[s] = kind[s] == 2 ? jel - 1 : jj[s] - 2 - (t - 2 * jj[s]);
-        if (kind[s] == 0) { jj[s] = jj[0]; pp[s] = pp[0]; }
+    for (int k = 0; k < NS; ++k) {
+        const int s = s0 + k, idx = idx0b + s;
+        kind[k] = s >= ipw ? 0 : (idx < nch ? 1 : ((idx == nch && jel > 0) ? 2 : 0));
+        jj[k] = kind[k] == 1 ? jlo + idx : (kind[k] == 2 ? jel : jlo + idx0b);
+        pp[k] = kind[k] == 2 ? jel - 1 : jj[k] - 2 - (t - 2 * jj[k]);
+        if (kind[k] == 0) { jj[k] = jj[0]; pp[k] = pp[0]; }
 #pragma unroll
-        for (int r = 0; r < 2; ++r) sdv[s][r] = (pp[s] >= 1 && left) ? sdv[s][r] : 0.0;
+        for (int r = 0; r < 2; ++r) sdv[k][r] = (pp[k] >= 1 && left) ? sdv[k][r] : 0.0;
     }
     // the elimination of this wavefront, if this wave holds it (at most one, the last item): its Q and E_j
     int se = -1;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) if (kind[s] == 2) se = s;
+    for (int k = 0; k < NS; ++k) if (kind[k] == 2) se = k;
     const bool has_x = se >= 0 && (jel + 1 <= N - 1);
     if (se >= 0) {
         const double *Qj = Qel + ((int)chan >= nlh ? qstride : 0) + (size_t)jel * 256;
@@ -626,14 +642,14 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
     }
     if (diag) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tsd = __builtin_amdgcn_s_memtime(); }   // phase B's operands have arrived
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        if (kind[s] == 0) break;
-        const bool elim = kind[s] == 2;
-        const int p = pp[s];
+    for (int k = 0; k < NS; ++k) {
+        if (kind[k] == 0) break;
+        const bool elim = kind[k] == 2;
+        const int p = pp[k];
         double *D0 = D + (size_t)p * CWD, *E0 = E + (size_t)p * CBB;
         double q[4];
         if (!elim) {
-            const double *qs = Qsw + s * (16 * QLD);
+            const double *qs = Qsw + (s0 + k) * (16 * QLD);
 #pragma unroll
             for (int r = 0; r < 4; ++r) q[r] = qs[(4 * r + g) * QLD + c];
         } else {
@@ -642,12 +658,12 @@ __device__ __forceinline__ void cw_quad(const int N, const int t, const int jlo,
         }
         double4_t P = {0.0, 0.0, 0.0, 0.0}, Wn = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) P = cw_mfma(wv[s][r], q[r], P);
+        for (int r = 0; r < 4; ++r) P = cw_mfma(wv[k][r], q[r], P);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Wn = cw_mfma(q[r], P[r], Wn);
         double4_t O = {0.0, 0.0, 0.0, 0.0};
-        O = cw_mfma(q[0], sdv[s][0], O);
-        O = cw_mfma(q[1], sdv[s][1], O);
+        O = cw_mfma(q[0], sdv[k][0], O);
+        O = cw_mfma(q[1], sdv[k][1], O);
         // The results as scalars the compiler cannot see through: (1) left ? Wn[r] : Wn[r + 2] as a select between vector elements
         // becomes an element picked by a computed index, a chain of six selects; (2) the products of O stay in front of the first
         // masked store, among the other products -- behind it they wait for nothing but themselves, once per item.
@@ -727,6 +743,26 @@ __global__ __launch_bounds__(64 * NW, (BCAST ? 16 : 8) / NW) void crawford_item4
     cw_quad<ONEDIV, BCAST>(N, t, jlo, nch, jel, ipw, nlh, qstride, nlead, (int)blockIdx.y, (blockIdx.x * NW + wave) * ipw, lane,
                            &Qs[wave][0][0], BCAST ? nullptr : &Bc[wave][0][0], Wsw + wave * (BCAST ? 4 * 16 * QLD : 4 * 4 * CBB), Qel, Dall,
                            Eall, Gall, Uall, diag);
+}
+
+// The same quad on a workgroup of SPREAD waves (cw_quad: phase A on wave 0, phase B's four congruences on SPREAD SIMDs), for the
+// launches that leave most of the chip's SIMDs without a wave (crawford_run chooses).  grid = (quads, channels), four items per
+// quad.  Q and phase B's operands lie apart, 17 KB per workgroup: where these launches run, nothing competes for the LDS.
+template <bool ONEDIV, int SPREAD>
+__global__ __launch_bounds__(64 * SPREAD, 16 / SPREAD) void crawford_item4_spread_kernel(int N, int t, int jlo, int nch, int jel, int nlh, int qstride,
+                                                            int nlead, const double *__restrict__ Qel, double *Dall, double *Eall, double *Gall,
+                                                            double *Uall, unsigned long long *diag)
+{
+    __builtin_amdgcn_s_setprio(3);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // BSP_CW_DIAG: wave 0 reports -- it runs phase A and then its share of phase B: its "R, Q stored" holds the wait at the barrier,
+    // its "congruences issued" is a phase-B wave's
+    if (diag && (wave != 0 || ((blockIdx.x & 7) | (blockIdx.y & 7)) != 0)) diag = nullptr;
+    __shared__ __attribute__((aligned(16))) double Qs[4][16 * QLD];
+    __shared__ __attribute__((aligned(16))) double Wop[4][4 * CBB];
+    cw_quad<ONEDIV, true, SPREAD>(N, t, jlo, nch, jel, 4, nlh, qstride, nlead, (int)blockIdx.y, (int)blockIdx.x * 4, lane, &Qs[0][0], nullptr,
+                                  &Wop[0][0], Qel, Dall, Eall, Gall, Uall, diag, wave);
 }
 
 // index-reversed overlap band: SBf[d][i] = S_f(i, i + d) = S(n-1-i-d, n-1-i)
@@ -1079,6 +1115,9 @@ CwShape cw_shape(int n)
 }
 // The factor in chunks (crawford_prepare with events): columns per chunk, a multiple of 128 (whole blocks, whole load chunks of the
 // Cholesky kernel); one chunk for the small pencils, whose whole factor takes less than a launch or two of the reduction.
+// BSP_CW_SPREAD=1: a launch of at most this many quads (all channels, all groups) at 256 CUs runs its quads on 4 / on 2 waves
+// (in proportion on a chip of another size; the sweep: profiles/r26_cw_spread.txt)
+constexpr long CW_SPREAD_CAP4 = 1024, CW_SPREAD_CAP2 = 2048;
 int cw_chunk_cols(int n) { return n < opts().cw_chunk_min ? n + 128 : ((n + CW_CHUNKS - 1) / CW_CHUNKS + 127) / 128 * 128; }
 }  // namespace
 
@@ -1157,6 +1196,28 @@ int crawford_run(LaunchCtx &cx, int n, int npad, int k, int nl, const double *d_
             const int waves = (items + ipw - 1) / ipw;
             const dim3 grid((waves + nw - 1) / nw, cy), block(64 * nw);
             const size_t pad = (size_t)opts().cw_ldspad * 1024;
+            // SPREAD (BSP_CW_SPREAD): a quad's congruences on 4 or 2 waves of a workgroup (crawford_item4_spread_kernel) on the launches
+            // that leave SIMDs empty.  The rule reads the launch's own shape only -- the quads of this wavefront over ALL channels of the
+            // batch, whichever group launches them -- so every solve of one (n, nl) takes the same path; the bits are the same on
+            // every path.  The run from both ends, BSP_CW_NW=4, BSP_CW_IPW, BSP_CW_BCAST=0 and the one-item kernel keep one wave per quad.
+            int spread = 1;
+            if (opts().cw_spread > 0 && opts().cw_bcast && nw == 1 && ipw == 4 && !split) {
+                if (opts().cw_spread == 2 || opts().cw_spread == 4) spread = opts().cw_spread;
+                else {
+                    const long quads = (long)waves * ny, cus = device_cus();
+                    const long cap4 = opts().cw_spread_cap4 >= 0 ? opts().cw_spread_cap4 : CW_SPREAD_CAP4 * cus / 256;
+                    const long cap2 = opts().cw_spread_cap2 >= 0 ? opts().cw_spread_cap2 : CW_SPREAD_CAP2 * cus / 256;
+                    spread = quads <= cap4 ? 4 : (quads <= cap2 ? 2 : 1);
+                }
+            }
+            if (spread > 1) {
+#define CW_LAUNCHS(OD, S)                                                                                                            \
+    hipLaunchKernelGGL((crawford_item4_spread_kernel<OD, S>), dim3(waves, cy), dim3(64 * S), 0, ws, Ns, t, jlo, nch, jel, nl, qstride, nlead, w.Qel, gD, gE, gG, gU, dg)
+                if (opts().cw_onediv) { if (spread == 4) CW_LAUNCHS(true, 4); else CW_LAUNCHS(true, 2); }
+                else { if (spread == 4) CW_LAUNCHS(false, 4); else CW_LAUNCHS(false, 2); }
+#undef CW_LAUNCHS
+                return;
+            }
 #define CW_LAUNCH4(OD, NWV, BC, G, B, LDS)                                                                                           \
     hipLaunchKernelGGL((crawford_item4_kernel<OD, NWV, BC>), G, B, LDS, ws, Ns, t, jlo, nch, jel, ipw, nl, qstride, nlead, w.Qel, gD, gE, gG, gU, dg)
             if (opts().cw_bcast) {
