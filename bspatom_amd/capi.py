@@ -888,6 +888,32 @@ class Problem:
                 coef = np.ascontiguousarray(np.broadcast_to(coef, (nsteps, nscan, ncoup, nop)))
         return l.size, l, w, cr, cc, ctr, coef
 
+    @staticmethod
+    def _split_system(l, w, Q, lam):
+        """(nch, l int32 (nch,), w int32 (nch,) or None, Q float64 (nch, nch) or None, lam float64 (nch,) or None), contiguous"""
+        nch, l, w = Problem._spline_system(l, w, None, None, 0, 0, 0)[:3]
+        Q = None if Q is None else np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(nch, nch))
+        lam = None if lam is None else np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(nch))
+        return nch, l, w, Q, lam
+
+    def _spline_run(self, nch, c0, W, P, nsteps, obs_every, snap_every, nexp=0):
+        """what the host calls of tdse_spline and tdse_split share: (nabs, W (nabs, 2k-1, nfun) or None, nscan, c complex (nscan, nch,
+        nfun), a copy of c0, nproj, P (nproj, nch, nfun) or None (without rows), snaps, obs with rows nch + 2 nproj + 2 nexp wide, info,
+        result), contiguous; result() is what the calls return once the entry point has filled the arrays"""
+        n = self.nfun
+        W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
+        c = np.array(c0, dtype=np.complex128, order="C")
+        one = c.ndim == 2
+        c = np.ascontiguousarray(c.reshape(-1, nch, n))
+        nscan = c.shape[0]
+        P = None if P is None or obs_every < 1 else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, nch, n))
+        nproj = 0 if P is None else P.shape[0]
+        snaps = np.zeros((nsteps // snap_every, nscan, nch, n), dtype=np.complex128) if snap_every > 0 else None
+        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj + 2 * nexp)) if obs_every > 0 else None
+        info = np.zeros(nscan, dtype=np.int32)
+        result = lambda: (c[0] if one else c, info) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+        return 0 if W is None else W.shape[0], W, nscan, c, nproj, P, snaps, obs, info, result
+
     def tdse_spline(self, l, c0, dt, nsteps, couplings=None, G=None, coef=None, W=None, w=None, P=None, obs_every=0, snap_every=0):
         """nsteps Crank-Nicolson steps dt of i S dc/dt = (sum_c (H_l[c] - i W_w[c]) + V(t)) c in the B-spline basis itself
         (bspatom_tdse_spline): the whole continuum of the box, any absorber, any coupling, one banded LU per step and packet, the
@@ -908,25 +934,14 @@ class Problem:
 
     def _tdse_spline(self, entry, l, c0, dt, nsteps, couplings, G, coef, W, w, P, obs_every, snap_every):
         """the body of tdse_spline and tdse_spline_wide: the arrays of the call, the entry point by name"""
-        n = self.nfun
-        W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
-        G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
-        nabs, nop = 0 if W is None else W.shape[0], 0 if G is None else G.shape[0]
-        c = np.array(c0, dtype=np.complex128, order="C")
-        one = c.ndim == 2
-        nch = np.asarray(l).size
-        c = np.ascontiguousarray(c.reshape(-1, nch, n))
-        nscan = c.shape[0]
+        G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(-1, 2 * self.k - 1, self.nfun))
+        nop = 0 if G is None else G.shape[0]
+        nabs, W, nscan, c, nproj, P, snaps, obs, info, result = self._spline_run(np.asarray(l).size, c0, W, P, nsteps, obs_every, snap_every)
         nch, l, w, cr, cc, ctr, coef = self._spline_system(l, w, couplings, coef, nscan, nsteps, nop)
-        P = None if P is None or obs_every < 1 else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, nch, n))
-        nproj = 0 if P is None else P.shape[0]
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, n), dtype=np.complex128) if snap_every > 0 else None
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj)) if obs_every > 0 else None
-        info = np.zeros(nscan, dtype=np.int32)
         _chk(getattr(lib(), entry)(self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), 0 if cr is None else cr.size, _p(cr), _p(cc), _p(ctr),
                                    nop, _p(G), nsteps, float(dt), _p(coef), _p(c), snap_every, _p(snaps), obs_every, nproj, _p(P),
                                    _p(obs), _p(info)), entry)
-        return (c[0] if one else c, info) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+        return result()
 
     def tdse_spline_dev(self, l, nscan, nsteps, dt, c_ptr, couplings=None, nop=0, G_ptr=None, coef_ptr=None, nabs=0, W_ptr=None, w=None,
                         nproj=0, P_ptr=None, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None):
@@ -1008,19 +1023,10 @@ class Problem:
 
     def _tdse_split(self, l, c0, dt, nsteps, G, Q, lam, f, W, w, P, obs_every, snap_every, expect):
         """the body of tdse_split and tdse_split_observe: the arrays of the call; expect None: bspatom_tdse_split"""
-        n = self.nfun
-        W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, 2 * self.k - 1, n))
-        nabs = 0 if W is None else W.shape[0]
-        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
-        nch = l.size
-        w = None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), l.shape))
-        c = np.array(c0, dtype=np.complex128, order="C")
-        one = c.ndim == 2
-        c = np.ascontiguousarray(c.reshape(-1, nch, n))
-        nscan = c.shape[0]
-        G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(2 * self.k - 1, n))
-        Q = None if Q is None else np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(nch, nch))
-        lam = None if lam is None else np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(nch))
+        nch, l, w, Q, lam = self._split_system(l, w, Q, lam)
+        nexp, B, GE = self._expect_operators(nch, expect if obs_every > 0 else None)
+        nabs, W, nscan, c, nproj, P, snaps, obs, info, result = self._spline_run(nch, c0, W, P, nsteps, obs_every, snap_every, nexp)
+        G = None if G is None else np.ascontiguousarray(np.asarray(G, dtype=np.float64).reshape(2 * self.k - 1, self.nfun))
         if f is not None and nsteps > 0:
             f = np.asarray(f, dtype=np.complex128)
             f = f[:, None] if f.ndim == 1 else f
@@ -1028,30 +1034,20 @@ class Problem:
             f = np.ascontiguousarray(np.broadcast_to(f, (nsteps, nscan)))
         else:
             f = None
-        P = None if P is None or obs_every < 1 else np.ascontiguousarray(np.asarray(P, dtype=np.complex128).reshape(-1, nch, n))
-        nproj = 0 if P is None else P.shape[0]
-        snaps = np.zeros((nsteps // snap_every, nscan, nch, n), dtype=np.complex128) if snap_every > 0 else None
-        nexp, B, GE = self._expect_operators(nch, expect if obs_every > 0 else None)
-        obs = np.zeros((self.tdse_nobs(nsteps, obs_every), nscan, nch + 2 * nproj + 2 * nexp)) if obs_every > 0 else None
-        info = np.zeros(nscan, dtype=np.int32)
         args = (self._h, nscan, nch, _p(l), nabs, _p(W), _p(w), _p(G), _p(Q), _p(lam), nsteps, float(dt), _p(f), _p(c), snap_every, _p(snaps),
                 obs_every, nproj, _p(P), _p(obs), _p(info))
         if expect is None:
             _chk(lib().bspatom_tdse_split(*args), "bspatom_tdse_split")
         else:
             _chk(lib().bspatom_tdse_split_observe(*args, nexp, _p(B), _p(GE)), "bspatom_tdse_split_observe")
-        return (c[0] if one else c, info) + (() if obs is None else (obs,)) + (() if snaps is None else (snaps,))
+        return result()
 
     def tdse_split_dev(self, l, nscan, nsteps, dt, c_ptr, G_ptr=None, Q=None, lam=None, f_ptr=None, nabs=0, W_ptr=None, w=None, nproj=0,
                        P_ptr=None, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None):
         """tdse_split with the packets (nscan * nch * nfun complex at c_ptr, advanced in place), G, W, the field table (nsteps * nscan
         complex), P, the rows and the snapshots in device memory of this problem's device, e.g. torch tensors' data_ptr(); l, w, Q and
         lam are host values.  Returns info (nscan,) when the result is there."""
-        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
-        nch = l.size
-        w = None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), l.shape))
-        Q = None if Q is None else np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(nch, nch))
-        lam = None if lam is None else np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(nch))
+        nch, l, w, Q, lam = self._split_system(l, w, Q, lam)
         info = np.zeros(nscan, dtype=np.int32)
         _chk(lib().bspatom_tdse_split_dev(self._h, nscan, nch, _p(l), nabs, _ptr(W_ptr), _p(w), _ptr(G_ptr), _p(Q), _p(lam), nsteps, float(dt),
                                           _ptr(f_ptr), _ptr(c_ptr), snap_every, _ptr(snap_ptr), obs_every, nproj, _ptr(P_ptr), _ptr(obs_ptr),
@@ -1062,11 +1058,7 @@ class Problem:
                                P_ptr=None, obs_every=0, obs_ptr=None, snap_every=0, snap_ptr=None, expect=None):
         """tdse_split_dev with expectation values along the run (bspatom_tdse_split_observe_dev): expect = (B, GE_ptr), B a host array
         (nexp, nch, nch), GE_ptr nexp * (2k-1) * nfun doubles in device memory; the rows at obs_ptr are nch + 2 nproj + 2 nexp wide."""
-        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
-        nch = l.size
-        w = None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), l.shape))
-        Q = None if Q is None else np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(nch, nch))
-        lam = None if lam is None else np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(nch))
+        nch, l, w, Q, lam = self._split_system(l, w, Q, lam)
         B, GE_ptr = (None, None) if expect is None else expect
         B = None if B is None else np.ascontiguousarray(np.asarray(B, dtype=np.float64).reshape(-1, nch, nch))
         info = np.zeros(nscan, dtype=np.int32)

@@ -1,6 +1,7 @@
 // capi_internal.h -- what the translation units of the C ABI share (capi.hip: handle, options, solve; capi_states.hip: the
 // consumers of the last solve; capi_stage.hip: the stage-level entry points).  Private to csrc.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <vector>
 #include "common.h"
@@ -111,4 +112,40 @@ inline int drain(bspatom_problem *p, int rc)
 inline int finish(bspatom_problem *p, int rc) { return (rc = drain(p, rc)) ? rc : invit_failed(p); }
 
 int ensure_vec_scratch(bspatom_problem *p);     // capi.hip: d_vwork, d_vec, d_chan, d_Esel for one vector
+
+// The bounds of a call's device scratch (capi_resolvent.hip, capi_spline.hip, capi_tdse.hip): resolvent_stage_mb for the work slots and a
+// group's X, tdse_stage_mb for what a stepped run's host variant stages (the table, the snapshots and the rows of one group of steps)
+inline size_t resolvent_stage_bytes() { return (size_t)(opts().resolvent_stage_mb > 0 ? opts().resolvent_stage_mb : 2048) << 20; }
+inline size_t tdse_stage_bytes() { return (size_t)(opts().tdse_stage_mb > 0 ? opts().tdse_stage_mb : 256) << 20; }
+
+// the work slots of a call: what the kernel's occupancy query gave, or resolvent_slots (the items at most), within the bound, one at least
+inline int bounded_slots(int queried, int items, size_t slot_doubles)
+{
+    if (opts().resolvent_slots > 0) queried = std::min(opts().resolvent_slots, items);
+    return (int)std::max<size_t>(1, std::min<size_t>(queried, resolvent_stage_bytes() / (slot_doubles * sizeof(double))));
+}
+
+// nrec records (l, w): every channel among the bands the handle holds, every absorber index -1 or among the nabs of WB (w null: none given)
+inline int screen_channels(const bspatom_problem *p, const int32_t *l, const int32_t *w, int nrec, int nabs)
+{
+    for (int m = 0; m < nrec; ++m) {
+        if (p->band_nl < 1 || l[m] < p->band_l0 || l[m] >= p->band_l0 + p->band_nl) return BSP_ERR_ARG;
+        if (w && (w[m] < -1 || w[m] >= nabs)) return BSP_ERR_ARG;
+    }
+    return BSP_OK;
+}
+// the coupling topology: blocks (cr, cc) among the nch channels, ctr 0 or 1
+inline int screen_couplings(int nch, int ncoup, const int32_t *cr, const int32_t *cc, const int32_t *ctr)
+{
+    for (int q = 0; q < ncoup; ++q)
+        if (cr[q] < 0 || cr[q] >= nch || cc[q] < 0 || cc[q] >= nch || ctr[q] < 0 || ctr[q] > 1) return BSP_ERR_ARG;
+    return BSP_OK;
+}
+// what the kernels read for screened records: the channel's place among the bands, its absorber (without w the first, -1: none)
+inline void select_channels(const bspatom_problem *p, const int32_t *l, const int32_t *w, int nrec, int nabs, std::vector<int> &chan, std::vector<int> &wsel)
+{
+    chan.resize(nrec);
+    wsel.assign(nrec, nabs > 0 && !w ? 0 : -1);
+    for (int m = 0; m < nrec; ++m) { chan[m] = l[m] - p->band_l0; if (w) wsel[m] = w[m]; }
+}
 }  // namespace bsp

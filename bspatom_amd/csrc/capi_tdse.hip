@@ -12,8 +12,6 @@
 using namespace bsp;
 
 namespace {
-constexpr size_t TDSE_STAGE_BYTES = (size_t)256 << 20;
-size_t tdse_stage_bytes() { return opts().tdse_stage_mb > 0 ? (size_t)opts().tdse_stage_mb << 20 : TDSE_STAGE_BYTES; }
 // attempts enqueued between two looks at the control block (tdse_adapt_group: the test's hook; nothing depends on it)
 int adapt_group() { return opts().tdse_adapt_group > 0 ? opts().tdse_adapt_group : 16; }
 

@@ -14,7 +14,7 @@
 //   3. rw_factor with nrhs = 1, rw_backsolve;
 //   4. the update (ts_update) and the snapshot when due.
 // A wide step is slow -- tens to hundreds of milliseconds -- so the host keeps launches shorter than tdse_spline.hip's 64 steps
-// (capi_resolvent.hip: the launch-length rule).
+// (capi_spline.hip: the launch-length rule).
 #include "common.h"
 #include "wave_ops.h"
 #include "resolvent_shared.h"
