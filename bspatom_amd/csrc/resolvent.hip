@@ -11,19 +11,24 @@
 //
 // Arithmetic, fixed: pivot by |Re| + |Im| (LAPACK's cabs1), ties to the smallest row; a complex product is the plain four-product
 // form (ac - bd, ad + bc); one reciprocal per pivot (scaled by cabs1, so that it neither overflows nor underflows), kept in U's
-// diagonal slot and multiplied with in the factorisation and in the back substitution.  With Im z = 0, no absorber and real
+// diagonal slot and multiplied with in the factorisation and in the back substitution.  The factorisation and the two substitutions
+// are band_lu_wave.h's wave_lu_factor and wave_lu_solve with the policy WaveLuResolvent, the matrix comes in as RsPencil; the whole
+// file is compiled with contraction off and every multiply-add is written out (DESIGN.md 4.7 "Fused products").  With Im z = 0, no absorber and real
 // right-hand sides every imaginary part is a sum of products with a zero factor: +-0.0 throughout (G3 of include/bspatom.h).
 // A matrix is one item, its right-hand sides are solved one after the other: nothing of an x depends on the other matrices, on the
 // number of right-hand sides or projections, or on the slot that took the item (G2).
 //
 // Beyond second order the amplitudes are PRODUCTS of resolvents with an operator in between, p^T G(z2) A2 G(z1) A1 c: the second
-// solve's right-hand side is the first one's solution.  resolvent_chain_kernel keeps such a chain on its wave: the same rs_factor
-// and rs_solve per stage, and between the stages rs_band_apply, y = (sum_o a_o G_o) x in fixed no-FMA arithmetic (C1 - C6 of
+// solve's right-hand side is the first one's solution.  resolvent_chain_kernel keeps such a chain on its wave: the same
+// wave_lu_factor and wave_lu_solve per stage, and between the stages rs_band_apply, y = (sum_o a_o G_o) x in fixed no-FMA arithmetic (C1 - C6 of
 // include/bspatom.h: a stage is bit for bit what resolvent_kernel gives for that right-hand side).  What this file shares with
-// resolvent_coupled.hip and resolvent_wide.hip -- the pivot rule, the reciprocal, the forward substitution -- is in resolvent_shared.h.
+// resolvent_coupled.hip and resolvent_wide.hip -- the pivot rule, the reciprocal -- is in resolvent_shared.h.
 #include "common.h"
 #include "wave_ops.h"
 #include "resolvent_shared.h"
+#include "band_lu_wave.h"
+
+#pragma clang fp contract(off)             // every multiply-add of this file is written out
 
 namespace bsp {
 namespace {
@@ -36,175 +41,38 @@ __host__ __device__ inline size_t rs_slot_doubles(int n, int k)
     return 2 * ((size_t)n * (2 * b + 1) + (size_t)n * b + (size_t)n) + piv + (piv & 1);
 }
 
-// M(r, c); SB, HB upper bands [k][n] used symmetrically (eigvec.hip::pencil_entry), WB the absorber's FULL band [2k-1][n] with
-// WB[d + b][i] = W(i, i + d), both triangles as given, or null
-__device__ __forceinline__ void rs_entry(const double *__restrict__ SB, const double *__restrict__ HB, const double *__restrict__ WB,
-                                         int n, int b, double zr, double zi, int r, int c, double &re, double &im)
-{
-    const int d = (r > c) ? (r - c) : (c - r);
-    re = 0.0; im = 0.0;
-    if (d > b || r < 0 || c < 0 || r >= n || c >= n) return;
-    const int lo = (r > c) ? c : r;
-    const double s = SB[(size_t)d * n + lo];
-    re = HB[(size_t)d * n + lo] - zr * s;
-    im = -(zi * s);
-    if (WB) im -= WB[(size_t)(c - r + b) * n + r];
-}
-
-// The factorisation P M = L U of one matrix by one wavefront.  U: [n][2b+1] complex, row j = (1 / pivot, U(j, j+1 .. j+2b));
-// Lm: [n][b] complex multipliers; piv: [n] pivot rows.  Returns the number of pivots that were replaced by pertol.
-template <int BT>
-__device__ __forceinline__ int rs_factor(int n, int b, const double *__restrict__ SB, const double *__restrict__ HB,
-                                         const double *__restrict__ WB, const double zr, const double zi, double2 *U, double2 *Lm,
-                                         int *piv, const int lane)
-{
-    constexpr int PF = RS_PF;
-    // scale of the zero-pivot perturbation (rs_pertol)
-    double dmax = 0.0, dflo = 0.0;
-    for (int j = lane; j < n; j += 64) {
+// The matrix of an item, wave_lu_factor's argument.  SB, HB upper bands [k][n] used symmetrically (eigvec.hip::pencil_entry), WB the
+// absorber's FULL band [2k-1][n] with WB[d + b][i] = W(i, i + d), both triangles as given, or null.  entry: M(r, c); diag: |M(j,j)| by
+// cabs1 and the sum of the magnitudes of its terms (rs_pertol).  h - zr s and -(zi s) - w round once.
+struct RsPencil {
+    const double *SB, *HB, *WB;
+    int n, b;
+    double zr, zi;
+    __device__ __forceinline__ void entry(int r, int c, double &re, double &im) const
+    {
+        const int d = (r > c) ? (r - c) : (c - r);
+        re = 0.0; im = 0.0;
+        if (d > b || r < 0 || c < 0 || r >= n || c >= n) return;
+        const int lo = (r > c) ? c : r;
+        const double s = SB[(size_t)d * n + lo];
+        re = __builtin_fma(-zr, s, HB[(size_t)d * n + lo]);
+        im = -(zi * s);
+        if (WB) im = im - WB[(size_t)(c - r + b) * n + r];
+    }
+    __device__ __forceinline__ void diag(int j, double &mag, double &flo) const
+    {
         const double s = SB[j], h = HB[j], wv = WB ? WB[(size_t)b * n + j] : 0.0;
-        dmax = fmax(dmax, fabs(h - zr * s) + fabs(-(zi * s) - wv));
-        dflo = fmax(dflo, (fabs(h) + fabs(zr * s)) + (fabs(zi * s) + fabs(wv)));
+        mag = fabs(__builtin_fma(-zr, s, h)) + fabs(__builtin_fma(-zi, s, -wv));
+        flo = (fabs(h) + fabs(zr * s)) + (fabs(zi * s) + fabs(wv));
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { dmax = fmax(dmax, __shfl_xor(dmax, off)); dflo = fmax(dflo, __shfl_xor(dflo, off)); }
-    const double pertol = rs_pertol(dmax, dflo);
-
-    // lane c (0 .. 2 b) holds column j + c of the rows j .. j + b: a[t] = M(j + t, j + c)
-    double ar[BT + 1], ai[BT + 1];
-#pragma unroll
-    for (int t = 0; t <= BT; ++t) {
-        ar[t] = 0.0; ai[t] = 0.0;
-        if (t <= b && lane <= 2 * b) rs_entry(SB, HB, WB, n, b, zr, zi, t, lane, ar[t], ai[t]);
-    }
-    // the row that enters at step j (row j + b + 1), one entry per lane and step, requested a block of PF steps ahead
-    double per[PF], pei[PF], pnr[PF], pni[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-        pnr[u] = 0.0; pni[u] = 0.0;
-        if (lane <= 2 * b) rs_entry(SB, HB, WB, n, b, zr, zi, u + b + 1, u + 1 + lane, pnr[u], pni[u]);
-    }
-    int nper = 0;
-    for (int j = 0; j < n; ++j) {
-        if ((j & (PF - 1)) == 0) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                per[u] = pnr[u]; pei[u] = pni[u];
-                pnr[u] = 0.0; pni[u] = 0.0;
-                if (lane <= 2 * b) rs_entry(SB, HB, WB, n, b, zr, zi, j + PF + u + b + 1, j + PF + u + 1 + lane, pnr[u], pni[u]);
-            }
-        }
-        const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;       // rows below the pivot row
-        // pivot search down lane 0's registers (column j); ties go to the smallest row
-        double mxv = fabs(ar[0]) + fabs(ai[0]);
-        int dpl = 0;
-#pragma unroll
-        for (int t = 1; t <= BT; ++t) {
-            const double v = (t <= nrow) ? fabs(ar[t]) + fabs(ai[t]) : -1.0;
-            if (v > mxv) { mxv = v; dpl = t; }
-        }
-        const int dp = __builtin_amdgcn_readfirstlane(dpl);
-        if (dp != 0) {                                               // uniform: rows j and j + dp change places, in every column
-#pragma unroll
-            for (int t = 1; t <= BT; ++t)
-                if (t == dp) {
-                    const double t1 = ar[0], t2 = ai[0];
-                    ar[0] = ar[t]; ai[0] = ai[t]; ar[t] = t1; ai[t] = t2;
-                }
-        }
-        const double2 rcp = rs_pivot_recip(read_lane(ar[0], 0), read_lane(ai[0], 0), pertol, nper);
-        const double rr = rcp.x, ri = rcp.y;
-        double lmr = 0.0, lmi = 0.0;                                 // this lane's multiplier (row j + lane), for the store
-#pragma unroll
-        for (int t = 1; t <= BT; ++t) {
-            const double xr = read_lane(ar[t], 0), xi = read_lane(ai[t], 0);
-            const double ltr = (t <= nrow) ? xr * rr - xi * ri : 0.0;
-            const double lti = (t <= nrow) ? xr * ri + xi * rr : 0.0;
-            lmr = (lane == t) ? ltr : lmr;
-            lmi = (lane == t) ? lti : lmi;
-            const double ur = ltr * ar[0] - lti * ai[0], ui = ltr * ai[0] + lti * ar[0];
-            ar[t] = (lane >= 1) ? ar[t] - ur : 0.0;                  // columns j + 1 .. j + 2 b; column j is eliminated
-            ai[t] = (lane >= 1) ? ai[t] - ui : 0.0;
-        }
-        if (lane == 0) piv[j] = j + dp;
-        if (lane <= 2 * b) U[(size_t)j * (2 * b + 1) + lane] = (lane == 0) ? make_double2(rr, ri) : make_double2(ar[0], ai[0]);
-        if (lane >= 1 && lane <= b) Lm[(size_t)j * b + lane - 1] = make_double2(lmr, lmi);
-        // slide the window: row j leaves, row j + b + 1 enters; column j leaves, column j + 2 b + 1 enters (zero above the entering row)
-        double pinr = per[0], pini = pei[0];
-#pragma unroll
-        for (int u = 1; u < PF; ++u) {
-            pinr = ((j & (PF - 1)) == u) ? per[u] : pinr;
-            pini = ((j & (PF - 1)) == u) ? pei[u] : pini;
-        }
-#pragma unroll
-        for (int t = 0; t < BT; ++t) { ar[t] = dpp_mov<0x130>(ar[t + 1]); ai[t] = dpp_mov<0x130>(ai[t + 1]); }   // wave_shl:1
-        ar[BT] = 0.0; ai[BT] = 0.0;
-#pragma unroll
-        for (int t = 0; t <= BT; ++t)
-            if (t == b) { ar[t] = pinr; ai[t] = pini; }              // uniform
-    }
-    return nper;
-}
-
-// y <- U^-1 L^-1 P y in place (y: n complex in global memory, the slot's): invit_body's two passes, the b + 1 (forward) and 2 b
-// (backward) entries a step can touch in a register window, what enters it requested a block ahead.  The caller has made y visible
-// (rs_sync); on return the solution is visible to every lane.
-__device__ __forceinline__ void rs_solve(int n, int b, const double2 *U, const double2 *Lm, const int *piv, double2 *y, const int lane)
-{
-    rs_forward(n, b, Lm, piv, y, lane);
-    // backward: x_j = (y_j - sum_{c=1..2b} U[j][c] x_{j+c}) / pivot_j; lane c holds x[j + c] (zero beyond the matrix)
-    constexpr int PF = RS_PF;
-    const int w = 2 * b + 1;
-    double wr = 0.0, wi = 0.0;
-    double2 uvn[PF], udn[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-        const int j = n - 1 - u;
-        uvn[u] = (j >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)j * w + lane] : make_double2(0.0, 0.0);
-        udn[u] = (j >= 0) ? U[(size_t)j * w] : make_double2(0.0, 0.0);
-    }
-    double2 ybn = (lane < PF && n - 1 - lane >= 0) ? y[n - 1 - lane] : make_double2(0.0, 0.0);
-    for (int j0 = n - 1; j0 >= 0; j0 -= PF) {
-        double2 uv[PF], ru[PF];
-        const double2 yb = ybn;
-        ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int jn = j0 - u - PF;
-            uv[u] = uvn[u]; ru[u] = udn[u];
-            uvn[u] = (jn >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)jn * w + lane] : make_double2(0.0, 0.0);
-            udn[u] = (jn >= 0) ? U[(size_t)jn * w] : make_double2(0.0, 0.0);
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int j = j0 - u;
-            if (j >= 0) {
-                double sr = 0.0, si = 0.0;
-                if (lane >= 1 && lane <= 2 * b && j + lane < n) {
-                    sr = uv[u].x * wr - uv[u].y * wi;
-                    // The fused form of x wi + y wr is written out.  Left to the compiler, which of the two products it fuses depends
-                    // on the code around this loop, not on this line, and the results of the call with it.  These are
-                    // the forms the kernel computes since it exists: the first step of a block differs from the other seven.
-                    si = (u == 0) ? __builtin_fma(uv[u].x, wi, uv[u].y * wr) : __builtin_fma(uv[u].y, wr, uv[u].x * wi);
-                }
-                sr = wave_sum32(sr); si = wave_sum32(si);
-                const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
-                const double xr = dr * ru[u].x - di * ru[u].y, xi = dr * ru[u].y + di * ru[u].x;
-                if (lane == 0) y[j] = make_double2(xr, xi);
-                wr = dpp_mov<0x138>(wr); wi = dpp_mov<0x138>(wi);  // wave_shr:1 -- lane i takes lane i - 1
-                if (lane == 1) { wr = xr; wi = xi; }
-            }
-        }
-    }
-    rs_sync();
-}
+};
 
 // y <- A x, A = sum_o ac[o] G_o: the right-hand side of a chain's next stage (include/bspatom.h: bspatom_resolvent_chain).  GB: nop
 // full bands [2b+1][n], GB[(d + b) n + i] = G(i, i + d).  Lane-strided over the rows; an entry is t = ac[0] G_0, then t = t + ac[o] G_o
 // for o ascending; y_re(i), y_im(i) start at +0.0 and add t x_re(i + d), t x_im(i + d) for d ascending, columns outside 0 .. n-1
-// skipped.  IEEE multiplies and adds in the order written, NOTHING contracted (the pragma covers the whole body; the rest of this
-// file contracts): opmat.hip::band_combine_apply_kernel's arithmetic on the two components.  x and y are distinct vectors of the
-// slot; the caller has made x visible (rs_sync) and makes y visible.
+// skipped.  IEEE multiplies and adds in the order written, NOTHING contracted (as in the whole file):
+// opmat.hip::band_combine_apply_kernel's arithmetic on the two components.  x and y are distinct vectors of the slot; the caller has
+// made x visible (rs_sync) and makes y visible.
 // A row's loads are independent of each other and issued together by blocks of CH diagonals -- the block's entries of one operator,
 // then its entries of x -- so a row costs 3 (nop + 1) memory round trips at most, not (2b + 1)(nop + 1): every address is clamped
 // into its array (diagonals beyond 2b, columns outside the matrix) and what was loaded there is dropped by a select, never added.
@@ -212,7 +80,6 @@ template <int BT>
 __device__ __forceinline__ void rs_band_apply(int n, int b, int nop, const double *__restrict__ GB, const double *__restrict__ ac,
                                               const double2 *x, double2 *y, const int lane)
 {
-#pragma clang fp contract(off)
     constexpr int CH = (2 * BT + 1 + 2) / 3;                   // 6 of 17 diagonals (BT = 8), 11 of 31 (BT = 15)
     const int nd = 2 * b + 1;
     const size_t cs = (size_t)nd * n;
@@ -270,14 +137,15 @@ __global__ __launch_bounds__(64) void resolvent_kernel(const ResolventArgs a)
         int *piv = reinterpret_cast<int *>(y + n);
         const int wsel = a.w ? a.w[it] : -1;
         const double *wband = (wb && wsel >= 0) ? wb + (size_t)wsel * (2 * b + 1) * n : nullptr;
-        const int nper = rs_factor<BT>(n, b, sb, hb + (size_t)a.chan[it] * a.k * n, wband, a.z[2 * it], a.z[2 * it + 1], U, Lm, piv, lane);
+        const RsPencil e = {sb, hb + (size_t)a.chan[it] * a.k * n, wband, n, b, a.z[2 * it], a.z[2 * it + 1]};
+        const int nper = wave_lu_factor<BT, WaveLuResolvent>(n, b, e, U, Lm, piv, lane);
         if (lane == 0) a.info[it] = nper;
         for (int r = 0; r < a.nrhs; ++r) {
             // (the caller's arrays are read and written as doubles: the ABI promises no more than their alignment)
             const double *B = a.B + (size_t)2 * r * n;
             for (int j = lane; j < n; j += 64) y[j] = make_double2(B[2 * j], B[2 * j + 1]);
             rs_sync();                                               // y, and with the first right-hand side U, L, piv, are in memory
-            rs_solve(n, b, U, Lm, piv, y, lane);
+            wave_lu_solve<WaveLuResolvent>(n, b, U, Lm, piv, y, lane);
             const size_t mr = (size_t)it * a.nrhs + r;
             if (a.X) {
                 double *X = a.X + 2 * mr * n;
@@ -290,8 +158,8 @@ __global__ __launch_bounds__(64) void resolvent_kernel(const ResolventArgs a)
                     double sr = 0.0, si = 0.0;
                     for (int j = lane; j < n; j += 64) {
                         const double2 pv = make_double2(P[2 * j], P[2 * j + 1]), xv = y[j];
-                        sr += pv.x * xv.x - pv.y * xv.y;
-                        si += pv.x * xv.y + pv.y * xv.x;
+                        sr = sr + __builtin_fma(pv.x, xv.x, -(pv.y * xv.y));
+                        si = si + __builtin_fma(pv.y, xv.x, pv.x * xv.y);
                     }
                     sr = wave_sum(sr); si = wave_sum(si);
                     if (lane == 0) { a.R[2 * (mr * a.nproj + q)] = sr; a.R[2 * (mr * a.nproj + q) + 1] = si; }
@@ -302,8 +170,8 @@ __global__ __launch_bounds__(64) void resolvent_kernel(const ResolventArgs a)
 }
 
 // Chains of resolvents, p^T G(z_s) A_s ... G(z_1) A_1 b: the same persistent grid, the CHAINS taken by the static stride, a chain
-// on its wave from the first factorisation to the last projection.  A stage is resolvent_kernel's item -- rs_factor, then per
-// right-hand side the load of y, rs_solve, X (last stage), the projections -- with y loaded from B at stage 0 and from
+// on its wave from the first factorisation to the last projection.  A stage is resolvent_kernel's item -- wave_lu_factor, then per
+// right-hand side the load of y, wave_lu_solve, X (last stage), the projections -- with y loaded from B at stage 0 and from
 // rs_band_apply of the previous stage's solution otherwise; one factorisation serves the nrhs right-hand sides of its stage, so the
 // slot keeps nrhs previous vectors.  Slot scratch: resolvent_kernel's (U, L, y, piv: rs_slot_doubles, even), then xp [nrhs][n] complex.
 // nstage = 1 is resolvent_kernel statement for statement.
@@ -326,7 +194,8 @@ __global__ __launch_bounds__(64) void resolvent_chain_kernel(const ResolventChai
             const size_t it = (size_t)c * a.nstage + s;
             const int wsel = a.w ? a.w[it] : -1;
             const double *wband = (wb && wsel >= 0) ? wb + (size_t)wsel * (2 * b + 1) * n : nullptr;
-            const int nper = rs_factor<BT>(n, b, sb, hb + (size_t)a.chan[it] * a.k * n, wband, a.z[2 * it], a.z[2 * it + 1], U, Lm, piv, lane);
+            const RsPencil e = {sb, hb + (size_t)a.chan[it] * a.k * n, wband, n, b, a.z[2 * it], a.z[2 * it + 1]};
+            const int nper = wave_lu_factor<BT, WaveLuResolvent>(n, b, e, U, Lm, piv, lane);
             if (lane == 0) a.info[it] = nper;
             const bool last = s + 1 == a.nstage;
             for (int r = 0; r < a.nrhs; ++r) {
@@ -337,7 +206,7 @@ __global__ __launch_bounds__(64) void resolvent_chain_kernel(const ResolventChai
                     rs_band_apply<BT>(n, b, a.nop, gb, a.acoef + ((size_t)c * (a.nstage - 1) + (s - 1)) * a.nop, xp + (size_t)r * n, y, lane);
                 }
                 rs_sync();                                           // y, and with the first right-hand side U, L, piv, are in memory
-                rs_solve(n, b, U, Lm, piv, y, lane);
+                wave_lu_solve<WaveLuResolvent>(n, b, U, Lm, piv, y, lane);
                 if (a.X && last) {
                     double *X = a.X + 2 * ((size_t)c * a.nrhs + r) * n;
                     for (int j = lane; j < n; j += 64) { const double2 v = y[j]; X[2 * j] = v.x; X[2 * j + 1] = v.y; }
@@ -350,8 +219,8 @@ __global__ __launch_bounds__(64) void resolvent_chain_kernel(const ResolventChai
                         double sr = 0.0, si = 0.0;
                         for (int j = lane; j < n; j += 64) {
                             const double2 pv = make_double2(P[2 * j], P[2 * j + 1]), xv = y[j];
-                            sr += pv.x * xv.x - pv.y * xv.y;
-                            si += pv.x * xv.y + pv.y * xv.x;
+                            sr = sr + __builtin_fma(pv.x, xv.x, -(pv.y * xv.y));
+                            si = si + __builtin_fma(pv.y, xv.x, pv.x * xv.y);
                         }
                         sr = wave_sum(sr); si = wave_sum(si);
                         if (lane == 0) { a.R[2 * (mr * a.nproj + q)] = sr; a.R[2 * (mr * a.nproj + q) + 1] = si; }

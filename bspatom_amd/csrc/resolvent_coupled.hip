@@ -16,7 +16,7 @@
 // reciprocal and the multipliers, copies the pivot row out (U, and a broadcast copy in LDS) and puts row j where the pivot row
 // was; after a barrier all waves update the window, a wave per row, a lane per column, while the last two waves store the entering
 // row, which they requested two steps ahead; a second barrier ends the step.  U rows, L multipliers and pivot indices stream
-// to the slot's scratch; the solves run from there on wave 0 (forward: rs_forward of resolvent_shared.h, resolvent.hip's register window on bw + 1 lanes; backward: the
+// to the slot's scratch; the solves run from there on wave 0 (forward: wave_lu_forward of band_lu_wave.h, resolvent.hip's register window on bw + 1 lanes; backward: the
 // last 2 bw unknowns in an LDS ring, two per lane), one right-hand side after the other.
 //
 // The matrix is first ASSEMBLED, by all threads, into the rows of U itself -- row r of the band, columns r - bw .. r + bw, lies where

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "wave_ops.h"
 #include "resolvent_shared.h"
+#include "band_lu_wave.h"
 #include "../../include/bspatom.h"
 
 namespace bsp {
@@ -149,12 +150,12 @@ __device__ __forceinline__ int rc_factor(const int N, const int bw, const double
 }
 
 // y <- U^-1 L^-1 P y in place on ONE wave (y: N complex in global memory, visible to the wave; xs: an LDS ring of 128 complex).
-// Forward: rs_forward, the pass of resolvent.hip::rs_solve, lane i holds y[j + i], i <= bw <= 63.  Backward: x_j = (y_j - sum_{c=1..2bw} U[j][c]
+// Forward: wave_lu_forward (band_lu_wave.h), the pass of the one-wave kernels, lane i holds y[j + i], i <= bw <= 63.  Backward: x_j = (y_j - sum_{c=1..2bw} U[j][c]
 // x_{j+c}) / pivot_j, the 2 bw unknowns behind j in the ring, lane l takes c = l and c = 64 + l, then the wave's fixed tree.
 __device__ __forceinline__ void rc_solve(const int N, const int bw, const double2 *U, const double2 *Lm, const int *piv, double2 *y,
                                          double2 *xs, const int lane)
 {
-    rs_forward(N, bw, Lm, piv, y, lane);
+    wave_lu_forward<WaveLuArith>(N, bw, Lm, piv, y, lane);
     constexpr int PF = RC_PFB;
     const int W = 2 * bw + 1;
     xs[lane] = make_double2(0.0, 0.0); xs[lane + 64] = make_double2(0.0, 0.0);

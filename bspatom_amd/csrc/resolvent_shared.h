@@ -1,6 +1,7 @@
 // resolvent_shared.h -- what the resolvent kernels (resolvent.hip, resolvent_coupled.hip, resolvent_wide.hip) share on the device: the
-// zero-pivot rule and the reciprocal of a pivot, the one-wave forward substitution, the way a right-hand side comes into a workgroup
-// and a solution and its projections go out, the entry of the coupled matrix and the wave-level pieces of its pivot search.  One
+// zero-pivot rule and the reciprocal of a pivot, the way a right-hand side comes into a workgroup and a solution and its projections
+// go out, the entry of the coupled matrix and the wave-level pieces of its pivot search.  (The one-wave LU and its substitutions,
+// the forward pass that rc_solve runs among them, are band_lu_wave.h.)  One
 // definition each, so that "resolvent.hip's form" and "as resolvent_coupled.hip" in the guarantees of include/bspatom.h (G2/G3,
 // C1 - C6, K1 - K4) name code, not copies: the calls factor the same numbers and sum in the same order because they run the same
 // statements.  (The one-wave kernels keep their own loads, stores and projections: through helpers they measured slower.)
@@ -23,7 +24,8 @@ __device__ __forceinline__ double rs_pertol(double dmax, double dflo)
 }
 // 1 / pivot, once per column: a pivot below the threshold is replaced by +-pertol and counted in nper; the reciprocal is scaled by
 // cabs1, so that it neither overflows nor underflows.  (The replacement as selects: written as a branch it compiles to one, in the
-// dependent chain of every step of the one-wave factorisation.)
+// dependent chain of every step of the one-wave factorisation.)  The squared modulus states its fused product: the form every
+// includer had compiled, with contraction on or off around it.
 __device__ __forceinline__ double2 rs_pivot_recip(double pr, double pi, const double pertol, int &nper)
 {
     const bool tiny = fabs(pr) + fabs(pi) < pertol;
@@ -32,62 +34,8 @@ __device__ __forceinline__ double2 rs_pivot_recip(double pr, double pi, const do
     nper += tiny;
     const double sc = 1.0 / (fabs(pr) + fabs(pi));
     const double qr = pr * sc, qi = pi * sc;
-    const double rd = 1.0 / (qr * qr + qi * qi);
+    const double rd = 1.0 / __builtin_fma(qr, qr, qi * qi);
     return make_double2((qr * rd) * sc, -((qi * rd) * sc));
-}
-
-// y <- L^-1 P y in place on ONE wave (y: n complex in global memory, visible to the wave; Lm: [n][b] multipliers, piv: [n] pivot
-// rows, b <= 63): invit_body's forward pass, lane i holds y[j + i], the b + 1 entries a step can touch in a register window, what
-// enters it requested a block ahead.  On return the result is visible to every lane.
-__device__ __forceinline__ void rs_forward(const int n, const int b, const double2 *Lm, const int *piv, double2 *y, const int lane)
-{
-    constexpr int PF = RS_PF;
-    double wr = 0.0, wi = 0.0;
-    if (lane <= b && lane < n) { const double2 v = y[lane]; wr = v.x; wi = v.y; }
-    double2 lvn[PF]; int pvn[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-        lvn[u] = (u < n && lane >= 1 && lane <= b) ? Lm[(size_t)u * b + lane - 1] : make_double2(0.0, 0.0);
-        pvn[u] = (u < n) ? piv[u] : 0;
-    }
-    // the entering entries: one per lane (lane u: step u's), a block ahead; above every index this pass has written
-    double2 yln = (lane < PF && lane + b + 1 < n) ? y[lane + b + 1] : make_double2(0.0, 0.0);
-    for (int j0 = 0; j0 < n; j0 += PF) {
-        double2 lv[PF]; int pvv[PF];
-        const double2 yl = yln;
-        yln = (lane < PF && j0 + PF + lane + b + 1 < n) ? y[j0 + PF + lane + b + 1] : make_double2(0.0, 0.0);
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int jn = j0 + u + PF;
-            lv[u] = lvn[u]; pvv[u] = pvn[u];
-            lvn[u] = (jn < n && lane >= 1 && lane <= b) ? Lm[(size_t)jn * b + lane - 1] : make_double2(0.0, 0.0);
-            pvn[u] = (jn < n) ? piv[jn] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int j = j0 + u;
-            if (j < n) {
-                const int p = __builtin_amdgcn_readfirstlane(pvv[u]);
-                if (p != j) {                                    // uniform: rows j and p change places (p - j <= b: inside the window)
-                    const double t0r = read_lane(wr, 0), t0i = read_lane(wi, 0);
-                    const double tqr = read_lane(wr, p - j), tqi = read_lane(wi, p - j);
-                    wr = lane == 0 ? tqr : (lane == p - j ? t0r : wr);
-                    wi = lane == 0 ? tqi : (lane == p - j ? t0i : wi);
-                }
-                const double yr = read_lane(wr, 0), yi = read_lane(wi, 0);
-                const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;
-                if (lane >= 1 && lane <= nrow) {
-                    wr -= lv[u].x * yr - lv[u].y * yi;
-                    wi -= lv[u].x * yi + lv[u].y * yr;
-                }
-                if (lane == 0) y[j] = make_double2(yr, yi);
-                wr = dpp_mov<0x130>(wr); wi = dpp_mov<0x130>(wi);  // wave_shl:1 -- lane i takes lane i + 1
-                const double er = read_lane(yl.x, u), ei = read_lane(yl.y, u);
-                if (lane == b) { wr = er; wi = ei; }
-            }
-        }
-    }
-    rs_sync();
 }
 
 // ---- a right-hand side in, a solution and its projections out, for the coupled kernels' workgroups of NT threads: the caller's

@@ -14,12 +14,12 @@
 //                                  N_j changes with the step: factored every time.
 //   back:                          c_c = sum_j Q(c,j) d_j, then the atomic half step again.
 //
-// How: one wavefront per system -- the methods of resolvent.hip (rs_factor, rs_solve, rs_band_apply): the row window in registers,
-// multipliers and the pivot row by readlane, the window moved by a one-lane DPP shift, no LDS and no barrier in the n dependent steps
-// -- in statements of this file's own: this call promises no bit equality with bspatom_resolvent, and resolvent.hip's bits depend on
-// the code around its loops, so nothing is moved out of it.  Shared with it through resolvent_shared.h: the pivot
-// threshold, the reciprocal of a pivot, the forward substitution.  Every sum whose order the header fixes is written without FMA
-// (the whole file is compiled with contraction off; the LU's multiply-adds are explicit fma calls).
+// How: one wavefront per system -- band_lu_wave.h's wave_lu_factor and wave_lu_solve, the one definition resolvent.hip runs too: the
+// row window in registers, multipliers and the pivot row by readlane, the window moved by a one-lane DPP shift, no LDS and no barrier
+// in the n dependent steps -- with this file's own arithmetic policy, WaveLuSplit, and its two matrices as SpAtomic and SpField:
+// this call promises no bit equality with bspatom_resolvent.  The pivot threshold and the reciprocal of a pivot are
+// resolvent_shared.h's.  Every sum whose order the header fixes is written without FMA (the whole file is compiled with contraction
+// off; the LU's multiply-adds are explicit fma calls).
 //
 // Scheduling: a PERSISTENT grid of single-wave workgroups takes the nscan * nch items of a substep by static stride; substeps are
 // separated by kernel boundaries, three launches per step: the first atomic half step (with the rows), the field step, the second
@@ -29,6 +29,7 @@
 #include "common.h"
 #include "wave_ops.h"
 #include "resolvent_shared.h"
+#include "band_lu_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -59,7 +60,8 @@ __device__ __forceinline__ SpFactor sp_factor_at(double *base, int n, int b)
 }
 
 // The two matrices.  SB, HB upper bands [k][n] used symmetrically, WB and GB FULL bands [2k-1][n], X[(d + b) n + i] = X(i, i + d).
-// entry: M(r, c), zero outside the band and the matrix; diag: |M(j,j)| by cabs1 and the sum of the magnitudes of its terms (rs_pertol)
+// wave_lu_factor's argument -- entry: M(r, c), zero outside the band and the matrix; diag: |M(j,j)| by cabs1 and the sum of the
+// magnitudes of its terms (rs_pertol)
 // M_c = H - i W - (0, zi) S
 struct SpAtomic {
     const double *SB, *HB, *WB;
@@ -104,151 +106,6 @@ struct SpField {
         flo = (fabs(s) + fabs(ar * g)) + fabs(ai * g);
     }
 };
-
-// The factorisation P M = L U of one matrix by one wavefront, resolvent.hip's method.  U: [n][2b+1] complex, row j = (1 / pivot,
-// U(j, j+1 .. j+2b)); Lm: [n][b] complex multipliers; piv: [n] pivot rows.  Pivot by |Re| + |Im|, ties to the smallest row; the
-// threshold and the reciprocal are rs_pertol and rs_pivot_recip.  Returns the number of pivots that were replaced.
-template <int BT, class Entry>
-__device__ __forceinline__ int sp_factor(const int n, const int b, const Entry &e, const SpFactor &f, const int lane)
-{
-    constexpr int PF = RS_PF;
-    double dmax = 0.0, dflo = 0.0;
-    for (int j = lane; j < n; j += 64) {
-        double mag, flo;
-        e.diag(j, mag, flo);
-        dmax = fmax(dmax, mag);
-        dflo = fmax(dflo, flo);
-    }
-    dmax = rc_wave_max(dmax); dflo = rc_wave_max(dflo);
-    const double pertol = rs_pertol(dmax, dflo);
-
-    // lane c (0 .. 2 b) holds column j + c of the rows j .. j + b: a[t] = M(j + t, j + c)
-    double ar[BT + 1], ai[BT + 1];
-#pragma unroll
-    for (int t = 0; t <= BT; ++t) {
-        ar[t] = 0.0; ai[t] = 0.0;
-        if (t <= b && lane <= 2 * b) e.entry(t, lane, ar[t], ai[t]);
-    }
-    // the row that enters at step j (row j + b + 1), one entry per lane and step, requested a block of PF steps ahead
-    double per[PF], pei[PF], pnr[PF], pni[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-        pnr[u] = 0.0; pni[u] = 0.0;
-        if (lane <= 2 * b) e.entry(u + b + 1, u + 1 + lane, pnr[u], pni[u]);
-    }
-    int nper = 0;
-    for (int j = 0; j < n; ++j) {
-        if ((j & (PF - 1)) == 0) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                per[u] = pnr[u]; pei[u] = pni[u];
-                pnr[u] = 0.0; pni[u] = 0.0;
-                if (lane <= 2 * b) e.entry(j + PF + u + b + 1, j + PF + u + 1 + lane, pnr[u], pni[u]);
-            }
-        }
-        const int nrow = (n - 1 - j < b) ? (n - 1 - j) : b;       // rows below the pivot row
-        // pivot search down lane 0's registers (column j)
-        double mxv = fabs(ar[0]) + fabs(ai[0]);
-        int dpl = 0;
-#pragma unroll
-        for (int t = 1; t <= BT; ++t) {
-            const double v = (t <= nrow) ? fabs(ar[t]) + fabs(ai[t]) : -1.0;
-            if (v > mxv) { mxv = v; dpl = t; }
-        }
-        const int dp = __builtin_amdgcn_readfirstlane(dpl);
-        if (dp != 0) {                                               // uniform: rows j and j + dp change places, in every column
-#pragma unroll
-            for (int t = 1; t <= BT; ++t)
-                if (t == dp) {
-                    const double t1 = ar[0], t2 = ai[0];
-                    ar[0] = ar[t]; ai[0] = ai[t]; ar[t] = t1; ai[t] = t2;
-                }
-        }
-        const double2 rcp = rs_pivot_recip(read_lane(ar[0], 0), read_lane(ai[0], 0), pertol, nper);
-        const double rr = rcp.x, ri = rcp.y;
-        double lmr = 0.0, lmi = 0.0;                                 // this lane's multiplier (row j + lane), for the store
-#pragma unroll
-        for (int t = 1; t <= BT; ++t) {
-            const double xr = read_lane(ar[t], 0), xi = read_lane(ai[t], 0);
-            const double ltr = (t <= nrow) ? __builtin_fma(xr, rr, -(xi * ri)) : 0.0;
-            const double lti = (t <= nrow) ? __builtin_fma(xr, ri, xi * rr) : 0.0;
-            lmr = (lane == t) ? ltr : lmr;
-            lmi = (lane == t) ? lti : lmi;
-            // a[t] -= l a[0], four fused multiply-adds
-            const double nr = __builtin_fma(lti, ai[0], __builtin_fma(-ltr, ar[0], ar[t]));
-            const double ni = __builtin_fma(-lti, ar[0], __builtin_fma(-ltr, ai[0], ai[t]));
-            ar[t] = (lane >= 1) ? nr : 0.0;                          // columns j + 1 .. j + 2 b; column j is eliminated
-            ai[t] = (lane >= 1) ? ni : 0.0;
-        }
-        if (lane == 0) f.piv[j] = j + dp;
-        if (lane <= 2 * b) f.U[(size_t)j * (2 * b + 1) + lane] = (lane == 0) ? make_double2(rr, ri) : make_double2(ar[0], ai[0]);
-        if (lane >= 1 && lane <= b) f.Lm[(size_t)j * b + lane - 1] = make_double2(lmr, lmi);
-        // slide the window: row j leaves, row j + b + 1 enters; column j leaves, column j + 2 b + 1 enters (zero above the entering row)
-        double pinr = per[0], pini = pei[0];
-#pragma unroll
-        for (int u = 1; u < PF; ++u) {
-            pinr = ((j & (PF - 1)) == u) ? per[u] : pinr;
-            pini = ((j & (PF - 1)) == u) ? pei[u] : pini;
-        }
-#pragma unroll
-        for (int t = 0; t < BT; ++t) { ar[t] = dpp_mov<0x130>(ar[t + 1]); ai[t] = dpp_mov<0x130>(ai[t + 1]); }   // wave_shl:1
-        ar[BT] = 0.0; ai[BT] = 0.0;
-#pragma unroll
-        for (int t = 0; t <= BT; ++t)
-            if (t == b) { ar[t] = pinr; ai[t] = pini; }              // uniform
-    }
-    return nper;
-}
-
-// y <- U^-1 L^-1 P y in place (y: n complex of the slot, visible to the wave): rs_forward, then the backward pass
-// x_j = (y_j - sum_{c=1..2b} U[j][c] x_{j+c}) / pivot_j with lane c holding x[j + c], what enters requested a block ahead.  On return
-// the solution is visible to every lane.
-__device__ __forceinline__ void sp_solve(const int n, const int b, const SpFactor &f, double2 *y, const int lane)
-{
-    rs_forward(n, b, f.Lm, f.piv, y, lane);
-    constexpr int PF = RS_PF;
-    const int w = 2 * b + 1;
-    const double2 *U = f.U;
-    double wr = 0.0, wi = 0.0;
-    double2 uvn[PF], udn[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-        const int j = n - 1 - u;
-        uvn[u] = (j >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)j * w + lane] : make_double2(0.0, 0.0);
-        udn[u] = (j >= 0) ? U[(size_t)j * w] : make_double2(0.0, 0.0);
-    }
-    double2 ybn = (lane < PF && n - 1 - lane >= 0) ? y[n - 1 - lane] : make_double2(0.0, 0.0);
-    for (int j0 = n - 1; j0 >= 0; j0 -= PF) {
-        double2 uv[PF], ru[PF];
-        const double2 yb = ybn;
-        ybn = (lane < PF && j0 - PF - lane >= 0) ? y[j0 - PF - lane] : make_double2(0.0, 0.0);
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int jn = j0 - u - PF;
-            uv[u] = uvn[u]; ru[u] = udn[u];
-            uvn[u] = (jn >= 0 && lane >= 1 && lane <= 2 * b) ? U[(size_t)jn * w + lane] : make_double2(0.0, 0.0);
-            udn[u] = (jn >= 0) ? U[(size_t)jn * w] : make_double2(0.0, 0.0);
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int j = j0 - u;
-            if (j >= 0) {
-                double sr = 0.0, si = 0.0;
-                if (lane >= 1 && lane <= 2 * b && j + lane < n) {
-                    sr = __builtin_fma(uv[u].x, wr, -(uv[u].y * wi));
-                    si = __builtin_fma(uv[u].x, wi, uv[u].y * wr);
-                }
-                sr = wave_sum32(sr); si = wave_sum32(si);
-                const double dr = read_lane(yb.x, u) - sr, di = read_lane(yb.y, u) - si;
-                const double xr = __builtin_fma(dr, ru[u].x, -(di * ru[u].y)), xi = __builtin_fma(dr, ru[u].y, di * ru[u].x);
-                if (lane == 0) y[j] = make_double2(xr, xi);
-                wr = dpp_mov<0x138>(wr); wi = dpp_mov<0x138>(wi);  // wave_shr:1 -- lane i takes lane i - 1
-                if (lane == 1) { wr = xr; wi = xi; }
-            }
-        }
-    }
-    rs_sync();
-}
 
 // v(i) = sum_m q[m qs] in_m(i), m = 0 .. nch-1 ascending from +0.0, multiply then add: the mixing with Q folded into a kernel's operand
 // load.  in: the scan's packet [nch][n] complex; lane-strided over i, every lane its own rows.
@@ -322,7 +179,8 @@ __global__ __launch_bounds__(64) void tsplit_factor_kernel(const TdseSplitArgs a
     for (int f = blockIdx.x; f < a.nfac; f += gridDim.x) {
         const int ws = a.fw[f];
         SpAtomic e = {a.SB, a.HB + (size_t)a.fchan[f] * a.k * n, (a.WB && ws >= 0) ? a.WB + (size_t)ws * (2 * b + 1) * n : nullptr, n, b, a.zi};
-        const int nper = sp_factor<BT>(n, b, e, sp_factor_at(a.fstore + (size_t)f * sp_factor_doubles(n, a.k), n, b), lane);
+        const SpFactor fc = sp_factor_at(a.fstore + (size_t)f * sp_factor_doubles(n, a.k), n, b);
+        const int nper = wave_lu_factor<BT, WaveLuSplit>(n, b, e, fc.U, fc.Lm, fc.piv, lane);
         if (lane == 0) a.finfo[f] = nper;
     }
 }
@@ -374,7 +232,8 @@ __global__ __launch_bounds__(64) void tsplit_atomic_kernel(const TdseSplitArgs a
         }
         rs_sync();                                                   // b is in memory
         if (a.measure) continue;
-        sp_solve(n, b, sp_factor_at(a.fstore + (size_t)a.fac[ch] * sp_factor_doubles(n, a.k), n, b), y, lane);
+        const SpFactor fc = sp_factor_at(a.fstore + (size_t)a.fac[ch] * sp_factor_doubles(n, a.k), n, b);
+        wave_lu_solve<WaveLuSplit>(n, b, fc.U, fc.Lm, fc.piv, y, lane);
         // c' = -(8 i / dt) x - c: one multiply and one subtract per component
         double *out = a.out + 2 * ((size_t)q * nch + ch) * n;
         double *sn = a.snap ? a.snap + 2 * ((size_t)q * nch + ch) * n : nullptr;
@@ -420,10 +279,10 @@ __global__ __launch_bounds__(64) void tsplit_field_kernel(const TdseSplitArgs a)
         const double lam = a.lam[j], mur = a.f[2 * q] * lam, mui = a.f[2 * q + 1] * lam;
         SpField e = {a.SB, a.GB, n, b, -(a.h * mui), a.h * mur};
         const SpFactor fc = sp_factor_at(wk + 4 * (size_t)n, n, b);
-        const int nper = sp_factor<BT>(n, b, e, fc, lane);
+        const int nper = wave_lu_factor<BT, WaveLuSplit>(n, b, e, fc.U, fc.Lm, fc.piv, lane);
         if (lane == 0) a.pinfo[(size_t)q * nch + j] += nper;
         rs_sync();                                                   // b and the factors are in memory
-        sp_solve(n, b, fc, y, lane);
+        wave_lu_solve<WaveLuSplit>(n, b, fc.U, fc.Lm, fc.piv, y, lane);
         double *out = a.out + 2 * ((size_t)q * nch + j) * n;
         for (int i = lane; i < n; i += 64) {
             const double2 x = y[i], dv = xin[i];
