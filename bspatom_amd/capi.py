@@ -48,6 +48,10 @@ SPLIT_EXPORTS = ["bspatom_tdse_split", "bspatom_tdse_split_dev"]
 # what include/bspatom_spline_expect.h, the part of the header for expectation values in the spline basis, declares
 EXPECT_EXPORTS = ["bspatom_spline_expect", "bspatom_spline_expect_dev", "bspatom_tdse_split_observe", "bspatom_tdse_split_observe_dev"]
 
+# what include/bspatom_spline_window.h, the part of the header for the window operator on spline packets, declares
+WINDOW_EXPORTS = ["bspatom_spline_window", "bspatom_spline_window_dev"]
+WINDOW_MAX_FAC = 8                          # BSPATOM_WINDOW_MAX_FAC
+
 _lib = None
 
 
@@ -114,6 +118,8 @@ def lib():
         L.bspatom_spline_expect.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
         L.bspatom_spline_expect_dev.argtypes = list(L.bspatom_spline_expect.argtypes)
         L.bspatom_tdse_split_observe.argtypes = L.bspatom_tdse_split.argtypes + [i32, vp, vp]
+        L.bspatom_spline_window.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+        L.bspatom_spline_window_dev.argtypes = list(L.bspatom_spline_window.argtypes)
         L.bspatom_tdse_split_observe_dev.argtypes = list(L.bspatom_tdse_split_observe.argtypes)
         L.bspatom_last_timing.argtypes = [vp, vp]
         L.bspatom_early_vector_state.argtypes = [vp, vp]
@@ -1020,6 +1026,41 @@ class Problem:
         B = np.ascontiguousarray(B.reshape(-1, nch, nch))
         _chk(lib().bspatom_spline_expect_dev(self._h, nscan, nch, B.shape[0], _p(B), _ptr(GE_ptr), _ptr(c_ptr), _ptr(e_ptr)),
              "bspatom_spline_expect_dev")
+
+    def spline_window(self, l, c, z):
+        """N(q, c, e) = x^H S x with x = prod_j (H_l[c] - z[e, j] S)^-1 S applied to packet (q, c) (bspatom_spline_window): the window
+        operator of the grid codes in the spline basis, P_m(E) = gamma^(2m) N with the shifts of host.window_shifts(E, gamma, m)
+        (host.window_spectrum does both).  l: (nch,) channels among the assembled bands; c: complex (nscan, nch, nfun) or (nch, nfun),
+        tdse_split's packets; z: complex (ne, nfac), or (ne,) for one stage, nfac = 0 .. WINDOW_MAX_FAC, any values; (ne, 0) measures
+        the S-norm.  Returns (N (nscan, nch, ne) -- (nch, ne) for one packet --, info (ne,) replaced pivots, 0 whenever Im z != 0).
+        One factorisation per (distinct l, e, j) serves the packets of every scan and channel with that l; the arithmetic is
+        resolvent's and tdse_split's, bit for bit (include/bspatom_spline_window.h, W1 - W6)."""
+        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
+        nch, n = l.size, self.nfun
+        z = np.asarray(z, dtype=np.complex128)
+        z = np.ascontiguousarray(z.reshape(-1, 1) if z.ndim == 1 else z)
+        assert z.ndim == 2, z.shape
+        ne, nfac = z.shape
+        c = np.asarray(c, dtype=np.complex128)
+        one = c.ndim == 2
+        c = np.ascontiguousarray(c.reshape(-1, nch, n))
+        N = np.zeros((c.shape[0], nch, ne))
+        info = np.zeros(ne, dtype=np.int32)
+        _chk(lib().bspatom_spline_window(self._h, c.shape[0], nch, _p(l), ne, nfac, _p(z) if nfac else None, _p(c), _p(N), _p(info)),
+             "bspatom_spline_window")
+        return (N[0] if one else N), info
+
+    def spline_window_dev(self, l, nscan, c_ptr, z, N_ptr):
+        """spline_window with the packets (nscan * nch * nfun complex at c_ptr) and the result (nscan * nch * ne doubles at N_ptr) in
+        device memory of this problem's device; l and z are host values.  Returns info (ne,) when the result is there."""
+        l = np.ascontiguousarray(np.asarray(l, dtype=np.int32).reshape(-1))
+        z = np.asarray(z, dtype=np.complex128)
+        z = np.ascontiguousarray(z.reshape(-1, 1) if z.ndim == 1 else z)
+        ne, nfac = z.shape
+        info = np.zeros(ne, dtype=np.int32)
+        _chk(lib().bspatom_spline_window_dev(self._h, nscan, l.size, _p(l), ne, nfac, _p(z) if nfac else None, _ptr(c_ptr), _ptr(N_ptr),
+                                             _p(info)), "bspatom_spline_window_dev")
+        return info
 
     def _tdse_split(self, l, c0, dt, nsteps, G, Q, lam, f, W, w, P, obs_every, snap_every, expect):
         """the body of tdse_split and tdse_split_observe: the arrays of the call; expect None: bspatom_tdse_split"""

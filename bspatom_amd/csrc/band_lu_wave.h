@@ -1,6 +1,6 @@
 // band_lu_wave.h -- the pivoted complex banded LU of ONE wavefront and its two substitutions, one definition for every kernel that
 // runs them: resolvent.hip (resolvent_kernel, resolvent_chain_kernel), tdse_split.hip (tsplit_factor_kernel, tsplit_atomic_kernel,
-// tsplit_field_kernel) and, for the forward pass, resolvent_coupled_lu.h::rc_solve.  This is eigvec.hip::invit_body's method for a
+// tsplit_field_kernel), spline_window.hip (spline_window_kernel) and, for the forward pass, resolvent_coupled_lu.h::rc_solve.  This is eigvec.hip::invit_body's method for a
 // complex matrix: the row window in registers, multipliers and the pivot row by readlane, the window moved by a one-lane DPP
 // shift, the entering row fetched RS_PF steps ahead, no LDS and no barrier in the n dependent steps.
 //

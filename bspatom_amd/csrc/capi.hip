@@ -122,6 +122,7 @@ const OptName OPT_TABLE[] = {
     {"tdse_adapt_group", "BSP_TDSE_ADAPT_GROUP", &Options::tdse_adapt_group},
     {"tdse_spline_group", "BSP_TDSE_SPLINE_GROUP", &Options::tdse_spline_group},
     {"tdse_split_group", "BSP_TDSE_SPLIT_GROUP", &Options::tdse_split_group},
+    {"window_rhs", "BSP_WINDOW_RHS", &Options::window_rhs},
 };
 }  // namespace
 

@@ -3,6 +3,7 @@
 //   bspatom_tdse_spline / _dev, _wide / _wide_dev: Crank-Nicolson steps on the coupled LU (tdse_spline.hip, tdse_spline_wide.hip);
 //   bspatom_tdse_split / _dev, _observe / _observe_dev: split steps, nch one-wave systems per substep (tdse_split.hip);
 //   bspatom_spline_expect / _dev: <c| B (x) G |c> on packets (spline_expect.hip), one measurement (ExpectPlan).
+//   bspatom_spline_window / _dev: the window operator on packets (include/bspatom_spline_window.h, spline_window.hip), one launch.
 // The eight stepped entry points run through one skeleton, SteppedRun: the rules of the arguments they share, the sizes, the host
 // variant's staging groups, the loop over them with its copies, the last row, drain.  A flavour (tdse_spline_impl with its wide flag,
 // tdse_split_impl with its nexp) makes the checks particular to it, sets up its slots, scratch and kernel arguments, and hands over
@@ -252,6 +253,74 @@ static int spline_expect_impl(bspatom_problem *p, int nscan, int nch, int nexp, 
     return drain(p, rc);
 }
 
+// bspatom_spline_window / _dev: one launch over the items (energy, distinct band, block of that band's packets).  The channels' distinct
+// bands in the order of their first appearance; a band's packets (q, c) with q, then c ascending, cut into blocks of window_rhs.  The
+// kernel reads the packets as 16-byte complex values: a device pointer that is not so aligned is copied first.  info: the head
+// blocks' counts [ne][ng][nfac], summed here per energy.
+static constexpr int WINDOW_RHS = 8;                               // right-hand sides per factorisation (window_rhs)
+static int spline_window_impl(bspatom_problem *p, int nscan, int nch, const int32_t *l, int ne, int nfac, const double *z, const double *c, double *N,
+                              int32_t *info, bool dev)
+{
+    if (!p || !l || !c || !N || !info || nscan < 1 || nch < 1 || ne < 1 || nfac < 0 || nfac > BSPATOM_WINDOW_MAX_FAC || (nfac > 0 && !z)) return BSP_ERR_ARG;
+    int rc;
+    if ((rc = screen_channels(p, l, nullptr, nch, 0))) return rc;
+    const int n = p->hs.nfun, k = p->hs.k;
+    if ((long long)nch * n > 0x3fffffffLL || (long long)nscan * nch * ne > 0x3fffffffLL) return BSP_ERR_ARG;
+    const int wrhs = opts().window_rhs > 0 ? opts().window_rhs : WINDOW_RHS;
+    std::vector<int> chan, wsel, gchan, grp(nch), rhs, bg, b0, bn, bhead;
+    select_channels(p, l, nullptr, nch, 0, chan, wsel);
+    for (int ch = 0; ch < nch; ++ch) {
+        size_t at = 0;
+        while (at < gchan.size() && gchan[at] != chan[ch]) ++at;
+        if (at == gchan.size()) gchan.push_back(chan[ch]);
+        grp[ch] = (int)at;
+    }
+    const int ng = (int)gchan.size();
+    for (int g = 0; g < ng; ++g) {
+        const int first = (int)rhs.size();
+        for (int q = 0; q < nscan; ++q)
+            for (int ch = 0; ch < nch; ++ch)
+                if (grp[ch] == g) rhs.push_back(q * nch + ch);
+        for (int r0 = first; r0 < (int)rhs.size(); r0 += wrhs) {
+            bg.push_back(g); b0.push_back(r0); bn.push_back(std::min(wrhs, (int)rhs.size() - r0)); bhead.push_back(r0 == first);
+        }
+    }
+    const int nblk = (int)bg.size();
+    if ((long long)ne * nblk > 0x3fffffffLL) return BSP_ERR_ARG;
+    const int items = ne * nblk;
+    const size_t cdoubles = (size_t)2 * nscan * nch * n, ndoubles = (size_t)nscan * nch * ne, ninfo = (size_t)ne * ng * nfac;
+    BSP_HIP(hipSetDevice(p->device));
+    int slots = 0;
+    if ((rc = spline_window_slots(k, items, &slots))) return rc;
+    const size_t slot_doubles = spline_window_slot_doubles(n, k, wrhs);
+    slots = bounded_slots(slots, items, slot_doubles);
+    DevArray<double> work, dz, dc, dN;
+    DevArray<int> dgchan, drhs, dbg, db0, dbn, dbhead, dinfo;
+    const bool copy = !dev || (reinterpret_cast<uintptr_t>(c) & 15) != 0;
+    if ((rc = work.alloc((size_t)slots * slot_doubles)) || (rc = nfac > 0 ? dz.put(z, (size_t)2 * ne * nfac) : dz.alloc(1)) || (rc = dgchan.put(gchan.data(), ng)) ||
+        (rc = drhs.put(rhs.data(), rhs.size())) || (rc = dbg.put(bg.data(), nblk)) || (rc = db0.put(b0.data(), nblk)) ||
+        (rc = dbn.put(bn.data(), nblk)) || (rc = dbhead.put(bhead.data(), nblk)) || (rc = dinfo.alloc(ninfo)) ||
+        (copy && (rc = dc.alloc(cdoubles))) || (!dev && (rc = dN.alloc(ndoubles)))) return rc;
+    std::vector<int> hinfo(ninfo);
+    rc = HIP_RC(hipMemsetAsync(dinfo.p, 0, std::max<size_t>(ninfo, 1) * sizeof(int), p->st));
+    if (!rc && copy) rc = HIP_RC(hipMemcpyAsync(dc.p, c, cdoubles * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, p->st));
+    SplineWindowArgs a = {};
+    a.n = n; a.k = k; a.ne = ne; a.nfac = nfac; a.ng = ng; a.nblk = nblk; a.wrhs = wrhs;
+    a.SB = p->d_SB; a.HB = p->d_HB;
+    a.gchan = dgchan.p; a.rhs = drhs.p; a.bg = dbg.p; a.b0 = db0.p; a.bn = dbn.p; a.bhead = dbhead.p;
+    a.z = dz.p; a.c = copy ? dc.p : c; a.N = dev ? N : dN.p; a.info = dinfo.p; a.work = work.p;
+    if (!rc) rc = launch_spline_window(a, slots, p->st);
+    if (!rc && !dev) rc = HIP_RC(hipMemcpyAsync(N, dN.p, ndoubles * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    if (!rc && ninfo > 0) rc = HIP_RC(hipMemcpyAsync(hinfo.data(), dinfo.p, ninfo * sizeof(int), hipMemcpyDeviceToHost, p->st));
+    if ((rc = drain(p, rc))) return rc;
+    for (int e = 0; e < ne; ++e) {
+        int sum = 0;
+        for (size_t i = 0; i < (size_t)ng * nfac; ++i) sum += hinfo[(size_t)e * ng * nfac + i];
+        info[e] = sum;
+    }
+    return BSP_OK;
+}
+
 // bspatom_tdse_split / _dev: a step is three launches over the nscan * nch one-wave systems -- atomic half step, field step, atomic
 // half step -- on two packet buffers that alternate; the atomic matrices are factored once, one per distinct (l, w).  The launches of
 // tdse_split_group steps are enqueued, then waited for; the kernels take the place of a step's row and snapshot.  With nexp > 0
@@ -404,3 +473,6 @@ extern "C" int bspatom_tdse_split_observe_dev(SPLIT_PARAMS, int nexp, const doub
 #define EXPECT_PARAMS bspatom_problem *p, int nscan, int nch, int nexp, const double *B, const double *GE, const double *c, double *e
 extern "C" int bspatom_spline_expect(EXPECT_PARAMS) { return spline_expect_impl(p, nscan, nch, nexp, B, GE, c, e, false); }
 extern "C" int bspatom_spline_expect_dev(EXPECT_PARAMS) { return spline_expect_impl(p, nscan, nch, nexp, B, GE, c, e, true); }
+#define WINDOW_PARAMS bspatom_problem *p, int nscan, int nch, const int32_t *l, int ne, int nfac, const double *z, const double *c, double *N, int32_t *info
+extern "C" int bspatom_spline_window(WINDOW_PARAMS) { return spline_window_impl(p, nscan, nch, l, ne, nfac, z, c, N, info, false); }
+extern "C" int bspatom_spline_window_dev(WINDOW_PARAMS) { return spline_window_impl(p, nscan, nch, l, ne, nfac, z, c, N, info, true); }

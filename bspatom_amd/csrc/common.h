@@ -130,6 +130,8 @@ struct Options {
                                  // of its host variant (0 = 2048); one slot and one matrix at least; results do not depend on it (the test's hook)
     int resolvent_slots = 0;     // BSP_RESOLVENT_SLOTS: > 0 = work slots (resident waves) of resolvent_kernel, 0 = the occupancy query x CUs;
                                  // results do not depend on it (the test's hook)
+    int window_rhs = 0;          // BSP_WINDOW_RHS: > 0 = right-hand sides that one factorisation of bspatom_spline_window serves in one work item (0 = 8);
+                                 // results do not depend on it (the test's hook; 1 = a factorisation per packet, the measurement's baseline)
     int ktime = 0;               // 1: HIP events around every launch of the kernels in KSlot (bspatom_kernel_times; bench.py's
                                  // per-kernel roofline entries are measured with it in one extra, untimed step)
 };
@@ -484,6 +486,23 @@ int spline_expect_slots(int items, int *slots);
 int launch_spline_expect(const SplineExpectArgs &a, int slots, hipStream_t st);
 // out [nrows][rw0 + 2 nexp] = row0 [nrows][rw0] beside e [nrows][2 nexp]: the rows of bspatom_tdse_split_observe
 int launch_spline_expect_rows(double *out, const double *row0, const double *e, int rw0, int nexp, int nrows, hipStream_t st);
+// spline_window.hip: N(q, c, e) = x^H S x, x = prod_j (H_l - z_{e,j} S)^-1 S applied to packet (q, c) (bspatom_spline_window).  The
+// channels' ng distinct bands: gchan [ng], the place in HB.  rhs: the packets q * nch + c grouped by band; block blk of the nblk
+// blocks is bn[blk] <= wrhs of them from rhs[b0[blk]] on, all of band bg[blk]; bhead[blk]: the first block of its band.  An item is
+// (e, blk).  z: [ne][nfac] complex; c: [nscan][nch][n] complex, 16-byte aligned; N: [nscan][nch][ne]; info: [ne][ng][nfac], the
+// replaced pivots of every factorisation, written by the head blocks.  work: slots * spline_window_slot_doubles(n, k, wrhs).
+struct SplineWindowArgs {
+    int n, k, ne, nfac, ng, nblk, wrhs;
+    const double *SB, *HB;
+    const int *gchan, *rhs, *bg, *b0, *bn, *bhead;
+    const double *z, *c;
+    double *N;
+    int *info;
+    double *work;
+};
+size_t spline_window_slot_doubles(int n, int k, int wrhs);
+int spline_window_slots(int k, int items, int *slots);
+int launch_spline_window(const SplineWindowArgs &a, int slots, hipStream_t st);
 int launch_wf_tabulate(int nkp, int k, int n, const double *d_rt, const double *d_c, double ra,
                        double rb, int npts, double *d_r, double *d_u, int *d_status, hipStream_t st);
 // wavefn.hip: u(r), u'(r) of blocks of coefficient vectors (bspatom_tabulate, bspatom_wavefunctions)

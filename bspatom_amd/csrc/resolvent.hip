@@ -27,6 +27,7 @@
 #include "wave_ops.h"
 #include "resolvent_shared.h"
 #include "band_lu_wave.h"
+#include "resolvent_pencil.h"
 
 #pragma clang fp contract(off)             // every multiply-add of this file is written out
 
@@ -34,38 +35,7 @@ namespace bsp {
 namespace {
 constexpr int RS_BMAX = 15;                // half-bandwidth limit (k <= 16)
 // (sums of wave_ops.h: wave_sum32 over lanes 0 .. 31 -- the callers' terms are zero beyond lane 2 b <= 30 --, wave_sum over all)
-// doubles of one slot's scratch, even (a slot starts on a 16-byte boundary)
-__host__ __device__ inline size_t rs_slot_doubles(int n, int k)
-{
-    const size_t b = (size_t)k - 1, piv = ((size_t)n + 1) / 2;
-    return 2 * ((size_t)n * (2 * b + 1) + (size_t)n * b + (size_t)n) + piv + (piv & 1);
-}
-
-// The matrix of an item, wave_lu_factor's argument.  SB, HB upper bands [k][n] used symmetrically (eigvec.hip::pencil_entry), WB the
-// absorber's FULL band [2k-1][n] with WB[d + b][i] = W(i, i + d), both triangles as given, or null.  entry: M(r, c); diag: |M(j,j)| by
-// cabs1 and the sum of the magnitudes of its terms (rs_pertol).  h - zr s and -(zi s) - w round once.
-struct RsPencil {
-    const double *SB, *HB, *WB;
-    int n, b;
-    double zr, zi;
-    __device__ __forceinline__ void entry(int r, int c, double &re, double &im) const
-    {
-        const int d = (r > c) ? (r - c) : (c - r);
-        re = 0.0; im = 0.0;
-        if (d > b || r < 0 || c < 0 || r >= n || c >= n) return;
-        const int lo = (r > c) ? c : r;
-        const double s = SB[(size_t)d * n + lo];
-        re = __builtin_fma(-zr, s, HB[(size_t)d * n + lo]);
-        im = -(zi * s);
-        if (WB) im = im - WB[(size_t)(c - r + b) * n + r];
-    }
-    __device__ __forceinline__ void diag(int j, double &mag, double &flo) const
-    {
-        const double s = SB[j], h = HB[j], wv = WB ? WB[(size_t)b * n + j] : 0.0;
-        mag = fabs(__builtin_fma(-zr, s, h)) + fabs(__builtin_fma(-zi, s, -wv));
-        flo = (fabs(h) + fabs(zr * s)) + (fabs(zi * s) + fabs(wv));
-    }
-};
+// (the slot's scratch rs_slot_doubles and the matrix of an item, RsPencil: resolvent_pencil.h, which spline_window.hip includes too)
 
 // y <- A x, A = sum_o ac[o] G_o: the right-hand side of a chain's next stage (include/bspatom.h: bspatom_resolvent_chain).  GB: nop
 // full bands [2b+1][n], GB[(d + b) n + i] = G(i, i + d).  Lane-strided over the rows; an entry is t = ac[0] G_0, then t = t + ac[o] G_o

@@ -1240,6 +1240,61 @@ def hhg_spectrum(d, dt_rows, window="hann", kind="dipole"):
     return omega, np.abs(xt) ** 2
 
 
+# ---- photoelectron spectra of spline packets: the window operator (Problem.spline_window) -------------------------------------
+def _window_integral(m):
+    """I_m = integral of 1 / (x^(2m) + 1) over the real line = pi / (m sin(pi / 2m))"""
+    import numpy as np
+    return np.pi / (m * np.sin(np.pi / (2 * m)))
+
+
+def window_shifts(E, gamma, m):
+    """The shifts of the window operator of order m for Problem.spline_window: z[e, j] = E[e] + gamma exp(i pi (2j + 1) / (2m)),
+    j < m, the roots of (lambda - E)^(2m) + gamma^(2m) in the upper half plane (their conjugates are the other m):
+    prod_j (lambda - z_j)(lambda - conj z_j) = (lambda - E)^(2m) + gamma^(2m).  E: energies (ne,) or a scalar; returns complex (ne, m)."""
+    import numpy as np
+    m = int(m)
+    if m < 1 or not float(gamma) > 0.0:
+        raise ValueError("window_shifts: order m = %r >= 1 and width gamma = %r > 0 are needed" % (m, gamma))
+    E = np.atleast_1d(np.asarray(E, dtype=np.float64))
+    ph = np.exp(1j * np.pi * (2 * np.arange(m) + 1) / (2 * m))
+    return np.ascontiguousarray(E[:, None] + float(gamma) * ph[None, :])
+
+
+def window_spectrum(prob, l, c, E, gamma, m=2):
+    """P_m(E) = <c| gamma^(2m) / ((H_l - E)^(2m) + gamma^(2m)) |c> per scan, channel and energy: (nscan, nch, ne), or (nch, ne) for one
+    packet -- the part of every channel's packet within about gamma of E, sum_n |<n|c>|^2 gamma^(2m) / ((E_n - E)^(2m) + gamma^(2m))
+    over the box states of that channel, from m banded solves per energy instead of the eigenvectors (Problem.spline_window with
+    window_shifts).  The packets must come from a run WITHOUT an absorber on a box that still holds them: the window needs a
+    Hermitian H.  Raises RuntimeError if a pivot had to be replaced (it cannot with gamma > 0)."""
+    import numpy as np
+    N, info = prob.spline_window(l, c, window_shifts(E, gamma, m))
+    if np.any(info != 0):
+        raise RuntimeError("window_spectrum: replaced pivots at energies %s" % np.flatnonzero(info))
+    return float(gamma) ** (2 * int(m)) * N
+
+
+def window_density(P, gamma, m):
+    """dP/dE = P / (gamma I_m), I_m = pi / (m sin(pi / 2m)): a window of order m has the area gamma I_m, so that the integral of the
+    density over all energies is the norm c^H S c of the packet (for energy grids finer than gamma)"""
+    import numpy as np
+    return np.asarray(P, dtype=np.float64) / (float(gamma) * _window_integral(int(m)))
+
+
+def window_yield(P, E, gamma, m, emin=0.0):
+    """The trapezoid integral of window_density(P, gamma, m) over the energies E >= emin, per scan and channel: P (..., ne) on the
+    ascending grid E (ne,).  With emin = 0 and a grid that covers the continuum of the box, the ionisation yield per channel."""
+    import numpy as np
+    E = np.asarray(E, dtype=np.float64).reshape(-1)
+    D = window_density(P, gamma, m)
+    if D.shape[-1] != E.size or np.any(np.diff(E) <= 0.0):
+        raise ValueError("window_yield: P (..., %d) needs an ascending energy grid of that length, got %d" % (D.shape[-1], E.size))
+    keep = E >= float(emin)
+    if np.count_nonzero(keep) < 2:
+        return np.zeros(D.shape[:-1])
+    Ek, Dk = E[keep], D[..., keep]
+    return np.sum(0.5 * (Dk[..., 1:] + Dk[..., :-1]) * np.diff(Ek), axis=-1)
+
+
 def spline_yield(obs, nch=None):
     """1 - sum_c N_c of every row of Problem.tdse_spline, (nobs, nscan): with an absorber and a packet normalised to c^H S c = 1, the
     ionisation yield so far.  nch: the channels, when the rows carry projections behind the norms (default: every column is a norm)."""

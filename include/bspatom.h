@@ -667,6 +667,9 @@ int bspatom_tdse_adaptive_dev(bspatom_problem *p, int nch, int count, const doub
 /* Expectation values <c| B (x) G |c> on packets in the spline basis -- the induced dipole, the dipole acceleration -- in a call of
  * their own and as further row entries along a split-step run: bspatom_spline_expect.h, a part of this header like the two above. */
 #include "bspatom_spline_expect.h"
+/* How a packet in the spline basis is distributed over energy -- photoelectron spectra by the window operator, a product of resolvents
+ * with the S-norm at its end --: bspatom_spline_window.h, a fourth part of this header, with its guarantees W1 - W6. */
+#include "bspatom_spline_window.h"
 
 /* The eigenvector the reference consumes (l_ini, n0_ini; matrices.f90:267) is computed during bspatom_solve when its channel is in
  * the batch.  On the band route its eigenvalue comes from the pencil's inertia right after the assembly (csrc/bandsect.hip), and the
